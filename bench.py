@@ -7,7 +7,7 @@ gfx950 checksum kernel — over one batch (config c3_1500B: 2^20 packets x 1500 
 per GPU, already resident in HBM).  value = payload bytes checksummed by all
 ranks / max-over-ranks wall time of the K timed steps / 2^30.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3_1500B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c3_1500B] [--dump-outputs DIR] [--full]
         (N > 1 without a launcher: bench.py starts N ranks under torch.distributed.run itself,
          as a child process, and exits with its code)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -19,6 +19,14 @@ aggregate.  At N>1 the line also carries the §8(e) collective leg measured
 separately: `value_gather` = the same steps with one RCCL all-gather of every
 rank's u16 results (as uint8, 2 B per packet) per step, and `gather_ms` = the
 all-gather alone.  Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`,
+`ms_per_step`, the roofline of the timed steps).  Everything that takes runs of its own
+comes with --full: the CPU baseline, the PCIe-inclusive host pipeline, the isolated
+one-stream re-measurement, the oracle parity checks and, at N>1, the collective legs.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32),
+so two builds can be compared output for output (the inputs are seeded: the same
+arguments give the same bytes).
 
 Descriptors (--desc auto): the packed form (rns_csum_batch_packed_dev: u16 length and
 u16 seed per packet, one u64 offset per 64 packets; the synthetic batches are packed at
@@ -76,11 +84,23 @@ def parse_args(argv=None):
                         "auto = strided for tiny equal-length packets (c2), packed otherwise (u16 lengths: packets "
                         "above 65535 B take 32 below 4 GiB, else 64)")
     p.add_argument("--shape", default="", help="variant,G,U,max_blocks kernel shape override (tuning)")
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample duration (single thread)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-host-pipeline", action="store_true", help="skip the PCIe-inclusive extra measurement")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the legs that take runs of their own: the CPU baseline, the "
+                        "PCIe-inclusive host pipeline, the isolated one-stream re-measurement, the oracle parity "
+                        "checks and, at N>1, the collective legs (the --no-* options below drop single legs of it)")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps write what the last of them computed (the arrays its caller receives: "
+                        "per-packet checksums; verify: statuses; finalize: statuses and the finalized head fragments) "
+                        "as DIR/<name>.npy in float32, at most 64 MB in all (larger outputs: a fixed seeded sample of "
+                        "rows, its indices beside it); at N>1 every rank writes DIR/<name>.rank<r>.npy")
+    p.add_argument("--cpu-seconds", type=float, default=10.0,
+                   help="--full: CPU baseline sample duration (single thread)")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    p.add_argument("--no-host-pipeline", action="store_true",
+                   help="--full without the PCIe-inclusive extra measurement")
     p.add_argument("--no-gather", action="store_true",
-                   help="N>1: skip the compute+all-gather and gather-only legs (value is compute-only either way)")
+                   help="--full at N>1 without the compute+all-gather and gather-only legs (value is compute-only "
+                        "either way)")
     p.add_argument("--median-launches", type=int, default=0,
                    help="diagnostic: N extra launches each inside its own event pair, median reported "
                         "(pairs add ~5 us per launch; 0 = skip)")
@@ -203,11 +223,13 @@ def clock_ramp(engine, seconds: float, step=None, graph=None) -> int:
     step = step or engine.step
     n, t0 = 0, time.perf_counter()
     while time.perf_counter() - t0 < seconds:
+        if graph is not None:  # one replay is already K steps: look at the clock after each
+            graph.replay()
+            engine.sync()
+            n += 1
+            continue
         for _ in range(8):
-            if graph is not None:
-                graph.replay()
-            else:
-                step()
+            step()
         engine.sync()
         n += 8
     return n
@@ -876,6 +898,47 @@ def shard_leg(engine, args) -> dict:
                                           "(no peer GPU on a 1-GPU box), mean of 20"}}
 
 
+DUMP_MAX_BYTES = 60_000_000  # --dump-outputs: all files of one rank together stay below 64 MB
+DUMP_SAMPLE_SEED = 0x5EEDC0DE
+
+
+def dump_outputs(engine, dist, outdir: str) -> dict:
+    """--dump-outputs: the arrays the last timed step left for its caller, read back from the
+    batch that step ran on (engine.last) before any other leg runs, as float32 .npy files.
+    An array that does not fit its share of DUMP_MAX_BYTES is cut to a fixed seeded sample
+    of its rows (sorted indices, the same for every run), written beside it as <name>_rows."""
+    import numpy as np
+    torch = engine.torch
+    b = engine.last
+    op = getattr(engine, "op", "csum")
+    if op == "finalize":
+        n = b.layout.n
+        head = b.layout.head
+        arrays = {"status": b.status, "heads": b.arena[:n * head].view(n, head)}
+    elif op == "verify":
+        arrays = {"status": b.status}
+    else:
+        arrays = {"checksums": b.out.view(torch.int16)}
+    os.makedirs(outdir, exist_ok=True)
+    suffix = f".rank{dist.rank}" if dist.world > 1 else ""
+    budget = DUMP_MAX_BYTES // len(arrays) // 4  # float32 elements per array
+    written = {}
+    for name, t in arrays.items():
+        rows = int(t.shape[0])
+        per_row = int(t.numel() // rows) if rows else 1
+        if rows * per_row > budget:
+            keep = max(1, budget // (per_row + 2))  # room for the float64 index file too
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(rows, size=keep, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+            np.save(os.path.join(outdir, f"{name}_rows{suffix}.npy"), idx.astype(np.float64))
+        a = t.cpu().numpy()
+        if a.dtype == np.int16:
+            a = a.view(np.uint16)
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), a.astype(np.float32))
+        written[name] = list(a.shape)
+    return written
+
+
 class _NoDist:
     """Single-process stand-in for Dist (the isolated re-measurement needs no barrier)."""
     enabled = False
@@ -954,6 +1017,8 @@ def main(argv=None):
     strong = args.scaling == "strong" or (args.scaling == "auto" and args.config == "c5_imix")
     verify = args.op == "verify"
     finalize = args.op == "finalize"
+    if not args.full:  # a plain run: set up, warm up, time the K steps, print the line
+        args.no_cpu_baseline = args.no_host_pipeline = args.no_gather = True
     if verify:
         args.no_cpu_baseline = args.no_host_pipeline = True  # the headline's CPU legs; not this mode's
     if finalize:
@@ -987,13 +1052,14 @@ def main(argv=None):
     ramp_steps = clock_ramp(engine, args.ramp_s, graph=graph) if args.ramp_s > 0 else 0
     r = timed_loop(engine, dist, args.steps, args.warmup, graph=graph)
     elapsed = r["elapsed_s"]
+    dumped = dump_outputs(engine, dist, args.dump_outputs) if args.dump_outputs else None
     # all ranks' payload (strong: the shards add up to the config's one batch)
     step_bytes = int(dist.sum(engine.payload_bytes))
     total_bytes = step_bytes * args.steps
     value = total_bytes / elapsed / 2 ** 30
     kernel_ms = r["kernel_ms"]
     isolated = None
-    if use_graph and args.graph_streams > 1:
+    if args.full and use_graph and args.graph_streams > 1:
         # the same K launches one after another on ONE stream, as a graph too (no host launch cost;
         # untimed for `value`): the per-dispatch duration rocprof reports, next to the pipelined
         # per-step time above
@@ -1023,6 +1089,7 @@ def main(argv=None):
         "launches_before_timed": ramp_steps * (args.steps if graph else 1)
         + ((args.steps if args.warmup else 0) if graph else args.warmup),
         "ms_per_step": round(elapsed * 1e3 / args.steps, 4),
+        "full": bool(args.full),
         "higher_is_better": True,
         "scaling": "strong" if strong else "weak",
         "vs_baseline": None,
@@ -1079,8 +1146,9 @@ def main(argv=None):
             "kernel_avg_us": round(kernel_us, 2),
             "frac_from": ("kernel_avg_us: one event pair (capture stream) around the graph replay of the K timed "
                           "launches / K — consecutive steps overlap on " + str(args.graph_streams) + " streams, so "
-                          "this is the per-step time, shorter than one dispatch (isolated below)"
-                          if isolated is not None else
+                          "this is the per-step time, shorter than one dispatch (" +
+                          ("isolated below)" if isolated is not None else "--full adds the isolated figure)")
+                          if use_graph and args.graph_streams > 1 else
                           "kernel_avg_us: one event pair (launch stream) around the K back-to-back timed launches / K"),
             "algorithmic_bytes_per_launch": algo_bytes,
             "descriptor_bytes_per_launch": desc_bytes,
@@ -1103,6 +1171,8 @@ def main(argv=None):
             "launches": args.steps,
             "how": "after the timed region: the same K launches as a graph on ONE stream (no overlap), one event "
                    "pair / K (what rocprof's per-dispatch durations measure)"}
+    if dumped is not None:
+        line["dumped_outputs"] = dumped
     if per:
         srt = sorted(per)
         line["roofline"]["evpair_median_us"] = round(srt[len(srt) // 2], 2)
@@ -1151,7 +1221,7 @@ def main(argv=None):
             "value_gather_overlap": "eager; step i's all-gather on a side stream under step i+1's kernel "
                                     "(OverlappedGather, DESIGN §6)",
             "gather_ms": "eager; the all-gather alone, per step"}
-    if finalize:
+    if finalize and args.full:
         # every rank: its first batch's heads against the CPU restatement; rank 0 then times it
         par = finalize_parity(engine, threads=max(1, min(8, cpu_grant()["threads"])))
         par.pop("arena", None)
@@ -1167,7 +1237,7 @@ def main(argv=None):
         if dist.rank == 0 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline_finalize(engine, args.cpu_seconds)
         dist.barrier()
-    if dist.world > 1 and not verify and not finalize:
+    if dist.world > 1 and not verify and not finalize and args.full:
         # after every rank's GPU legs: each rank checks its own results; rank 0 times the CPU
         # baseline on its own batch while the others wait (benches/util_bench.rs:20-45 beside
         # the N-GPU figure, on the same box's host cores, in the same run)

@@ -73,7 +73,7 @@ class CpuEngine(bench.GpuEngine):
 
 bench.GpuEngine = CpuEngine
 line = bench.main(["--gpus", "2", "--config", {config!r}, "--steps", "3", "--warmup", "1", "--median-launches", "3",
-                   "--traffic-json", "/nonexistent/{{config}}.json", "--cpu-seconds", "0.5"])
+                   "--traffic-json", "/nonexistent/{{config}}.json", "--full", "--cpu-seconds", "0.5"])
 if line is None:   # the launching parent (bench.py --gpus 2 without torchrun): the ranks did the work
     sys.exit(0)
 eng = ENGINES[0]
@@ -162,6 +162,50 @@ def test_two_rank_gloo_bench_main(tmp_path, oracle, config, n, launch):
         assert np.array_equal(np.array(res[rank]["gathered"], dtype=np.uint16), expect)
 
 
+# the same CPU engine under a plain run (no --full) that dumps its outputs
+PLAIN_WORKER = WORKER.split("bench.GpuEngine = CpuEngine")[0] + r'''
+bench.GpuEngine = CpuEngine
+line = bench.main(["--gpus", "2", "--config", {config!r}, "--steps", "3", "--warmup", "1", "--ramp-s", "0",
+                   "--traffic-json", "/nonexistent/{{config}}.json", "--dump-outputs", os.path.join({outdir!r}, "dump")])
+assert ENGINES[0].gatherer is None   # no collective leg ran
+'''
+
+
+def test_two_rank_gloo_plain_run_dumps_outputs(tmp_path, oracle):
+    """Without --full a two-rank run times its steps and prints the line: no gather legs, no CPU
+    baseline, no parity leg.  --dump-outputs: every rank writes the checksums its last step left
+    (DIR/checksums.rank<r>.npy, float32), equal to the oracle's over that rank's batch."""
+    import numpy as np
+
+    from oracle.oracle import splitmix64_bytes
+    from rustnetworkstack_amd.workloads import make_layout
+    config, n = "c3_1500B", 2000
+    script = tmp_path / "worker.py"
+    script.write_text(PLAIN_WORKER.format(root=ROOT, n=n, config=config, outdir=str(tmp_path)))
+    env = dict(os.environ, OMP_NUM_THREADS="1", RNS_BENCH_BACKEND="gloo")  # CPU ranks, also on a GPU host
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
+        env.pop(k, None)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
+           "--master-addr=127.0.0.1", f"--master-port={free_port()}", str(script)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=str(tmp_path))
+    assert r.returncode == 0, r.stderr[-3000:]
+    printed = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(printed) == 1
+    line = printed[0]
+    assert line["full"] is False and line["n_gpus"] == 2 and line["steps"] == 3
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "GiB/s"
+    for k in ("value_gather", "value_compute_eager", "gather_ms", "legs", "parity", "host_inclusive"):
+        assert k not in line, k
+    assert line["cpu_baseline"] is None
+    assert line["dumped_outputs"] == {"checksums": [n]}
+    for rank in (0, 1):
+        lay = make_layout(config, n=n, data_seed=0x5EEDC0DE + 0x1000 * rank)
+        arena = splitmix64_bytes(lay.data_seed, lay.arena_bytes)
+        want = oracle.batch(arena, lay.off, lay.length, lay.seed, complement=True)
+        got = np.load(tmp_path / "dump" / f"checksums.rank{rank}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, want.astype(np.float32))
+
+
 VERIFY_WORKER = r'''
 import json, os, sys, time
 sys.path.insert(0, {root!r})
@@ -232,7 +276,7 @@ class CpuVerifyEngine(bench.GpuEngine):
         return "cpu stand-in"
 
 bench.GpuEngine = CpuVerifyEngine
-line = bench.main(["--gpus", "2", "--config", {config!r}, "--op", "verify", "--steps", "2", "--warmup", "1",
+line = bench.main(["--gpus", "2", "--config", {config!r}, "--op", "verify", "--steps", "2", "--warmup", "1", "--full",
                    "--traffic-json", "/nonexistent/{{config}}.json"])
 rank = int(os.environ["RANK"])
 with open(os.path.join({outdir!r}, f"rank{{rank}}.json"), "w") as f:
@@ -335,7 +379,7 @@ class CpuFinalizeEngine(bench.GpuEngine):
 
 bench.GpuEngine = CpuFinalizeEngine
 line = bench.main(["--gpus", "2", "--config", {config!r}, "--op", "finalize", "--steps", "2", "--warmup", "1",
-                   "--cpu-seconds", "0.2", "--ramp-s", "0"])
+                   "--full", "--cpu-seconds", "0.2", "--ramp-s", "0"])
 rank = int(os.environ["RANK"])
 with open(os.path.join({outdir!r}, f"rank{{rank}}.json"), "w") as f:
     json.dump({{"rank": rank, "line": line}}, f)

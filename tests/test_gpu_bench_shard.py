@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("shard", ["0/8", "7/8"])
 def test_bench_c5_shard_of_8(shard):
     line = bench.main(["--config", "c5_imix", "--shard", shard, "--steps", "4", "--warmup", "1", "--ramp-s", "0",
-                       "--cpu-seconds", "1", "--no-host-pipeline", "--traffic-json", "/nonexistent/{config}.json"])
+                       "--full", "--cpu-seconds", "1", "--no-host-pipeline", "--traffic-json", "/nonexistent/{config}.json"])
     from rustnetworkstack_amd.workloads import make_layout
     r, n = (int(x) for x in shard.split("/"))
     lay = make_layout("c5_imix", shard=(r, n))
@@ -52,7 +52,30 @@ def test_bench_c2_strided_form():
     """--desc strided (rns_csum_batch_strided_dev: no offset/length descriptors) on the c2
     config: the CPU-baseline leg re-checks the rotating batches' results against the oracle."""
     line = bench.main(["--config", "c2_64B", "--desc", "strided", "--steps", "24", "--warmup", "1", "--ramp-s", "0",
-                       "--cpu-seconds", "1", "--no-host-pipeline", "--traffic-json", "/nonexistent/{config}.json"])
+                       "--full", "--cpu-seconds", "1", "--no-host-pipeline", "--traffic-json", "/nonexistent/{config}.json"])
     assert line["config"]["descriptors"].startswith("strided")
     assert line["roofline"]["descriptor_bytes_per_launch"] == 2 * (1 << 20)
     assert line["cpu_baseline"]["gpu_sample_bit_exact"] is True
+
+
+def test_plain_run_times_the_steps_only_and_dumps_the_last_step(tmp_path, oracle):
+    """A run without --full carries the headline fields and none of the legs that take runs of
+    their own; --dump-outputs writes the checksums of the batch the LAST timed step ran on
+    (c2 rotates 12 batches: step 5 of 5 ran on batch 4), equal to the oracle's for every packet,
+    and a second run with the same arguments writes the same file."""
+    from oracle.oracle import splitmix64_bytes
+    from rustnetworkstack_amd.workloads import DATA_SEED, make_layout
+    dumps = []
+    for sub in ("a", "b"):
+        line = bench.main(["--config", "c2_64B", "--steps", "5", "--warmup", "1", "--ramp-s", "0",
+                           "--dump-outputs", str(tmp_path / sub), "--traffic-json", "/nonexistent/{config}.json"])
+        assert line["full"] is False and line["steps"] == 5 and line["ms_per_step"] > 0
+        assert line["cpu_baseline"] is None and "host_inclusive" not in line and "parity" not in line
+        assert "isolated" not in line["roofline"]
+        assert line["dumped_outputs"] == {"checksums": [1 << 20]}
+        dumps.append(np.load(tmp_path / sub / "checksums.npy"))
+    assert dumps[0].dtype == np.float32 and np.array_equal(dumps[0], dumps[1])
+    lay = make_layout("c2_64B", data_seed=DATA_SEED + 4)
+    arena = splitmix64_bytes(lay.data_seed, lay.arena_bytes)
+    want = oracle.batch(arena, lay.off, lay.length, lay.seed, complement=True, check=False)
+    assert np.array_equal(dumps[0], want.astype(np.float32))

@@ -43,7 +43,7 @@ def test_bench_finalize_line(config):
     heads and statuses equal the C restatement of the transmit path run on a host copy, and the
     line carries the roofline and the CPU baseline of that restatement."""
     line = bench.main(["--config", config, "--op", "finalize", "--steps", "6", "--warmup", "1", "--ramp-s", "0",
-                       "--cpu-seconds", "1"])
+                       "--full", "--cpu-seconds", "1"])
     assert line["metric"] == bench.METRIC_FINALIZE
     assert line["parity"]["bit_exact_all_ranks"] and line["parity"]["packets_checked"] > 0
     assert line["roofline"]["kernel"].startswith("csum_txrows_kernel FIN")

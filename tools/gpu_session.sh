@@ -38,7 +38,7 @@ fi
 # the driver's command, profiled: the bench line and the kernel trace come from ONE run
 cd /tmp
 step bench_prof 900 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-     python3 "$ROOT/bench.py" --gpus 1 --steps "$STEPS" --warmup "$WARMUP" --config "$CONFIG"
+     python3 "$ROOT/bench.py" --gpus 1 --steps "$STEPS" --warmup "$WARMUP" --config "$CONFIG" --full
 cd "$ROOT"
 python tools/profile_bench.py --trace "$OUT/prof/run_kernel_trace.csv" --stats "$OUT/prof/run_kernel_stats.csv" \
      --bench "$OUT/bench_prof.log" --out "$OUT/rocprof_bench_$CONFIG.json" --timed-stats-out "$OUT/rocprof_bench_${CONFIG}_timed_stats.csv" > "$OUT/profile_bench.log" 2>&1

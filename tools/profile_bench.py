@@ -3,7 +3,7 @@
 On the GPU box (tools/gpu_session.sh does this):
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o run -- \\
-        python3 bench.py --gpus 1 --steps 20 --warmup 5 > bench.log
+        python3 bench.py --gpus 1 --steps 20 --warmup 5 --full > bench.log
 
 then here (or there):
 
@@ -73,7 +73,7 @@ def main():
 
     out = {
         "command": "rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py "
-                   f"--gpus 1 --steps {K} --warmup {b['warmup']}",
+                   f"--gpus 1 --steps {K} --warmup {b['warmup']}" + (" --full" if b.get("full") else ""),
         "untimed_launches_skipped": W,
         "kernel": name,
         "grid_size_x": grid,
