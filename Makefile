@@ -11,12 +11,20 @@ LIB      := $(PKG)/librns_checksum.so
 
 CABI_TEST := tests/c/test_batch_abi
 
-all: $(LIB) oracle $(CABI_TEST)
+CABI_TXCP_TEST := tests/c/test_tx_chain_packed_abi
+
+all: $(LIB) oracle $(CABI_TEST) $(CABI_TXCP_TEST)
 
 # A plain C caller of the C ABI (no torch): built here, run by tests/test_c_caller.py on a GPU.
 $(CABI_TEST): tests/c/test_batch_abi.c oracle/csum_oracle.c include/rns_checksum.h $(LIB)
 	gcc -std=gnu11 -O1 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include \
 	    tests/c/test_batch_abi.c oracle/csum_oracle.c -L$(PKG) -lrns_checksum -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
+	    -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread -o $@
+
+# The same for the compact-descriptor chain finalize: run by tests/test_c_caller_tx_chain_packed.py.
+$(CABI_TXCP_TEST): tests/c/test_tx_chain_packed_abi.c oracle/csum_oracle.c include/rns_checksum.h $(LIB)
+	gcc -std=gnu11 -O1 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include \
+	    tests/c/test_tx_chain_packed_abi.c oracle/csum_oracle.c -L$(PKG) -lrns_checksum -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
 	    -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread -o $@
 
 # One translation unit per kernel family (rns_launch.hpp), compiled in parallel (make -j).
@@ -70,7 +78,7 @@ asm: $(HIP_SRCS)
 	    --cuda-device-only -S ../../../$$f -o $$(basename $$f .hip).s) || exit 1; done
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(CABI_TEST)
+	rm -rf $(BUILD) $(LIB) $(CABI_TEST) $(CABI_TXCP_TEST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle resources asm clean ab

@@ -330,6 +330,43 @@ int rns_tx_fill_packed_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_
 int rns_tx_fill_chain_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_frag_off, const uint32_t *d_frag_len,
                           uint32_t n_frags, const uint32_t *d_first, uint32_t n_pkts, uint8_t *d_status, void *stream);
 
+/* The same finalize over COMPACT descriptors, for the layout a batching transmit path builds
+ * itself: datagram i = [head] or [head, payload], the heads of a 64-datagram block back to back
+ * in a header region and its payloads back to back at 2^pay_align_log2 boundaries in a payload
+ * region, so every offset is implied by the lengths.  Within block b: head 64b starts at
+ * d_head_blk_off[b] and head i where head i-1 ends (no padding); payload 64b starts at
+ * d_pay_blk_off[b] and payload i at the end of payload i-1 rounded up to 2^pay_align_log2 (each
+ * payload occupies its length padded to that alignment; a zero-length payload occupies nothing
+ * and means a head-only datagram).  The blocks' offsets are independent of each other, as in
+ * rns_csum_batch_packed_dev.  Descriptors: 3 B per datagram (u8 head length, u16 payload length)
+ * + 16 B per 64 datagrams — about 3.25 B per datagram against the CSR form's 28 B per
+ * [head, payload] datagram.  With ho_i / po_i the implied offsets, the bytes stored and
+ * d_status[i] (optional) are exactly those of rns_tx_fill_chain_dev for the chain
+ * [(ho_i, head_len_i)] plus [(po_i, pay_len_i)] when pay_len_i > 0: the same RNS_TX_* bits and
+ * rejections (a head that does not hold its IP header, a head of length 0, anything outside the
+ * arena: RNS_TX_MALFORMED, untouched; an L4 field past the head: no L4 fill).  Only head bytes
+ * are written; heads and payloads of different datagrams must not overlap.  A block with a head
+ * past 80 bytes from its 16-byte boundary, or whose payload block offset is not 16-byte aligned
+ * (in memory: arena base + offset), takes the exact per-datagram loop (same results, slower).
+ * pay_align_log2 outside 4..12 or n > RNS_CHAIN_MAX_PACKETS is RNS_E_INVALID. */
+int rns_tx_fill_chain_packed_dev(uint8_t *d_arena, uint64_t arena_bytes,
+                                 const uint64_t *d_head_blk_off, /* offset of the head of datagram 64*b */
+                                 const uint8_t *d_head_len8,     /* head fragment length per datagram, 0..255 */
+                                 const uint64_t *d_pay_blk_off,  /* offset of the payload of datagram 64*b */
+                                 const uint16_t *d_pay_len16,    /* payload length per datagram, 0 = head only */
+                                 uint32_t pay_align_log2,        /* payloads start at 2^this boundaries, 4..12 */
+                                 uint32_t n, uint8_t *d_status, void *stream);
+
+/* Host helper for the compact chain form (CPU only): given the n head and payload lengths, the
+ * payload alignment (4..12) and the first head's and first payload's offsets, writes the
+ * (n + 63) / 64 block offsets of each region, the offsets just past the last head and the last
+ * payload's padded end (*head_end, *pay_end), and optionally (non-NULL) every datagram's head
+ * and payload offset. */
+int rns_tx_chain_packed_layout(const uint8_t *head_len8, const uint16_t *pay_len16, uint64_t n,
+                               uint32_t pay_align_log2, uint64_t head_first_off, uint64_t pay_first_off,
+                               uint64_t *head_blk_off, uint64_t *pay_blk_off, uint64_t *head_off /*opt*/,
+                               uint64_t *pay_off /*opt*/, uint64_t *head_end, uint64_t *pay_end);
+
 /* Tuning entry (bench / tests): explicit kernel shape.  variant bit 0: 0 = group
  * kernel (one lane stores each result), 1 = rounds kernel (a wave owns 64
  * consecutive packets, one coalesced result store); bit 1: nontemporal packet

@@ -623,6 +623,79 @@ def tx_fill_chain(arena: torch.Tensor, frag_off: torch.Tensor, frag_len: torch.T
     return status
 
 
+def tx_chain_packed_layout(head_len, pay_len, pay_align_log2: int = 4, head_first_off: int = 0,
+                           pay_first_off: int = 0):
+    """Offsets of the compact chain form (rns_tx_chain_packed_layout): heads back to back from
+    ``head_first_off``, payloads at 2**pay_align_log2 steps from ``pay_first_off`` (a zero-length
+    payload occupies nothing).  ``head_len`` <= 255, ``pay_len`` <= 65535.  Returns
+    (head_blk_off uint64 [ceil(n/64)], pay_blk_off uint64 [ceil(n/64)], head_off uint64 [n],
+    pay_off uint64 [n], head_end, pay_end)."""
+    hl, pl = np.asarray(head_len), np.asarray(pay_len)
+    if hl.shape != pl.shape or hl.ndim != 1:
+        raise ValueError("head_len and pay_len must be 1-D and of the same size")
+    if hl.size and (int(hl.max()) > 0xFF or int(hl.min()) < 0):
+        raise ValueError("the compact chain form holds u8 head lengths (<= 255)")
+    if pl.size and (int(pl.max()) > 0xFFFF or int(pl.min()) < 0):
+        raise ValueError("the compact chain form holds u16 payload lengths (<= 65535)")
+    if not 4 <= int(pay_align_log2) <= 12:
+        raise ValueError("the compact chain form needs pay_align_log2 in 4..12")
+    h8 = np.ascontiguousarray(hl, dtype=np.uint8)
+    p16 = np.ascontiguousarray(pl, dtype=np.uint16)
+    n = int(h8.size)
+    nb = (n + 63) // 64
+    hblk, pblk = np.zeros(max(nb, 1), dtype=np.uint64), np.zeros(max(nb, 1), dtype=np.uint64)
+    hoff, poff = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+    hend, pend = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    st = _lib.load().rns_tx_chain_packed_layout(h8.ctypes.data, p16.ctypes.data, n, int(pay_align_log2),
+                                                int(head_first_off), int(pay_first_off), hblk.ctypes.data,
+                                                pblk.ctypes.data, hoff.ctypes.data, poff.ctypes.data,
+                                                ctypes.byref(hend), ctypes.byref(pend))
+    _lib.check(st, "rns_tx_chain_packed_layout")
+    return hblk[:nb], pblk[:nb], hoff[:n], poff[:n], int(hend.value), int(pend.value)
+
+
+def tx_fill_chain_packed(arena: torch.Tensor, head_blk_off: torch.Tensor, head_len8: torch.Tensor,
+                         pay_blk_off: torch.Tensor, pay_len16: torch.Tensor, *, pay_align_log2: int = 4,
+                         status: torch.Tensor | None = None) -> torch.Tensor:
+    """Transmit finalize of [head, payload] chains over COMPACT descriptors
+    (rns_tx_fill_chain_packed_dev): u8 head lengths and u16 payload lengths (0 = head only), one
+    head offset and one payload offset per 64 datagrams (see ``tx_chain_packed_layout``) — 3 B per
+    datagram + 16 B per 64 instead of the CSR form's 28 B.  The bytes and the uint8 status per
+    datagram of ``tx_fill_chain`` on the chains the lengths imply."""
+    _require_cuda(arena, "arena", (torch.uint8,))
+    _require_cuda(head_blk_off, "head_blk_off", (torch.int64,))
+    _require_cuda(head_len8, "head_len8", (torch.uint8,))
+    _require_cuda(pay_blk_off, "pay_blk_off", (torch.int64,))
+    _require_cuda(pay_len16, "pay_len16", _U16)
+    n = head_len8.numel()
+    if pay_len16.numel() != n:
+        raise ValueError("head_len8 and pay_len16 must have one entry per datagram each")
+    if head_blk_off.numel() < (n + 63) // 64 or pay_blk_off.numel() < (n + 63) // 64:
+        raise ValueError("head_blk_off and pay_blk_off need one offset per 64 datagrams")
+    if not 4 <= pay_align_log2 <= 12:
+        raise ValueError("the compact chain finalize needs pay_align_log2 in 4..12")
+    if n > _lib.RNS_CHAIN_MAX_PACKETS:
+        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} datagrams per chain call")
+    dev = arena.device
+    for name, t in (("head_blk_off", head_blk_off), ("head_len8", head_len8), ("pay_blk_off", pay_blk_off),
+                    ("pay_len16", pay_len16)):
+        if t.device != dev:
+            raise ValueError(f"{name} is on {t.device}, arena on {dev}")
+    if status is None:
+        status = torch.empty(n, dtype=torch.uint8, device=dev)
+    else:
+        _require_cuda(status, "status", (torch.uint8,))
+        if status.numel() != n or status.device != dev:
+            raise ValueError(f"status must be {n} uint8 entries on {dev}")
+    with torch.cuda.device(dev):
+        st = _lib.load().rns_tx_fill_chain_packed_dev(arena.data_ptr(), arena.numel(), head_blk_off.data_ptr(),
+                                                     head_len8.data_ptr(), pay_blk_off.data_ptr(),
+                                                     pay_len16.data_ptr(), int(pay_align_log2), n,
+                                                     status.data_ptr(), _stream_handle(dev))
+    _lib.check(st, "rns_tx_fill_chain_packed_dev")
+    return status
+
+
 def tx_fill(arena: torch.Tensor, off: torch.Tensor, length: torch.Tensor, *,
             status: torch.Tensor | None = None) -> torch.Tensor:
     """Transmit finalize of a batch of outgoing IP datagrams (rns_tx_fill_dev): the

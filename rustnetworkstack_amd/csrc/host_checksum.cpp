@@ -148,6 +148,33 @@ int rns_packed_layout(const uint16_t *len16, uint64_t n, uint32_t align_log2, ui
     return RNS_OK;
 }
 
+int rns_tx_chain_packed_layout(const uint8_t *head_len8, const uint16_t *pay_len16, uint64_t n, uint32_t pay_align_log2,
+                               uint64_t head_first_off, uint64_t pay_first_off, uint64_t *head_blk_off,
+                               uint64_t *pay_blk_off, uint64_t *head_off, uint64_t *pay_off, uint64_t *head_end,
+                               uint64_t *pay_end)
+{
+    if ((n && (!head_len8 || !pay_len16 || !head_blk_off || !pay_blk_off)) || !head_end || !pay_end ||
+        pay_align_log2 < 4 || pay_align_log2 > 12)
+        return RNS_E_INVALID;
+    const uint64_t m = (1ull << pay_align_log2) - 1;
+    uint64_t h = head_first_off, p = pay_first_off;
+    for (uint64_t i = 0; i < n; ++i) {
+        if ((i & 63) == 0) {
+            head_blk_off[i >> 6] = h;
+            pay_blk_off[i >> 6] = p;
+        }
+        if (head_off)
+            head_off[i] = h;
+        if (pay_off)
+            pay_off[i] = p;
+        h += head_len8[i];                                     // no padding between heads
+        p += (static_cast<uint64_t>(pay_len16[i]) + m) & ~m;  // the kernel's padded length (0 stays 0)
+    }
+    *head_end = h;
+    *pay_end = p;
+    return RNS_OK;
+}
+
 int rns_abi_version(void) { return RNS_ABI_VERSION; }
 
 const char *rns_strerror(int status)

@@ -69,6 +69,18 @@ int launch_txfin(const CsumArgs &a, hipStream_t st)
     return hip_status(hipGetLastError());
 }
 
+// The same finalize over the compact descriptors (rns_tx_fill_chain_packed_dev): the kernel's CPT mode.
+int launch_txfin_packed(const CsumArgs &a, hipStream_t st)
+{
+    constexpr bool NT = RNS_STREAM_NT != 0;
+    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(a.n) + 63) / 64)), block(64);
+    if (buf_records(a) < kOobOffset)
+        hipLaunchKernelGGL((csum_txrows_kernel<NT, true, RNS_TXROWS_D, false, true, true>), grid, block, 0, st, a);
+    else
+        hipLaunchKernelGGL((csum_txrows_kernel<NT, false, RNS_TXROWS_D, false, true, true>), grid, block, 0, st, a);
+    return hip_status(hipGetLastError());
+}
+
 template int launch_chain<false>(const CsumArgs &, uint32_t, bool, bool, hipStream_t);
 template int launch_chain<true>(const CsumArgs &, uint32_t, bool, bool, hipStream_t);
 template int launch_txrows<false>(const CsumArgs &, hipStream_t);

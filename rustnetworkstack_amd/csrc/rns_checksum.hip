@@ -508,6 +508,30 @@ int rns_tx_fill_chain_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t
     return launch_txfin(a, static_cast<hipStream_t>(stream));
 }
 
+int rns_tx_fill_chain_packed_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_head_blk_off,
+                                 const uint8_t *d_head_len8, const uint64_t *d_pay_blk_off, const uint16_t *d_pay_len16,
+                                 uint32_t pay_align_log2, uint32_t n, uint8_t *d_status, void *stream)
+{
+    if (n == 0)
+        return RNS_OK;
+    if (!d_arena || !d_head_blk_off || !d_head_len8 || !d_pay_blk_off || !d_pay_len16 || pay_align_log2 < 4 ||
+        pay_align_log2 > 12 || n > RNS_CHAIN_MAX_PACKETS)
+        return RNS_E_INVALID;
+    if (int st = check_device())
+        return st;
+    CsumArgs a{};
+    set_arena(a, d_arena, arena_bytes);
+    a.head_blk_off = d_head_blk_off;
+    a.head_len8 = d_head_len8;
+    a.blk_off = d_pay_blk_off;
+    a.len16 = d_pay_len16;
+    a.align_mask = (1u << pay_align_log2) - 1u;
+    a.n = n;
+    a.flags = RNS_FLAG_COMPLEMENT;
+    a.status = d_status;
+    return launch_txfin_packed(a, static_cast<hipStream_t>(stream));
+}
+
 int rns_tx_fill_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_off, const uint32_t *d_len,
                     uint32_t n, uint8_t *d_status, void *stream)
 {

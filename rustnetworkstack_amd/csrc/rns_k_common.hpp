@@ -53,6 +53,8 @@ struct CsumArgs {
     uint32_t n_frags;
     uint32_t chain_k;          // fragment chains: packets per lane (a wave owns 64*chain_k consecutive packets)
     uint32_t len_hint;         // packed form: the caller's typical packet length (kernel choice)
+    const uint8_t *head_len8;      // compact chain finalize: u8 head lengths (payloads: len16 / blk_off / align_mask)
+    const uint64_t *head_blk_off;  // compact chain finalize: offset of the head of datagram 64*b
 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));

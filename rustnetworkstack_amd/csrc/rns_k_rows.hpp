@@ -979,6 +979,18 @@ __global__ __launch_bounds__(64, D >= 16 ? 4 : RNS_ROWS_TX_OCC) void csum_rows_t
 // ip.rs:140-160 over [head[hdr..], payload...] exactly as compute_buffer_ones_comp folds it.
 // Heads of up to 80 bytes from their 16-byte boundary (an IPv6 + TCP head at any start) take
 // the rows; the status byte goes to a.status.
+//
+// CPT (rns_tx_fill_chain_packed_dev): FIN over the compact descriptors of this project's own
+// transmit layout — datagram i = [head, payload] with a u8 head length (a.head_len8) and a u16
+// payload length (a.len16; 0 = head only), heads back to back from a.head_blk_off[b], payloads
+// at multiples of align_mask + 1 from a.blk_off[b] for each 64-datagram block b: 3 B per
+// datagram + 16 B per block instead of 28 B.  Only the descriptor round differs: one round of
+// loads (no first[] round, no per-fragment loop, no run classification) and two DPP scans give
+// the head's and the payload's offsets.  The payloads ascend with bounded gaps by construction,
+// so the region test is "the payload block offset is 16-byte aligned", and a wave's heads are
+// always one run, so every fast wave without a rejected datagram takes the run write-back.  A
+// wave with a head past 80 bytes from its 16-byte boundary or an unaligned payload block takes
+// the exact loop, fed from the implied offsets.  From the head chunks on the code is FIN's.
 // ---------------------------------------------------------------------------
 #ifndef RNS_TXROWS_OCC  // waves/SIMD bound of the transmit-rows kernel
 #define RNS_TXROWS_OCC 5  // (zero scratch at 86-89 VGPRs; 6 spills 32-116 B/lane)
@@ -991,10 +1003,18 @@ constexpr uint32_t kTxHeadMax = 64;  // (head start & 15) + head length: at most
 #define RNS_TXFIN_RUNWRITE 1  // (IMIX 652.1-652.2 -> 632.5 us, c3 257.3 -> 256.0 against two 2-byte
 #endif                        //  stores per head: session r06h, txops / txops_rw)
 
-template <bool NT, bool BUF, int D, bool FILL, bool FIN = false>
+// A wave-uniform 64-bit value from lane l of a per-lane one.
+__device__ __forceinline__ uint64_t lane_u64(uint64_t v, uint32_t l)
+{
+    return (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<uint32_t>(v >> 32), l))) << 32) |
+           static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<uint32_t>(v), l));
+}
+
+template <bool NT, bool BUF, int D, bool FILL, bool FIN = false, bool CPT = false>
 __global__ __launch_bounds__(64, RNS_TXROWS_OCC) void csum_txrows_kernel(const CsumArgs a)
 {
     static_assert(!(FILL && FIN), "FIN finds its fields itself");
+    static_assert(!CPT || FIN, "the compact descriptors are a form of FIN");
     constexpr uint32_t kNH = FIN ? 5u : 4u;  // head chunks the fast path holds
     constexpr uint32_t kHeadMax = 16u * kNH;
     const uint32_t lane = threadIdx.x;
@@ -1003,8 +1023,23 @@ __global__ __launch_bounds__(64, RNS_TXROWS_OCC) void csum_txrows_kernel(const C
     const uint64_t recs = buf_records(a);
     const uint64_t p = static_cast<uint64_t>(blockIdx.x) * 64 + lane;
     const bool live = p < a.n;
-    const uint32_t f0 = live ? a.first[p] : 0u, f1 = live ? a.first[p + 1] : 0u;
-    const bool rng_ok = f0 <= f1 && f1 <= a.n_frags;
+    uint32_t f0 = 0, f1 = 0;
+    uint32_t hl8 = 0, pl16 = 0;      // CPT: the lane's two lengths
+    uint64_t hblk = 0, pblk = 0;     // CPT: the wave's two block offsets (loaded per lane, as csum_rows_kernel's)
+    if constexpr (CPT) {
+        // the whole descriptor round: one u8, one u16 and the block's two offsets
+        const uint64_t q = live ? p : a.n - 1;  // branch-free descriptor loads
+        const uint64_t blk = (p >> 6) + __builtin_amdgcn_mbcnt_lo(0u, 0u);
+        hblk = a.head_blk_off[blk];
+        pblk = a.blk_off[blk];
+        hl8 = live ? static_cast<uint32_t>(a.head_len8[q]) : 0u;
+        pl16 = live ? static_cast<uint32_t>(a.len16[q]) : 0u;
+        f1 = live ? (pl16 ? 2u : 1u) : 0u;  // the chain [head] or [head, payload]
+    } else {
+        f0 = live ? a.first[p] : 0u;
+        f1 = live ? a.first[p + 1] : 0u;
+    }
+    const bool rng_ok = CPT || (f0 <= f1 && f1 <= a.n_frags);
     const uint32_t nfr = live && rng_ok ? f1 - f0 : 0u;
     const uint32_t seed = (a.seed && live) ? static_cast<uint32_t>(a.seed[p]) : 0u;
     uint32_t fo = 0;
@@ -1018,16 +1053,30 @@ __global__ __launch_bounds__(64, RNS_TXROWS_OCC) void csum_txrows_kernel(const C
     for (uint32_t j = 0; j < kF; ++j) {
         o[j] = 0;
         l[j] = 0;
-        if (j < nfr) {
+        if (!CPT && j < nfr) {
             o[j] = a.off[f0 + j] + a.base_adjust;
             l[j] = a.len[f0 + j];
         }
     }
     bool all_in = true, run = nfr <= kF;
     uint32_t plen = 0;
+    uint64_t pbase = 0;  // CPT: the wave's payload block offset
+    if constexpr (CPT) {
+        // head i starts where head i-1 ends; payload i at the padded end of payload i-1
+        const uint32_t ppad = (pl16 + a.align_mask) & ~a.align_mask;
+        const uint32_t hin = wave_incl_scan(hl8), pin = wave_incl_scan(ppad);
+        pbase = lane_u64(pblk, 0) + a.base_adjust;
+        o[0] = lane_u64(hblk, 0) + a.base_adjust + (hin - hl8);
+        l[0] = hl8;
+        o[1] = pbase + (pin - ppad);
+        l[1] = pl16;
+        plen = pl16;
+        all_in = o[0] <= a.arena_bytes && hl8 <= a.arena_bytes - o[0] &&
+                 (pl16 == 0 || (o[1] <= a.arena_bytes && pl16 <= a.arena_bytes - o[1]));
+    }
 #pragma unroll
     for (uint32_t j = 0; j < kF; ++j) {
-        if (j < nfr) {
+        if (!CPT && j < nfr) {
             const bool in = o[j] <= a.arena_bytes && l[j] <= a.arena_bytes - o[j];
             all_in = all_in && in;
             if (j >= 1) {
@@ -1055,7 +1104,18 @@ __global__ __launch_bounds__(64, RNS_TXROWS_OCC) void csum_txrows_kernel(const C
     uint64_t r0 = 0;
     uint32_t rel = 0, c0 = 0, e = 0, total = 0;
     bool region = true;
-    if (pm) {
+    if constexpr (CPT) {
+        // the payloads ascend from the block offset with gaps below the alignment: one region
+        region = !pm || (pbase & 15u) == 0;
+        if (pm) {
+            r0 = pbase;
+            rel = static_cast<uint32_t>(po - pbase);
+            const uint32_t last = 63u - static_cast<uint32_t>(__builtin_clzll(pm));
+            total = __builtin_amdgcn_readlane(rel + ((plen + 15u) & ~15u), last);  // the last payload's end
+            c0 = has_pay ? rel >> 4 : 0u;
+            e = has_pay ? (rel + plen - 1u) >> 4 : 0u;
+        }
+    } else if (pm) {
         const uint32_t fl = static_cast<uint32_t>(__builtin_ctzll(pm));
         r0 = (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<uint32_t>(po >> 32), fl)))
               << 32) |
@@ -1092,7 +1152,7 @@ __global__ __launch_bounds__(64, RNS_TXROWS_OCC) void csum_txrows_kernel(const C
                                  __shfl(static_cast<int>(hend >> 32), static_cast<int>(lane) - 1, 64)))
                              << 32) |
                             static_cast<uint32_t>(__shfl(static_cast<int>(hend), static_cast<int>(lane) - 1, 64));
-        const bool contig = !live || (!bad && (lane == 0 || o[0] == pe));
+        const bool contig = !live || (!bad && (CPT || lane == 0 || o[0] == pe));  // (CPT: by construction)
         runw = fast && !__ballot(!contig);
         const uint32_t last = 63u - static_cast<uint32_t>(__builtin_clzll(__ballot(live)));
         b0 = ((static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(o[0] >> 32))))
@@ -1171,7 +1231,9 @@ __global__ __launch_bounds__(64, RNS_TXROWS_OCC) void csum_txrows_kernel(const C
             // the chain's length, and every fragment (not just the first kF) inside the arena
             uint32_t lt = 0;
             bool in = true;
-            if (live && rng_ok) {
+            if constexpr (CPT) {
+                lt = hl + plen;  // (both fragments were checked above)
+            } else if (live && rng_ok) {
                 for (uint32_t f = f0; f < f1; ++f) {
                     const uint64_t so = a.off[f] + a.base_adjust;
                     const uint32_t lf = a.len[f];
@@ -1202,9 +1264,19 @@ __global__ __launch_bounds__(64, RNS_TXROWS_OCC) void csum_txrows_kernel(const C
             const uint32_t FO = FIN ? __builtin_amdgcn_readlane(l4f, ow) - HD : __builtin_amdgcn_readlane(fo, ow);
             uint32_t acc = __builtin_amdgcn_readlane(sd, ow);
             bool pbad = false;
+            // CPT: the owner's implied fragments (F0 = 0: fragment 0 the head, 1 the payload)
+            const uint64_t HO = CPT ? lane_u64(o[0], ow) : 0, PO = CPT ? lane_u64(o[1], ow) : 0;
+            const uint32_t HL = CPT ? __builtin_amdgcn_readlane(hl, ow) : 0u, PL = CPT ? __builtin_amdgcn_readlane(plen, ow) : 0u;
             for (uint32_t f = F0; f < F1; ++f) {
-                uint64_t st = a.off[f] + a.base_adjust;
-                uint32_t L = a.len[f];
+                uint64_t st;
+                uint32_t L;
+                if constexpr (CPT) {
+                    st = f == 0 ? HO : PO;
+                    L = f == 0 ? HL : PL;
+                } else {
+                    st = a.off[f] + a.base_adjust;
+                    L = a.len[f];
+                }
                 if (!(st <= a.arena_bytes && L <= a.arena_bytes - st)) {
                     pbad = true;
                     break;

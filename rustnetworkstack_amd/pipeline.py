@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from .batch import (PinnedBuffer, recv_batch, recv_batch_packed, rx_verify, rx_verify_packed, send_batch,
-                    send_batch_chain, tx_fill, tx_fill_chain)
+                    send_batch_chain, tx_fill, tx_fill_chain, tx_fill_chain_packed)
 
 MRU = 2048  # netif.rs:66
 
@@ -313,7 +313,12 @@ class _ChainSet:
     """One buffer set of TxChainPipeline: a pinned arena [header region | payload region], its
     chain descriptors and statuses, and their HBM twins (the same offsets on both sides)."""
 
-    def __init__(self, dev: torch.device, max_pkts: int, head_region: int, payload_bytes: int):
+    def __init__(self, dev: torch.device, max_pkts: int, head_region: int, payload_bytes: int,
+                 compact: bool = False):
+        # the compact descriptors of a batch in one buffer: [head_blk_off | pay_blk_off | pay_len16 | head_len8]
+        cbytes = compact_desc_bytes(max_pkts)
+        self.h_cdesc = PinnedBuffer(cbytes) if compact else None
+        self.d_cdesc = torch.empty(cbytes, dtype=torch.uint8, device=dev) if compact else None
         self.host = PinnedBuffer(head_region + payload_bytes)
         self.h_off = PinnedBuffer(8 * 2 * max_pkts)
         self.h_len = PinnedBuffer(4 * 2 * max_pkts)
@@ -324,11 +329,46 @@ class _ChainSet:
         self.d_len = torch.empty(2 * max_pkts, dtype=torch.int32, device=dev)
         self.d_first = torch.empty(max_pkts + 1, dtype=torch.int32, device=dev)
         self.d_status = torch.empty(max_pkts, dtype=torch.uint8, device=dev)
+        self.cform = False  # the batch described last takes the compact route
         self.done = torch.cuda.Event()
 
     def close(self):
-        for b in (self.host, self.h_off, self.h_len, self.h_first, self.h_status):
-            b.free()
+        for b in (self.host, self.h_off, self.h_len, self.h_first, self.h_status, self.h_cdesc):
+            if b is not None:
+                b.free()
+
+
+def compact_desc_bytes(n: int) -> int:
+    """Bytes of a batch's compact chain descriptors: 3 B per datagram + 16 B per 64 datagrams."""
+    return 3 * n + 16 * ((n + 63) // 64)
+
+
+def chain_compact_form(head_len, pay_off, pay_len, pay_base: int = 0):
+    """The compact descriptors (rns_tx_fill_chain_packed_dev, 16-byte payload alignment) of a
+    batch of [head, payload] datagrams whose heads lie back to back from arena offset 0 and whose
+    payloads lie at ``pay_base + pay_off``, or None when the payload offsets are not exactly the
+    packed layout: ascending, each at the 16-byte-aligned end of the previous payload, from a
+    16-byte-aligned first offset (the offset of a zero-length payload means nothing and is not
+    looked at).  Returns (head_blk_off, head_len8, pay_blk_off, pay_len16) as numpy arrays."""
+    hl = np.ascontiguousarray(head_len, dtype=np.int64)
+    po = np.ascontiguousarray(pay_off, dtype=np.int64)
+    pl = np.ascontiguousarray(pay_len, dtype=np.int64)
+    n = hl.shape[0]
+    if n == 0 or hl.min() < 0 or hl.max() > 0xFF or pl.min() < 0 or pl.max() > 0xFFFF:
+        return None
+    pad = (pl + 15) & ~15
+    rel = np.cumsum(pad) - pad  # every payload's offset from the first one
+    has = pl > 0
+    first = 0
+    if has.any():
+        first = int(po[has][0])
+        if first < 0 or (first + pay_base) & 15 or not np.array_equal(po[has], first + rel[has]):
+            return None
+    # the block offsets rns_tx_chain_packed_layout gives for these lengths (heads from 0, payloads from
+    # pay_base + first), taken from the sums already at hand
+    hblk = (np.cumsum(hl) - hl)[::64].astype(np.uint64)
+    pblk = (rel[::64] + (pay_base + first)).astype(np.uint64)
+    return hblk, hl.astype(np.uint8), pblk, pl.astype(np.uint16)
 
 
 class TxChainPipeline:
@@ -346,12 +386,21 @@ class TxChainPipeline:
     HEAD_MAX = 128  # bytes per head fragment, at most (IPv4 with options + TCP with options)
     DEPTH = 2
 
-    def __init__(self, device: int = 0, max_pkts: int = 65536, payload_bytes: int | None = None):
+    def __init__(self, device: int = 0, max_pkts: int = 65536, payload_bytes: int | None = None,
+                 compact: bool = False):
         self.max_pkts = max_pkts
+        # compact=True: a batch whose payloads are exactly packed (chain_compact_form) sends only the
+        # compact descriptors to the device (3 B per datagram + 16 B per 64, not 28 B) and is finalized
+        # by rns_tx_fill_chain_packed_dev; any other batch takes the CSR route.  last_form / last_desc_bytes:
+        # the route of the last batch queued ("compact" or "csr") and the descriptor bytes it copied H2D.
+        self.compact = compact
+        self.last_form: str | None = None
+        self.last_desc_bytes = 0
         self.dev = torch.device(f"cuda:{device}")
         self.head_region = (self.HEAD_MAX * max_pkts + 4095) & ~4095
         self.payload_bytes = payload_bytes if payload_bytes is not None else MRU * max_pkts
-        self._sets = [_ChainSet(self.dev, max_pkts, self.head_region, self.payload_bytes) for _ in range(self.DEPTH)]
+        self._sets = [_ChainSet(self.dev, max_pkts, self.head_region, self.payload_bytes, compact)
+                      for _ in range(self.DEPTH)]
         self._next = 0
         self._inflight: deque = deque()
         self._stream = None
@@ -403,6 +452,18 @@ class TxChainPipeline:
         ln[f0[has] + 1] = pl[has].astype(np.uint32)
         hused = int(hoff[-1] + hl[-1]) if n else 0
         pused = int((po + pl).max()) if n else 0
+        # the compact route (its descriptors into the set's pinned buffer), when the batch has that form
+        s.cform = False
+        if self.compact and n:
+            c = chain_compact_form(hl, po, pl, self.head_region)
+            if c is not None:
+                nb = (n + 63) // 64
+                h = s.h_cdesc.array
+                h[:8 * nb].view(np.uint64)[:] = c[0]
+                h[8 * nb:16 * nb].view(np.uint64)[:] = c[2]
+                h[16 * nb:16 * nb + 2 * n].view(np.uint16)[:] = c[3]
+                h[16 * nb + 2 * n:16 * nb + 3 * n] = c[1]
+                s.cform = True
         return n, nf, hused, pused
 
     def _queue(self, s: _ChainSet, n: int, nf: int, hused: int, pused: int) -> None:
@@ -410,10 +471,20 @@ class TxChainPipeline:
         s.d_arena[:hused].copy_(torch.from_numpy(s.host.array[:hused]), non_blocking=True)
         if pused:
             s.d_arena[hr:hr + pused].copy_(torch.from_numpy(s.host.array[hr:hr + pused]), non_blocking=True)
-        s.d_off[:nf].copy_(torch.from_numpy(s.h_off.array.view(np.int64)[:nf]), non_blocking=True)
-        s.d_len[:nf].copy_(torch.from_numpy(s.h_len.array.view(np.int32)[:nf]), non_blocking=True)
-        s.d_first[:n + 1].copy_(torch.from_numpy(s.h_first.array.view(np.int32)[:n + 1]), non_blocking=True)
-        tx_fill_chain(s.d_arena, s.d_off[:nf], s.d_len[:nf], s.d_first[:n + 1], status=s.d_status[:n])
+        if s.cform:
+            nb, cb = (n + 63) // 64, compact_desc_bytes(n)
+            d = s.d_cdesc
+            d[:cb].copy_(torch.from_numpy(s.h_cdesc.array[:cb]), non_blocking=True)
+            tx_fill_chain_packed(s.d_arena, d[:8 * nb].view(torch.int64), d[16 * nb + 2 * n:cb],
+                                 d[8 * nb:16 * nb].view(torch.int64), d[16 * nb:16 * nb + 2 * n].view(torch.uint16),
+                                 pay_align_log2=4, status=s.d_status[:n])
+            self.last_form, self.last_desc_bytes = "compact", cb
+        else:
+            s.d_off[:nf].copy_(torch.from_numpy(s.h_off.array.view(np.int64)[:nf]), non_blocking=True)
+            s.d_len[:nf].copy_(torch.from_numpy(s.h_len.array.view(np.int32)[:nf]), non_blocking=True)
+            s.d_first[:n + 1].copy_(torch.from_numpy(s.h_first.array.view(np.int32)[:n + 1]), non_blocking=True)
+            tx_fill_chain(s.d_arena, s.d_off[:nf], s.d_len[:nf], s.d_first[:n + 1], status=s.d_status[:n])
+            self.last_form, self.last_desc_bytes = "csr", 12 * nf + 4 * (n + 1)
         torch.from_numpy(s.host.array[:hused]).copy_(s.d_arena[:hused], non_blocking=True)
         torch.from_numpy(s.h_status.array[:n]).copy_(s.d_status[:n], non_blocking=True)
         s.done.record()

@@ -363,6 +363,29 @@ def tx_chain_layout(name: str, n: int | None = None, head: int = 20, frag: int =
                          arena_bytes=arena_bytes, data_seed=lay.data_seed, payload_bytes=lay.payload_bytes)
 
 
+def tx_chain_compact(lay: TxChainLayout):
+    """The compact descriptors (rns_tx_fill_chain_packed_dev, 16-byte payload alignment) of a
+    tx_chain_layout with frag = 0: (head_blk_off uint64, head_len8 uint8, pay_blk_off uint64,
+    pay_len16 uint16), checked against the layout's own fragment offsets."""
+    from .batch import tx_chain_packed_layout
+    n = lay.n
+    first = lay.first.astype(np.int64)
+    nfr = first[1:] - first[:-1]
+    if n == 0 or int(nfr.max()) > 2:
+        raise ValueError("the compact chain form describes [head] / [head, payload] datagrams (frag = 0)")
+    hl = lay.frag_len[first[:-1]].astype(np.int64)
+    pl = np.zeros(n, dtype=np.int64)
+    has = nfr == 2
+    pl[has] = lay.frag_len[first[:-1][has] + 1]
+    hoff0 = int(lay.frag_off[0])
+    poff0 = int(lay.frag_off[first[:-1][has][0] + 1]) if has.any() else 0
+    hblk, pblk, hoff, poff, _, _ = tx_chain_packed_layout(hl, pl, 4, hoff0, poff0)
+    if not (np.array_equal(hoff, lay.frag_off[first[:-1]]) and
+            np.array_equal(poff[has], lay.frag_off[first[:-1][has] + 1])):
+        raise ValueError("the layout's fragments are not the compact form's implied offsets")
+    return hblk, hl.astype(np.uint8), pblk, pl.astype(np.uint16)
+
+
 class TxChainBatch:
     """A transmit batch as NetBuffer chains in HBM (bench.py --op finalize): the chains of
     tx_chain_layout(config, head=40) — 40-byte head fragments (an IPv4 header from LOCAL4 to
@@ -400,6 +423,13 @@ class TxChainBatch:
         self.d_len = torch.from_numpy(lay.frag_len.view(np.int32)).to(device)
         self.d_first = torch.from_numpy(lay.first.view(np.int32)).to(device)
         self.status = torch.empty(n, dtype=torch.uint8, device=device)
+        if frag == 0 and n:
+            # the same arena's compact descriptors (rns_tx_fill_chain_packed_dev): 3 B per datagram + 16 B per 64
+            hblk, hl8, pblk, pl16 = tx_chain_compact(lay)
+            self.d_head_blk_off = torch.from_numpy(hblk.view(np.int64)).to(device)
+            self.d_head_len8 = torch.from_numpy(hl8).to(device)
+            self.d_pay_blk_off = torch.from_numpy(pblk.view(np.int64)).to(device)
+            self.d_pay_len16 = torch.from_numpy(pl16.view(np.int16)).to(device)
 
     @property
     def n_frags(self) -> int:

@@ -19,6 +19,9 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
 * tx_chain — rns_tx_fill_chain_dev: whole-datagram finalize of the same transmit shape with
              40-byte IPv4 + TCP head fragments (the layout alloc_header builds, buf.rs:262-291),
              payload as one fragment or 512-byte NetBuffer fragments (round 6)
+* tx_chain_packed — rns_tx_fill_chain_packed_dev: the same finalize of the same arena (one payload
+             fragment) over the compact descriptors, 3 B per datagram + 16 B per 64 instead of 28 B;
+             timed in rounds alternating with tx_chain's, and both rows carry every round's time
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -68,19 +71,27 @@ def write_ipv4_tcp_headers(b, lay, dev):
     torch.cuda.synchronize()
 
 
-def timed(fn, steps, rounds):
+def timed_rounds(fns, steps, rounds):
+    """Every round's ms per launch (sorted) of each function; the rounds of several functions
+    alternate, so they see the same machine."""
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    fn()
-    fn()
-    res = []
+    for fn in fns:
+        fn()
+        fn()
+    res = [[] for _ in fns]
     for _ in range(rounds):
-        e0.record()
-        for _ in range(steps):
-            fn()
-        e1.record()
-        torch.cuda.synchronize()
-        res.append(e0.elapsed_time(e1) / steps)
-    res.sort()
+        for k, fn in enumerate(fns):
+            e0.record()
+            for _ in range(steps):
+                fn()
+            e1.record()
+            torch.cuda.synchronize()
+            res[k].append(e0.elapsed_time(e1) / steps)
+    return [sorted(r) for r in res]
+
+
+def timed(fn, steps, rounds):
+    res = timed_rounds([fn], steps, rounds)[0]
     return res[len(res) // 2]
 
 
@@ -121,9 +132,10 @@ def main():
         if "chain_fill" in ops:
             for frag in (int(x) for x in args.tx_frags.split(",")):
                 r.update(bench_chain_fill(cfg, dev, args, frag))
-        if "tx_chain" in ops:
+        if "tx_chain" in ops or "tx_chain_packed" in ops:
             for frag in (int(x) for x in args.tx_frags.split(",")):
-                r.update(bench_tx_chain(cfg, dev, args, frag))
+                if "tx_chain" in ops or frag == 0:
+                    r.update(bench_tx_chain(cfg, dev, args, frag, packed="tx_chain_packed" in ops and frag == 0))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -245,11 +257,13 @@ def bench_chain_fill(cfg, dev, args, frag):
     return res
 
 
-def bench_tx_chain(cfg, dev, args, frag):
+def bench_tx_chain(cfg, dev, args, frag, packed=False):
     """Whole-datagram transmit finalize over NetBuffer chains: 40-byte IPv4 + TCP heads back to
-    back in a header region, payloads packed at 16-byte starts (one fragment, or 512-byte ones)."""
-    from rustnetworkstack_amd.batch import fill_splitmix64, tx_fill_chain
-    from rustnetworkstack_amd.workloads import tx_chain_layout
+    back in a header region, payloads packed at 16-byte starts (one fragment, or 512-byte ones).
+    packed: also the compact-descriptor entry over the same arena, its rounds alternating with the
+    CSR entry's (the finalize is idempotent: both store the same bytes every launch)."""
+    from rustnetworkstack_amd.batch import fill_splitmix64, tx_fill_chain, tx_fill_chain_packed
+    from rustnetworkstack_amd.workloads import tx_chain_compact, tx_chain_layout
     t = tx_chain_layout(cfg, head=40, frag=frag)
     n, pay, nf = t.n, t.payload_bytes, int(t.frag_off.shape[0])
     arena = torch.empty(t.arena_bytes + 64, dtype=torch.uint8, device=dev)
@@ -265,13 +279,42 @@ def bench_tx_chain(cfg, dev, args, frag):
     d_fl = torch.from_numpy(t.frag_len.view(np.int32)).to(dev)
     d_first = torch.from_numpy(t.first.view(np.int32)).to(dev)
     st = torch.empty(n, dtype=torch.uint8, device=dev)
-    ms = timed(lambda: tx_fill_chain(arena, d_fo, d_fl, d_first, status=st), args.steps, args.rounds)
-    filled = int((st == 3).sum().item())
     tag = "tx_chain" if frag == 0 else f"tx_chain{frag}"
+
+    def row(rs, desc_bytes):
+        ms = rs[len(rs) // 2]
+        return {"us": round(ms * 1e3, 1), "GBps": round((pay + n) / ms / 1e6, 1), "filled": int((st == 3).sum().item()),
+                "packets": n, "fragments": nf, "rounds_us": [round(x * 1e3, 1) for x in rs],
+                "spread_us": round((rs[-1] - rs[0]) * 1e3, 1), "descriptor_bytes": desc_bytes}
+
+    csr = lambda: tx_fill_chain(arena, d_fo, d_fl, d_first, status=st)  # noqa: E731
+    res = {}
+    if packed:
+        hblk, hl8, pblk, pl16 = tx_chain_compact(t)
+        d_hblk, d_hl8 = torch.from_numpy(hblk.view(np.int64)).to(dev), torch.from_numpy(hl8).to(dev)
+        d_pblk, d_pl16 = torch.from_numpy(pblk.view(np.int64)).to(dev), torch.from_numpy(pl16.view(np.int16)).to(dev)
+        st2 = torch.empty_like(st)
+        cpt = lambda: tx_fill_chain_packed(arena, d_hblk, d_hl8, d_pblk, d_pl16, status=st2)  # noqa: E731
+        # both entries from the same unfinalized header region: the bytes stored must be identical
+        hreg = int(pblk[0])  # the header region ends below the first payload
+        before = arena[:hreg].clone()
+        csr()
+        heads_csr = arena[:hreg].clone()
+        arena[:hreg].copy_(before)
+        cpt()
+        same = bool(torch.equal(arena[:hreg], heads_csr)) and bool(torch.equal(st, st2))
+        del before, heads_csr
+        rs_csr, rs_cpt = timed_rounds([csr, cpt], args.steps, args.rounds)
+        res[tag] = row(rs_csr, 12 * nf + 4 * (n + 1))
+        res["tx_chain_packed"] = row(rs_cpt, 3 * n + 16 * ((n + 63) // 64))
+        res["tx_chain_packed"]["bytes_and_status_equal_csr"] = same
+        med_csr, med_cpt = rs_csr[len(rs_csr) // 2], rs_cpt[len(rs_cpt) // 2]
+        res["tx_chain_packed"]["within_csr_median_plus_spread"] = bool(med_cpt <= med_csr + (rs_csr[-1] - rs_csr[0]))
+    else:
+        res[tag] = row(timed_rounds([csr], args.steps, args.rounds)[0], 12 * nf + 4 * (n + 1))
     del arena
     torch.cuda.empty_cache()
-    return {tag: {"us": round(ms * 1e3, 1), "GBps": round((pay + n) / ms / 1e6, 1), "filled": filled,
-                  "packets": n, "fragments": nf}}
+    return res
 
 
 def bench_chain_netbuf(lay, dev, args, shuffled=False, runs=False):

@@ -48,6 +48,8 @@ def main():
     ap.add_argument("--tx", action="store_true")
     ap.add_argument("--overlap", action="store_true")
     ap.add_argument("--chain", action="store_true", help="with --tx: TxChainPipeline (head + payload fragments)")
+    ap.add_argument("--compact", action="store_true",
+                    help="with --tx --chain: TxChainPipeline(compact=True), the compact descriptors on the device path")
     ap.add_argument("--slots", action="store_true", help="receive into 2048-B slots (round-5 form)")
     ap.add_argument("--config", default="c3_1500B", help="datagram sizes: c3_1500B or c2_64B")
     args = ap.parse_args()
@@ -115,7 +117,8 @@ def main_tx(args):
     a, r = socket.socketpair(socket.AF_UNIX, socket.SOCK_SEQPACKET)
     for s_, opt in ((a, socket.SO_SNDBUF), (r, socket.SO_RCVBUF)):
         s_.setsockopt(socket.SOL_SOCKET, opt, 64 << 20)
-    pipe = TxChainPipeline(device=0, max_pkts=args.batch) if args.chain else TxPipeline(device=0, max_pkts=args.batch)
+    pipe = TxChainPipeline(device=0, max_pkts=args.batch, compact=args.compact) if args.chain else \
+        TxPipeline(device=0, max_pkts=args.batch)
     got = [0]
     sample = {}
 
@@ -155,9 +158,11 @@ def main_tx(args):
     exact = all(np.array_equal(v, dgrams[i]) for i, v in sample.items())
     res = {"direction": "transmit", "chain": args.chain, "overlap": args.overlap, "packets": n, "received": got[0], "filled": filled,
            "sample_exact": exact, "sampled": len(sample), "seconds": round(dt, 3),
+           **({"compact": args.compact, "last_form": pipe.last_form,
+               "descriptor_bytes_h2d_last_batch": pipe.last_desc_bytes} if args.chain else {}),
            "packets_per_s": round(got[0] / dt), "GBps": round(got[0] * 1500 / dt / 1e9, 3),
            "path": ("host chains [40 B head, 1460 B payload] -> pinned header / payload regions -> H2D of the used "
-                    "bytes -> rns_tx_fill_chain_dev -> header region D2H -> rns_io_send_batch_chain (sendmmsg, "
+                    "bytes -> rns_tx_fill_chain_dev (--compact: rns_tx_fill_chain_packed_dev) -> header region D2H -> rns_io_send_batch_chain (sendmmsg, "
                     "two iovecs per datagram)" if args.chain else
                     "host datagrams -> pinned 2048-B slots -> H2D -> rns_tx_fill_dev -> 128 B/slot D2H -> "
                     "rns_io_send_batch") + " -> AF_UNIX SOCK_SEQPACKET socketpair; drain on another host thread"}
