@@ -13,7 +13,9 @@ CABI_TEST := tests/c/test_batch_abi
 
 CABI_TXCP_TEST := tests/c/test_tx_chain_packed_abi
 
-all: $(LIB) oracle $(CABI_TEST) $(CABI_TXCP_TEST)
+CABI_RXC_TEST := tests/c/test_rx_chain_abi
+
+all: $(LIB) oracle $(CABI_TEST) $(CABI_TXCP_TEST) $(CABI_RXC_TEST)
 
 # A plain C caller of the C ABI (no torch): built here, run by tests/test_c_caller.py on a GPU.
 $(CABI_TEST): tests/c/test_batch_abi.c oracle/csum_oracle.c include/rns_checksum.h $(LIB)
@@ -25,6 +27,12 @@ $(CABI_TEST): tests/c/test_batch_abi.c oracle/csum_oracle.c include/rns_checksum
 $(CABI_TXCP_TEST): tests/c/test_tx_chain_packed_abi.c oracle/csum_oracle.c include/rns_checksum.h $(LIB)
 	gcc -std=gnu11 -O1 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include \
 	    tests/c/test_tx_chain_packed_abi.c oracle/csum_oracle.c -L$(PKG) -lrns_checksum -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
+	    -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread -o $@
+
+# The same for the receive verify over fragment chains: run by tests/test_c_caller_rx_chain.py.
+$(CABI_RXC_TEST): tests/c/test_rx_chain_abi.c oracle/csum_oracle.c include/rns_checksum.h $(LIB)
+	gcc -std=gnu11 -O1 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include \
+	    tests/c/test_rx_chain_abi.c oracle/csum_oracle.c -L$(PKG) -lrns_checksum -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
 	    -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread -o $@
 
 # One translation unit per kernel family (rns_launch.hpp), compiled in parallel (make -j).
@@ -78,7 +86,7 @@ asm: $(HIP_SRCS)
 	    --cuda-device-only -S ../../../$$f -o $$(basename $$f .hip).s) || exit 1; done
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(CABI_TEST) $(CABI_TXCP_TEST)
+	rm -rf $(BUILD) $(LIB) $(CABI_TEST) $(CABI_TXCP_TEST) $(CABI_RXC_TEST)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle resources asm clean ab

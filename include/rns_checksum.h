@@ -280,6 +280,42 @@ int rns_rx_verify_strided_dev(const uint8_t *d_arena, uint64_t arena_bytes, uint
                               const uint16_t *d_len16, uint32_t n, const uint8_t *local_ipv4, const uint8_t *local_ipv6,
                               uint8_t *d_status, uint16_t *d_l4_sum, void *stream);
 
+/* Receive verify of NetBuffer FRAGMENT CHAINS, as the reference holds a received datagram
+ * (recv_packet, netif.rs:65-83: new_prealloc(2048) = four 512-byte pool fragments, trim_tail):
+ * datagram i = fragments [d_first[i], d_first[i+1]) of (d_frag_off, d_frag_len), the CSR form
+ * of rns_csum_chain_dev, anywhere in the arena at any byte alignment.  Nothing is written to
+ * the arena.  The RNS_RX_* bits mean what they mean for rns_rx_verify_dev, decided as the
+ * reference decides them on a NetBuffer; with len0 = the first fragment's length and T = the
+ * sum of all fragment lengths:
+ *   - header() is the FIRST fragment only (ip.rs:39, 69, 115): the version is header[0] >> 4;
+ *     IPv4: hdr = IHL*4, RNS_RX_MALFORMED when hdr == 0, len0 < 16 or hdr > len0, the header
+ *     checksum over header[..hdr] and the fields [6..8], [9], [12..16] from that fragment;
+ *     IPv6: hdr = 40, RNS_RX_MALFORMED when len0 < 24 (header[8..24]) or T < 40 (trim_head asserts);
+ *   - the L4 segment is the chain after trim_head(hdr) (buf.rs:294-329): whole fragments go while
+ *     their length does not exceed what remains to trim, then the next fragment's start advances
+ *     (a head fragment of exactly hdr bytes disappears; an IPv6 header may run over several short
+ *     fragments); its length is T - hdr, which the TCP / ICMPv6 pseudo-header carries;
+ *   - the L4 value is compute_buffer_ones_comp(seed, segment) ^ 0xffff (util.rs:112-119): folded
+ *     after every fragment, each fragment paired from its own start, an odd-length fragment
+ *     zero-padded as util.rs:97-99 pads it, a fragment past 128 KiB wrapping the u32 accumulator
+ *     as util.rs:89-99 does; an empty segment yields the seed;
+ *   - RNS_RX_MALFORMED (d_l4_sum 0) also for a malformed range (first[i] > first[i+1] or
+ *     first[i+1] > n_frags), a datagram without fragments (header() asserts), any fragment
+ *     outside the arena, and len0 == 0 (header[0] panics).
+ * An EMPTY fragment after the first adds nothing; the reference would panic on it (util.rs:92),
+ * so parity is unpinned there, as for the other len == 0 cases of this header.  A one-fragment
+ * chain gives exactly what rns_rx_verify_dev gives for (off, len).
+ * One pass: the fragments stream through the chain kernel's class pass, the owner lane parses
+ * its head fragment's first bytes and takes the header's words out of that fragment's sum.  An
+ * IPv6 header that runs past its first fragment, or a fragment past 128 KiB, sends its datagram
+ * through an exact per-datagram loop (same results, slower).  n_pkts == 0 is RNS_OK; a NULL
+ * d_arena / d_first / d_status / local address, NULL fragment arrays with n_frags > 0, or
+ * n_pkts > RNS_CHAIN_MAX_PACKETS is RNS_E_INVALID, all before the device is touched. */
+int rns_rx_verify_chain_dev(const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_frag_off,
+                            const uint32_t *d_frag_len, uint32_t n_frags, const uint32_t *d_first, uint32_t n_pkts,
+                            const uint8_t *local_ipv4, const uint8_t *local_ipv6, uint8_t *d_status,
+                            uint16_t *d_l4_sum /* optional */, void *stream);
+
 /* Transmit finalize (SURVEY a6, §8f row 2 for whole datagrams): for each finished
  * outgoing IP datagram d_arena[d_off[i] .. + d_len[i]), the checksums the stack's
  * transmit path stores — tcp_output (tcp.rs:957-973: pseudo-header from the header's
@@ -468,6 +504,26 @@ int rns_io_send_batch_chain(int fd, const uint8_t *h_arena, const uint64_t *h_fr
  * datagram.  Returns the number of datagrams (0 on timeout) or RNS_E_IO. */
 int rns_io_recv_batch_packed(int fd, uint8_t *h_arena, uint64_t arena_bytes, uint32_t mru, uint32_t max_pkts,
                              uint16_t *h_len16, uint64_t *h_blk_off, uint64_t *h_end, int timeout_ms);
+
+/* Batched recv_packet into NetBuffer chains (netif.rs:65-83: new_prealloc(MRU), readv over the
+ * fragments, trim_tail), the receive twin of rns_io_send_batch_chain: h_pool is a pool of
+ * buf_bytes-byte buffers (512 = the reference's FRAGMENT_SIZE), h_free[0..n_free) the indices of
+ * the free ones.  After waiting up to timeout_ms for the first datagram, every queued datagram is
+ * read into the next ceil(mru / buf_bytes) free buffers (at most RNS_IO_MAX_FRAGS, else
+ * RNS_E_INVALID) — recvmmsg with one iovec list per message on a socket fd, up to 64 datagrams
+ * per call; one readv per datagram on a TUN fd — and keeps the ceil(len / buf_bytes) buffers it
+ * filled, the last fragment's length the remainder.  The call goes on while that many free
+ * buffers remain and fewer than max_pkts datagrams were read.  On return h_free is permuted: its
+ * first *n_frags_out entries are the buffers now in use, in fragment order (h_frag_off[j] =
+ * h_free[j] * buf_bytes, h_frag_len[j]), the rest are still free; h_first (max_pkts + 1 entries)
+ * is the CSR index of the datagrams: what rns_rx_verify_chain_dev takes once the pool is on the
+ * device.  A datagram longer than mru is dropped and takes no buffer (MSG_TRUNC on sockets; a
+ * TUN read is offered mru + 1 bytes); a zero-length datagram is skipped and those after it are
+ * kept (a recvmmsg round of nothing but empty reads ends the call: a closed stream peer reads
+ * that way for ever).  Returns the number of datagrams (0 on timeout) or RNS_E_IO. */
+int rns_io_recv_batch_chain(int fd, uint8_t *h_pool, uint32_t buf_bytes, uint32_t *h_free, uint32_t n_free,
+                            uint32_t mru, uint32_t max_pkts, uint64_t *h_frag_off, uint32_t *h_frag_len,
+                            uint32_t *h_first /* max_pkts + 1 */, uint32_t *n_frags_out, int timeout_ms);
 
 /* Pinned host memory for arenas handed to rns_csum_batch_host. */
 int rns_host_alloc(uint64_t bytes, void **out);

@@ -503,6 +503,39 @@ def rx_verify(arena: torch.Tensor, off: torch.Tensor, length: torch.Tensor, loca
     return status
 
 
+def rx_verify_chain(arena: torch.Tensor, frag_off: torch.Tensor, frag_len: torch.Tensor, first: torch.Tensor,
+                    local_ipv4: bytes, local_ipv6: bytes, *, status: torch.Tensor | None = None,
+                    l4_sum: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor | None]:
+    """Receive verify of NetBuffer fragment chains (rns_rx_verify_chain_dev): datagram i =
+    fragments ``first[i] .. first[i+1]`` (``first``: int32 [n+1]) of ``(frag_off, frag_len)``,
+    the chains of csum_chain, decided as the reference decides on a NetBuffer (header() = the
+    first fragment, trim_head, the L4 sum folded fragment by fragment).  Nothing is written to
+    the arena.  Returns ``(status, l4_sum)``: uint8 RNS_RX_* bits per datagram, and the
+    ``l4_sum`` tensor passed in (complemented L4 sums) or None."""
+    _require_cuda(arena, "arena", (torch.uint8,))
+    _require_cuda(frag_off, "frag_off", (torch.int64,))
+    _require_cuda(frag_len, "frag_len", (torch.int32,))
+    _require_cuda(first, "first", (torch.int32,))
+    if len(local_ipv4) != 4 or len(local_ipv6) != 16:
+        raise ValueError("local_ipv4 must be 4 bytes and local_ipv6 16 bytes")
+    nf = frag_off.numel()
+    n = first.numel() - 1
+    if frag_len.numel() != nf or n < 0:
+        raise ValueError("frag_off/frag_len sizes differ or first is empty")
+    if n > _lib.RNS_CHAIN_MAX_PACKETS or nf >= 2 ** 32:
+        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} packets and 2^32-1 fragments per chain call")
+    dev = arena.device
+    lib = _lib.load()
+    status, l4_ptr = _rx_outputs(dev, n, status, l4_sum,
+                                 (("frag_off", frag_off), ("frag_len", frag_len), ("first", first)))
+    with torch.cuda.device(dev):
+        st = lib.rns_rx_verify_chain_dev(arena.data_ptr(), arena.numel(), frag_off.data_ptr(), frag_len.data_ptr(),
+                                         nf, first.data_ptr(), n, bytes(local_ipv4), bytes(local_ipv6),
+                                         status.data_ptr(), l4_ptr, _stream_handle(dev))
+    _lib.check(st, "rns_rx_verify_chain_dev")
+    return status, l4_sum
+
+
 def rx_verify_packed(arena: torch.Tensor, blk_off: torch.Tensor, len16: torch.Tensor, local_ipv4: bytes,
                      local_ipv6: bytes, *, align_log2: int = 4, status: torch.Tensor | None = None,
                      l4_sum: torch.Tensor | None = None) -> torch.Tensor:
@@ -775,6 +808,45 @@ def recv_batch_packed(fd: int, arena: np.ndarray, mru: int = 2048, max_pkts: int
     if r < 0:
         raise _lib.ChecksumError(r, "rns_io_recv_batch_packed")
     return ln[:r], blk[:(r + 63) // 64], int(end.value)
+
+
+def recv_batch_chain(fd: int, pool: np.ndarray, free: np.ndarray, buf_bytes: int = 512, mru: int = 2048,
+                     max_pkts: int | None = None, timeout_ms: int = 0):
+    """Read every queued datagram (after waiting up to ``timeout_ms`` for the first) into
+    NetBuffer chains (rns_io_recv_batch_chain; batched recv_packet, netif.rs:65-83): ``pool`` is
+    a uint8 pool of ``buf_bytes``-byte buffers, ``free`` (uint32, contiguous, permuted IN PLACE)
+    the indices of the free ones.  Each datagram is offered ``ceil(mru / buf_bytes)`` buffers and
+    keeps those it filled.  Returns ``(n, frag_off uint64, frag_len uint32, first uint32 [n+1],
+    n_frags)``: on return ``free[:n_frags]`` are the buffers in use, in fragment order, and
+    ``free[n_frags:]`` are still free."""
+    if pool.dtype != np.uint8 or not pool.flags["C_CONTIGUOUS"]:
+        raise ValueError("pool must be a contiguous uint8 array")
+    if free.dtype != np.uint32 or not free.flags["C_CONTIGUOUS"] or not free.flags["WRITEABLE"]:
+        raise ValueError("free must be a contiguous writable uint32 array (it is permuted in place)")
+    buf_bytes, mru = int(buf_bytes), int(mru)
+    if buf_bytes <= 0 or mru <= 0 or mru >= 2 ** 32:
+        raise ValueError("buf_bytes and mru must be positive")
+    need = -(-mru // buf_bytes)
+    if need > _lib.RNS_IO_MAX_FRAGS:
+        raise ValueError(f"a datagram of mru bytes may take at most {_lib.RNS_IO_MAX_FRAGS} buffers")
+    n_free = free.shape[0]
+    if n_free and int(free.max()) >= pool.shape[0] // buf_bytes:
+        raise ValueError("free names a buffer outside the pool")
+    cap = max(n_free - need + 1, 0)  # a datagram keeps at least one buffer and is offered `need`
+    max_pkts = cap if max_pkts is None else min(int(max_pkts), cap)
+    max_pkts = min(max_pkts, 2 ** 31 - 1)
+    frag_off = np.empty(max(n_free, 1), dtype=np.uint64)
+    frag_len = np.empty(max(n_free, 1), dtype=np.uint32)
+    first = np.zeros(max(max_pkts, 0) + 1, dtype=np.uint32)
+    if max_pkts <= 0:
+        return 0, frag_off[:0], frag_len[:0], first[:1], 0
+    nf = ctypes.c_uint32(0)
+    r = _lib.load().rns_io_recv_batch_chain(int(fd), pool.ctypes.data, buf_bytes, free.ctypes.data, n_free, mru,
+                                            max_pkts, frag_off.ctypes.data, frag_len.ctypes.data, first.ctypes.data,
+                                            ctypes.byref(nf), int(timeout_ms))
+    if r < 0:
+        raise _lib.ChecksumError(r, "rns_io_recv_batch_chain")
+    return r, frag_off[:nf.value], frag_len[:nf.value], first[:r + 1], int(nf.value)
 
 
 def send_batch(fd: int, arena: np.ndarray, off: np.ndarray, length: np.ndarray) -> int:

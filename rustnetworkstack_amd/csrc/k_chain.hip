@@ -81,6 +81,33 @@ int launch_txfin_packed(const CsumArgs &a, hipStream_t st)
     return hip_status(hipGetLastError());
 }
 
+// Receive verify over chains (rns_rx_verify_chain_dev): the chain kernel's receive form, one wave per
+// K*64 datagrams.
+int launch_rx_chain(const CsumArgs &a, uint32_t K, bool nt, hipStream_t st)
+{
+    const uint64_t waves = (static_cast<uint64_t>(a.n) + 64 * K - 1) / (64 * K);
+    const dim3 grid(static_cast<uint32_t>(waves)), block(kChainBlock);
+    const bool buf = buf_records(a) < kOobOffset;
+#define RNS_RX_CHAIN_LAUNCH(KM)                                                        \
+    if (nt && buf)                                                                     \
+        hipLaunchKernelGGL((rx_chain_kernel<true, true, KM>), grid, block, 0, st, a);  \
+    else if (nt)                                                                       \
+        hipLaunchKernelGGL((rx_chain_kernel<true, false, KM>), grid, block, 0, st, a); \
+    else if (buf)                                                                      \
+        hipLaunchKernelGGL((rx_chain_kernel<false, true, KM>), grid, block, 0, st, a); \
+    else                                                                               \
+        hipLaunchKernelGGL((rx_chain_kernel<false, false, KM>), grid, block, 0, st, a);
+    if (K == 1) {
+        RNS_RX_CHAIN_LAUNCH(1)
+    } else if (K == 2) {
+        RNS_RX_CHAIN_LAUNCH(2)
+    } else {
+        RNS_RX_CHAIN_LAUNCH(kChainMaxK)
+    }
+#undef RNS_RX_CHAIN_LAUNCH
+    return hip_status(hipGetLastError());
+}
+
 template int launch_chain<false>(const CsumArgs &, uint32_t, bool, bool, hipStream_t);
 template int launch_chain<true>(const CsumArgs &, uint32_t, bool, bool, hipStream_t);
 template int launch_txrows<false>(const CsumArgs &, hipStream_t);

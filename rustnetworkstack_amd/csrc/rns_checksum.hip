@@ -220,6 +220,21 @@ int rns_csum_batch_strided_dev(const uint8_t *d_arena, uint64_t arena_bytes, uin
 
 }  // extern "C"
 
+// Packets per lane K of the chain kernels for a mean fragment count (see chain_launch).
+static uint32_t chain_pick_k(double mean)
+{
+    uint32_t K = 1;
+    double best = -1.0;
+    for (uint32_t k = 1; k <= kChainMaxK; ++k) {
+        const double fr = k * mean, fill = fr > 0 ? fr / std::ceil(fr) : 1.0;
+        if (fill > best + 0.02) {
+            best = fill;
+            K = k;
+        }
+    }
+    return K;
+}
+
 // Fragment chains: the chain kernel's arguments and launch (checksum or head-fragment fill).
 template <bool FILL>
 static int chain_launch(CsumArgs &a, const uint64_t *d_frag_off, const uint32_t *d_frag_len, uint32_t n_frags,
@@ -241,15 +256,7 @@ static int chain_launch(CsumArgs &a, const uint64_t *d_frag_off, const uint32_t 
     // batches (a partial batch runs the class rounds for few bytes), so pick the K
     // in 1..8 whose expected fragment count K*mean fills its batches best.
     const double mean = static_cast<double>(n_frags) / static_cast<double>(n_pkts);
-    uint32_t K = 1;
-    double best = -1.0;
-    for (uint32_t k = 1; k <= kChainMaxK; ++k) {
-        const double fr = k * mean, fill = fr > 0 ? fr / std::ceil(fr) : 1.0;
-        if (fill > best + 0.02) {
-            best = fill;
-            K = k;
-        }
-    }
+    const uint32_t K = chain_pick_k(mean);
     a.chain_k = K;
     // transmit-shaped chains: heads + a packed payload region.  A batch whose mean fragment
     // count already exceeds the shape (a head + kRunFrags payload fragments) has most of its
@@ -464,6 +471,41 @@ int rns_rx_verify_strided_dev(const uint8_t *d_arena, uint64_t arena_bytes, uint
     a.local4_sum = be_sum(local_ipv4, 4);
     a.local6_sum = be_sum(local_ipv6, 16);
     return launch_strided_rx(a, static_cast<hipStream_t>(stream));
+}
+
+int rns_rx_verify_chain_dev(const uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_frag_off,
+                            const uint32_t *d_frag_len, uint32_t n_frags, const uint32_t *d_first, uint32_t n_pkts,
+                            const uint8_t *local_ipv4, const uint8_t *local_ipv6, uint8_t *d_status, uint16_t *d_l4_sum,
+                            void *stream)
+{
+    if (n_pkts == 0)
+        return RNS_OK;
+    if (!d_arena || !d_first || !d_status || !local_ipv4 || !local_ipv6 || (n_frags && (!d_frag_off || !d_frag_len)) ||
+        n_pkts > RNS_CHAIN_MAX_PACKETS)
+        return RNS_E_INVALID;
+    if (int st = check_device())
+        return st;
+    CsumArgs a{};
+    set_arena(a, d_arena, arena_bytes);
+    a.off = d_frag_off;
+    a.len = d_frag_len;
+    a.n = n_pkts;
+    a.flags = RNS_FLAG_COMPLEMENT;
+    a.first = d_first;
+    a.n_frags = n_frags;
+    a.status = d_status;
+    a.l4_out = d_l4_sum;
+    a.local4_sum = be_sum(local_ipv4, 4);
+    a.local6_sum = be_sum(local_ipv6, 16);
+    const double mean = static_cast<double>(n_frags) / static_cast<double>(n_pkts);
+    a.chain_k = chain_pick_k(mean);
+    // No fragment-length hint travels, so the typical fragment length is estimated: the arena's
+    // bytes per fragment (a pool's buffer size), every datagram's last fragment half full on
+    // average.  512-byte buffers: MTU datagrams (3 fragments) ~427 B, nontemporal loads; IMIX (1.5
+    // fragments) ~341 B, the temporal form with the tiny class — as chain_launch decides from its hint.
+    const double frag_est = mean > 0.5 ? static_cast<double>(arena_bytes) / n_frags * (mean - 0.5) / mean : 0.0;
+    const bool nt = n_frags == 0 || frag_est >= RNS_CHAIN_NT_FROM;
+    return launch_rx_chain(a, a.chain_k, nt, static_cast<hipStream_t>(stream));
 }
 
 int rns_tx_fill_packed_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_blk_off, const uint16_t *d_len16,

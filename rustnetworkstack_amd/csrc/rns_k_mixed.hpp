@@ -457,6 +457,11 @@ __device__ __forceinline__ uint32_t stash_sum_be(const uint4 (&ch)[NCH], int lo,
 
 // h = the datagram's first 24 bytes (head_from_stash), L = its length (the buffer length,
 // as the stack sees it).
+// CHAIN (rns_k_chain_rx.hpp): the datagram is a fragment chain and L = its FIRST fragment's
+// length, all header() shows (ip.rs:39, 69, 115): IPv6 needs header[8..24] there, the caller
+// checks the chain's total against trim_head(40), and ph is the seed without the L4 length
+// (the caller adds it once the total is known).
+template <bool CHAIN = false>
 __device__ __forceinline__ RxParse rx_parse(const uint32_t (&h)[6], uint32_t L, uint32_t local4_sum,
                                             uint32_t local6_sum)
 {
@@ -479,7 +484,7 @@ __device__ __forceinline__ RxParse rx_parse(const uint32_t (&h)[6], uint32_t L, 
         v4src = true;
     } else if (version == 6) {
         r.hdr = 40;
-        if (L < 40)                                          // trim_head(IPV6_HEADER_LEN) would panic
+        if (L < (CHAIN ? 24u : 40u))                         // trim_head(IPV6_HEADER_LEN) would panic
             return r;
         r.meta = kMetaV6;
         proto = p(6);                                        // ip.rs:116
@@ -488,7 +493,7 @@ __device__ __forceinline__ RxParse rx_parse(const uint32_t (&h)[6], uint32_t L, 
     } else {
         return r;                                            // "IP: Invalid version field"
     }
-    const uint32_t l4len = L - r.hdr;                        // packet.len() after trim_head
+    const uint32_t l4len = CHAIN ? 0u : L - r.hdr;           // packet.len() after trim_head
     if (proto == 6) {                                        // tcp.rs:838-850: dest = local address of src's family
         r.ph = v4src ? fold16(src_sum + local4_sum + 6 + (l4len & 0xffff))
                      : fold16(src_sum + local6_sum + (l4len >> 16) + (l4len & 0xffff) + 6);

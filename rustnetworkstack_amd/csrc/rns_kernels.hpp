@@ -30,5 +30,6 @@
 #include "rns_k_rounds.hpp"
 #include "rns_k_mixed.hpp"
 #include "rns_k_chain.hpp"
+#include "rns_k_chain_rx.hpp"
 #include "rns_k_stream.hpp"
 #include "rns_k_rows.hpp"

@@ -84,6 +84,7 @@ extern template int launch_txrows<false>(const CsumArgs &, hipStream_t);
 extern template int launch_txrows<true>(const CsumArgs &, hipStream_t);
 int launch_txfin(const CsumArgs &a, hipStream_t st);
 int launch_txfin_packed(const CsumArgs &a, hipStream_t st);
+int launch_rx_chain(const CsumArgs &a, uint32_t K, bool nt, hipStream_t st);  // receive verify over chains
 // k_stash.hip: the class kernel's stash modes on one-wave workgroups
 int launch_fill(const CsumArgs &a, dim3 grid, hipStream_t st);
 int launch_rx(const CsumArgs &a, dim3 grid, hipStream_t st);

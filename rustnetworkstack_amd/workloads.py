@@ -434,3 +434,109 @@ class TxChainBatch:
     @property
     def n_frags(self) -> int:
         return int(self.layout.frag_off.shape[0])
+
+
+# ---------------------------------------------------------------------------
+# Receive chains (rns_rx_verify_chain_dev): datagrams as recv_packet leaves them
+# (netif.rs:65-83) — read into pool fragments of FRAGMENT_SIZE bytes (buf.rs:50), every
+# fragment full but the last.  The pool hands buffers out in order after start-up and in
+# any order once buffers have been freed and reused: `shuffled`.
+# ---------------------------------------------------------------------------
+SHUFFLE_STREAM = 0x5AFF1E5AFF1E  # xor-ed into the data seed for the buffer permutation
+
+
+@dataclass
+class RxChainLayout:
+    """Received datagrams of a config as NetBuffer chains: datagram i (flat.length[i] bytes) =
+    fragments first[i] .. first[i+1], fragment j in pool buffer buf[j] (frag_off[j] = buf[j] *
+    buf_bytes).  `flat` is the same batch with every datagram padded to whole buffers: its arena,
+    cut into buf_bytes rows, is the pool in fragment order."""
+    name: str
+    flat: Layout
+    buf_bytes: int
+    buf: np.ndarray        # int64 [n_frags]
+    frag_off: np.ndarray   # uint64
+    frag_len: np.ndarray   # uint32
+    first: np.ndarray      # uint32 [n + 1]
+    shuffled: bool
+
+    @property
+    def n(self) -> int:
+        return int(self.first.shape[0] - 1)
+
+    @property
+    def n_frags(self) -> int:
+        return int(self.frag_off.shape[0])
+
+
+def rx_chain_layout(config: str, n: int | None = None, buf_bytes: int = 512, shuffled: bool = False,
+                    data_seed: int = DATA_SEED) -> RxChainLayout:
+    """The datagrams of `config` laid into `buf_bytes`-byte pool buffers as recv_packet would:
+    ceil(L / buf_bytes) buffers each, the last fragment the remainder; buffers in order, or
+    (shuffled) a seeded permutation of the pool."""
+    flat = make_layout(config, n=n, data_seed=data_seed, align=buf_bytes)
+    L = flat.length.astype(np.int64)
+    nfr = (L + buf_bytes - 1) // buf_bytes
+    first = np.zeros(flat.n + 1, dtype=np.int64)
+    np.cumsum(nfr, out=first[1:])
+    nf = int(first[-1])
+    assert nf * buf_bytes == flat.arena_bytes
+    frag_len = np.full(nf, buf_bytes, dtype=np.int64)
+    if flat.n:
+        frag_len[first[1:] - 1] = L - (nfr - 1) * buf_bytes
+    if shuffled:
+        buf = np.argsort(splitmix64(data_seed ^ SHUFFLE_STREAM, nf), kind="stable").astype(np.int64)
+    else:
+        buf = np.arange(nf, dtype=np.int64)
+    return RxChainLayout(name=config, flat=flat, buf_bytes=buf_bytes, buf=buf,
+                         frag_off=(buf * buf_bytes).astype(np.uint64), frag_len=frag_len.astype(np.uint32),
+                         first=first.astype(np.uint32), shuffled=shuffled)
+
+
+class RxChainBatch:
+    """A received batch as NetBuffer chains in HBM: the IPv4/TCP datagrams make_verify_batch
+    builds (same headers, same corrupt_mask) in the pool buffers of rx_chain_layout, with the
+    fragment descriptors, a status array and the statuses rns_rx_verify_chain_dev must give."""
+
+    def __init__(self, config: str, device, n: int | None = None, buf_bytes: int = 512, shuffled: bool = False,
+                 data_seed: int = DATA_SEED):
+        import torch
+
+        from . import _lib
+        lay = rx_chain_layout(config, n=n, buf_bytes=buf_bytes, shuffled=shuffled, data_seed=data_seed)
+        self.layout = lay
+        self.device = torch.device(device)
+        b = DeviceBatch(lay.flat, self.device)
+        make_verify_batch(b)
+        nf = lay.n_frags
+        if shuffled:
+            rows = b.arena[:nf * buf_bytes].view(nf, buf_bytes)
+            pool = torch.empty(nf * buf_bytes + 16, dtype=torch.uint8, device=self.device)
+            prow = pool[:nf * buf_bytes].view(nf, buf_bytes)
+            d_buf = torch.from_numpy(lay.buf).to(self.device)
+            step = 1 << 20  # buffers per scatter (bounds the temporaries)
+            for i in range(0, nf, step):
+                prow[d_buf[i:i + step]] = rows[i:i + step]
+            self.arena = pool
+        else:
+            self.arena = b.arena
+        self.d_off = torch.from_numpy(lay.frag_off.view(np.int64)).to(self.device)
+        self.d_len = torch.from_numpy(lay.frag_len.view(np.int32)).to(self.device)
+        self.d_first = torch.from_numpy(lay.first.view(np.int32)).to(self.device)
+        self.status = torch.empty(lay.n, dtype=torch.uint8, device=self.device)
+        self.l4_sum = torch.empty(lay.n, dtype=torch.uint16, device=self.device)
+        ok = _lib.RNS_RX_IP_OK | _lib.RNS_RX_L4_OK | _lib.RNS_RX_ACCEPT
+        self.expected_status = np.where(corrupt_mask(lay.n), _lib.RNS_RX_IP_OK, ok).astype(np.uint8)
+        self.expected_bad = b.expected_bad
+
+    @property
+    def n(self) -> int:
+        return self.layout.n
+
+    @property
+    def n_frags(self) -> int:
+        return self.layout.n_frags
+
+    @property
+    def payload_bytes(self) -> int:
+        return self.layout.flat.payload_bytes

@@ -22,6 +22,11 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
 * tx_chain_packed — rns_tx_fill_chain_packed_dev: the same finalize of the same arena (one payload
              fragment) over the compact descriptors, 3 B per datagram + 16 B per 64 instead of 28 B;
              timed in rounds alternating with tx_chain's, and both rows carry every round's time
+* rx_verify_chain — rns_rx_verify_chain_dev: receive verify of the datagrams as recv_packet leaves
+             them, NetBuffer chains in 512-byte pool buffers (workloads.RxChainBatch), the buffers in
+             order and shuffled; next to it csum_chain, rns_csum_chain_dev over the same chains of the
+             same arena (the yardstick: an entry that reads the same bytes), timed in alternating
+             rounds, both rows carrying every round's time
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -136,6 +141,9 @@ def main():
             for frag in (int(x) for x in args.tx_frags.split(",")):
                 if "tx_chain" in ops or frag == 0:
                     r.update(bench_tx_chain(cfg, dev, args, frag, packed="tx_chain_packed" in ops and frag == 0))
+        if "rx_verify_chain" in ops:
+            for shuffled in (False, True):
+                r.update(bench_rx_chain(cfg, dev, args, shuffled))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -313,6 +321,42 @@ def bench_tx_chain(cfg, dev, args, frag, packed=False):
     else:
         res[tag] = row(timed_rounds([csr], args.steps, args.rounds)[0], 12 * nf + 4 * (n + 1))
     del arena
+    torch.cuda.empty_cache()
+    return res
+
+
+def bench_rx_chain(cfg, dev, args, shuffled):
+    """Receive verify over NetBuffer chains and the plain chain checksum of the same chains, in
+    alternating rounds on one arena."""
+    from rustnetworkstack_amd.batch import rx_verify_chain
+    from rustnetworkstack_amd.workloads import LOCAL4, LOCAL6, RxChainBatch
+    rb = RxChainBatch(cfg, dev, shuffled=shuffled)
+    n, pay, nf = rb.n, rb.payload_bytes, rb.n_frags
+    out = torch.empty(n, dtype=torch.uint16, device=dev)
+    hint = int(round(pay / nf))
+    rx = lambda: rx_verify_chain(rb.arena, rb.d_off, rb.d_len, rb.d_first, LOCAL4, LOCAL6,  # noqa: E731
+                                 status=rb.status, l4_sum=rb.l4_sum)
+    cs = lambda: csum_chain(rb.arena, rb.d_off, rb.d_len, rb.d_first, None, complement=True, out=out,  # noqa: E731
+                            frag_len_hint=hint)
+    rx()
+    torch.cuda.synchronize()
+    st = rb.status.cpu().numpy()
+    as_expected = bool(np.array_equal(st, rb.expected_status))
+    rs_rx, rs_cs = timed_rounds([rx, cs], args.steps, args.rounds)
+
+    def row(rs, result_bytes):
+        ms = rs[len(rs) // 2]
+        return {"us": round(ms * 1e3, 1), "GBps": round((pay + result_bytes) / ms / 1e6, 1), "packets": n,
+                "fragments": nf, "rounds_us": [round(x * 1e3, 1) for x in rs],
+                "spread_us": round((rs[-1] - rs[0]) * 1e3, 1)}
+
+    tag = "_shuffled" if shuffled else ""
+    res = {"rx_verify_chain" + tag: row(rs_rx, 3 * n), "csum_chain" + tag: row(rs_cs, 2 * n)}
+    rxr = res["rx_verify_chain" + tag]
+    rxr["accepted"] = int((st == 0x43).sum())
+    rxr["statuses_as_expected"] = as_expected
+    rxr["ratio_to_csum_chain"] = round(rs_rx[len(rs_rx) // 2] / rs_cs[len(rs_cs) // 2], 4)
+    del rb
     torch.cuda.empty_cache()
     return res
 
