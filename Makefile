@@ -9,30 +9,16 @@ CSRC     := $(PKG)/csrc
 BUILD    := $(PKG)/build
 LIB      := $(PKG)/librns_checksum.so
 
-CABI_TEST := tests/c/test_batch_abi
+# Plain C callers of the C ABI (no torch): built here, run on a GPU by tests/test_c_caller.py
+# (test_batch_abi), tests/test_c_caller_tx_chain_packed.py (the compact-descriptor chain finalize)
+# and tests/test_c_caller_rx_chain.py (the receive verify over fragment chains).
+CABI_TESTS := tests/c/test_batch_abi tests/c/test_tx_chain_packed_abi tests/c/test_rx_chain_abi
 
-CABI_TXCP_TEST := tests/c/test_tx_chain_packed_abi
+all: $(LIB) oracle $(CABI_TESTS)
 
-CABI_RXC_TEST := tests/c/test_rx_chain_abi
-
-all: $(LIB) oracle $(CABI_TEST) $(CABI_TXCP_TEST) $(CABI_RXC_TEST)
-
-# A plain C caller of the C ABI (no torch): built here, run by tests/test_c_caller.py on a GPU.
-$(CABI_TEST): tests/c/test_batch_abi.c oracle/csum_oracle.c include/rns_checksum.h $(LIB)
+$(CABI_TESTS): tests/c/%: tests/c/%.c oracle/csum_oracle.c include/rns_checksum.h $(LIB)
 	gcc -std=gnu11 -O1 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include \
-	    tests/c/test_batch_abi.c oracle/csum_oracle.c -L$(PKG) -lrns_checksum -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
-	    -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread -o $@
-
-# The same for the compact-descriptor chain finalize: run by tests/test_c_caller_tx_chain_packed.py.
-$(CABI_TXCP_TEST): tests/c/test_tx_chain_packed_abi.c oracle/csum_oracle.c include/rns_checksum.h $(LIB)
-	gcc -std=gnu11 -O1 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include \
-	    tests/c/test_tx_chain_packed_abi.c oracle/csum_oracle.c -L$(PKG) -lrns_checksum -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
-	    -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread -o $@
-
-# The same for the receive verify over fragment chains: run by tests/test_c_caller_rx_chain.py.
-$(CABI_RXC_TEST): tests/c/test_rx_chain_abi.c oracle/csum_oracle.c include/rns_checksum.h $(LIB)
-	gcc -std=gnu11 -O1 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include \
-	    tests/c/test_rx_chain_abi.c oracle/csum_oracle.c -L$(PKG) -lrns_checksum -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
+	    $< oracle/csum_oracle.c -L$(PKG) -lrns_checksum -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
 	    -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread -o $@
 
 # One translation unit per kernel family (rns_launch.hpp), compiled in parallel (make -j).
@@ -86,7 +72,7 @@ asm: $(HIP_SRCS)
 	    --cuda-device-only -S ../../../$$f -o $$(basename $$f .hip).s) || exit 1; done
 
 clean:
-	rm -rf $(BUILD) $(LIB) $(CABI_TEST) $(CABI_TXCP_TEST) $(CABI_RXC_TEST)
+	rm -rf $(BUILD) $(LIB) $(CABI_TESTS)
 	$(MAKE) -C oracle clean
 
 .PHONY: all oracle resources asm clean ab

@@ -13,6 +13,11 @@ here is a packet ARENA (one uint8 buffer) plus per-packet descriptors:
 PyTorch only provides device memory and the stream; the compute is the
 hand-written gfx950 kernel in csrc/rns_checksum.hip.  There is no CPU fallback:
 a missing library or device raises.
+
+Every wrapper checks its tensors before the call: dtype and contiguity (TypeError /
+ValueError), one size per descriptor form, and that every descriptor, seed, field and
+output tensor is on the arena's device (ValueError) — a pointer of another device must
+never reach a kernel.
 """
 from __future__ import annotations
 
@@ -36,25 +41,94 @@ def _require_cuda(t: torch.Tensor, name: str, dtypes) -> None:
 
 
 _U16 = (torch.uint16, torch.int16)
+_U8 = (torch.uint8,)
+_I32 = (torch.int32,)
+_I64 = (torch.int64,)
 
 
-def _rx_outputs(dev: torch.device, n: int, status, l4_sum, inputs):
-    """Receive verify's outputs (caller-supplied or new) and its inputs' device: the kernel
-    writes n entries to each output, so an undersized or misplaced buffer is refused."""
-    for name, t in inputs:
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, the arena on {dev}")
+def _descriptors(arena: torch.Tensor, *desc) -> torch.device:
+    """The arena and its descriptor tensors ``(name, tensor, dtypes)``: GPU tensors of the
+    right dtype, contiguous, all on the arena's device (which is returned)."""
+    _require_cuda(arena, "arena", _U8)
+    for name, t, dtypes in desc:
+        _require_cuda(t, name, dtypes)
+    for name, t, _ in desc:
+        if t.device != arena.device:
+            raise ValueError(f"{name} is on {t.device}, the arena on {arena.device}")
+    return arena.device
+
+
+def _per_packet(t: torch.Tensor | None, name: str, n: int, dev: torch.device, dtypes=_U16) -> int | None:
+    """Pointer of an optional per-packet tensor (seed / field / out / l4_sum: 16-bit; status:
+    uint8) of exactly n entries on the arena's device, or None."""
+    if t is None:
+        return None
+    _require_cuda(t, name, dtypes)
+    if t.numel() != n or t.device != dev:
+        raise ValueError(f"{name} must have one entry per packet ({n}) on {dev}")
+    return t.data_ptr()
+
+
+def _out(out: torch.Tensor | None, n: int, dev: torch.device) -> torch.Tensor:
+    """The checksum output: the caller's (checked like any per-packet tensor) or a new one."""
+    if out is None:
+        return torch.empty(n, dtype=torch.uint16, device=dev)
+    _per_packet(out, "out", n, dev)
+    return out
+
+
+def _status(status: torch.Tensor | None, n: int, dev: torch.device) -> torch.Tensor:
+    """The uint8 status output: the kernel writes n entries, so an undersized or misplaced
+    buffer is refused."""
     if status is None:
-        status = torch.empty(n, dtype=torch.uint8, device=dev)
-    else:
-        _require_cuda(status, "status", (torch.uint8,))
-        if status.numel() != n or status.device != dev:
-            raise ValueError(f"status must be {n} uint8 entries on {dev}")
-    if l4_sum is not None:
-        _require_cuda(l4_sum, "l4_sum", _U16)
-        if l4_sum.numel() != n or l4_sum.device != dev:
-            raise ValueError(f"l4_sum must be {n} 16-bit entries on {dev}")
-    return status, (l4_sum.data_ptr() if l4_sum is not None else None)
+        return torch.empty(n, dtype=torch.uint8, device=dev)
+    _per_packet(status, "status", n, dev, _U8)
+    return status
+
+
+def _explicit(arena, off, length, off_dtypes=_I64) -> tuple[int, torch.device]:
+    """Explicit descriptors (off, length): (n, device)."""
+    dev = _descriptors(arena, ("off", off, off_dtypes), ("length", length, _I32))
+    n = off.numel()
+    if length.numel() != n:
+        raise ValueError("off and length must have the same number of packets")
+    if n >= 2 ** 32:
+        raise ValueError("at most 2^32-1 packets per call")
+    return n, dev
+
+
+def _packed(arena, blk_off, len16, align_log2, align_range, exact: bool = False) -> tuple[int, torch.device]:
+    """Packed descriptors (one offset per 64 packets, u16 lengths): (n, device).  ``exact``:
+    exactly ceil(n/64) block offsets, else at least that many.  ``align_range``: the wrapper's
+    (lowest, highest) align_log2, or None where the C ABI alone checks it."""
+    dev = _descriptors(arena, ("blk_off", blk_off, _I64), ("len16", len16, _U16))
+    n = len16.numel()
+    need = (n + 63) // 64
+    if blk_off.numel() != need if exact else blk_off.numel() < need:
+        raise ValueError("blk_off must have one entry per 64 packets")
+    if align_range is not None and not align_range[0] <= align_log2 <= align_range[1]:
+        raise ValueError(f"align_log2 must be in {align_range[0]}..{align_range[1]}")
+    if n >= 2 ** 32:
+        raise ValueError("at most 2^32-1 packets per call")
+    return n, dev
+
+
+def _chain(arena, frag_off, frag_len, first) -> tuple[int, int, torch.device]:
+    """Chain descriptors (CSR: packet i = fragments first[i] .. first[i+1]): (n, n_frags, device)."""
+    dev = _descriptors(arena, ("frag_off", frag_off, _I64), ("frag_len", frag_len, _I32), ("first", first, _I32))
+    nf = frag_off.numel()
+    n = first.numel() - 1
+    if frag_len.numel() != nf or n < 0:
+        raise ValueError("frag_off/frag_len sizes differ or first is empty")
+    if n > _lib.RNS_CHAIN_MAX_PACKETS or nf >= 2 ** 32:
+        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} packets and 2^32-1 fragments per chain call")
+    return n, nf, dev
+
+
+def _local_addrs(local_ipv4, local_ipv6) -> tuple[bytes, bytes]:
+    if len(local_ipv4) != 4 or len(local_ipv6) != 16:
+        raise ValueError("local_ipv4 must be 4 bytes and local_ipv6 16 bytes")
+    return bytes(local_ipv4), bytes(local_ipv6)
 
 
 def _bad_ptr(bad: torch.Tensor | None, dev: torch.device):
@@ -62,17 +136,53 @@ def _bad_ptr(bad: torch.Tensor | None, dev: torch.device):
     least one entry on the arena's device, or None."""
     if bad is None:
         return None
-    _require_cuda(bad, "bad", (torch.int32,))
+    _require_cuda(bad, "bad", _I32)
     if bad.numel() < 1 or bad.device != dev:
         raise ValueError(f"bad must be an int32 counter (at least 1 entry) on {dev}")
     return bad.data_ptr()
+
+
+def _flags(complement: bool, runs: bool = False, tx_packed: bool = False) -> int:
+    return (_lib.RNS_FLAG_COMPLEMENT if complement else 0) | (_lib.RNS_FLAG_CHAIN_RUNS if runs else 0) | \
+        (_lib.RNS_FLAG_CHAIN_TX_PACKED if tx_packed else 0)
 
 
 def _stream_handle(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
-class PreparedBatch:
+def _call(name: str, dev: torch.device, *args) -> None:
+    """One C ABI call on the arena's device and its current stream (the last argument)."""
+    with torch.cuda.device(dev):
+        st = getattr(_lib.load(), name)(*args, _stream_handle(dev))
+    _lib.check(st, name)
+
+
+class _BoundBatch:
+    """A batch bound to one C ABI entry point: the subclass's constructor validates and
+    marshals (``_bind``), so each launch is a single ctypes call with pre-marshalled
+    arguments.  Launches go to the stream that was current at construction."""
+
+    def _bind(self, name: str, args: tuple, keep: tuple, out: torch.Tensor, n: int, dev: torch.device) -> None:
+        self._name, self._fn, self._args = name, getattr(_lib.load(), name), args + (_stream_handle(dev),)
+        self._keep = keep  # keep the tensors alive as long as the bound pointers
+        self.out, self.n, self.device = out, n, dev
+
+    def __call__(self) -> torch.Tensor:
+        if self.n:
+            # The bound stream handle belongs to self.device (the null stream is 0): launch
+            # with that device current even if the caller has switched devices since.
+            if torch.cuda.current_device() != self.device.index:
+                with torch.cuda.device(self.device):
+                    st = self._fn(*self._args)
+            else:
+                st = self._fn(*self._args)
+            if st != _lib.RNS_OK:
+                raise _lib.ChecksumError(st, self._name)
+        return self.out
+
+
+class PreparedBatch(_BoundBatch):
     """A device-resident batch bound to the C ABI once: validation and argument
     marshalling happen here, so each launch is a single ctypes call (a few µs of
     host time).  Launches go to the stream that was current at construction.
@@ -91,71 +201,26 @@ class PreparedBatch:
                  seed: torch.Tensor | None = None, *, complement: bool = False, out: torch.Tensor | None = None,
                  len_hint: int = 0, bad: torch.Tensor | None = None,
                  shape: tuple[int, int, int, int] | None = None, compact: bool = False):
-        _require_cuda(arena, "arena", (torch.uint8,))
-        _require_cuda(off, "off", (torch.int32,) if compact else (torch.int64,))
-        _require_cuda(length, "length", (torch.int32,))
+        n, dev = _explicit(arena, off, length, _I32 if compact else _I64)
         if compact and shape is not None:
             raise ValueError("shape overrides take 64-bit offsets")
-        n = off.numel()
-        if length.numel() != n:
-            raise ValueError("off and length must have the same number of packets")
-        if n >= 2 ** 32:
-            raise ValueError("at most 2^32-1 packets per call")
-        dev = arena.device
-        for name, t in (("off", off), ("length", length)):
-            if t.device != dev:
-                raise ValueError(f"{name} is on {t.device}, arena on {dev}")
-        seed_ptr = None
-        if seed is not None:
-            _require_cuda(seed, "seed", _U16)
-            if seed.numel() != n or seed.device != dev:
-                raise ValueError("seed must have one entry per packet on the arena's device")
-            seed_ptr = seed.data_ptr()
-        if out is None:
-            out = torch.empty(n, dtype=torch.uint16, device=dev)
-        else:
-            _require_cuda(out, "out", _U16)
-            if out.numel() != n or out.device != dev:
-                raise ValueError("out must have one entry per packet on the arena's device")
-        bad_ptr = _bad_ptr(bad, arena.device)
-        lib = _lib.load()
-        flags = _lib.RNS_FLAG_COMPLEMENT if complement else 0
-        stream = _stream_handle(dev)
-        # keep the tensors alive as long as the bound pointers
-        self._keep = (arena, off, length, seed, out, bad)
-        self.out = out
-        self.n = n
-        self.device = dev
-        self._name = "rns_csum_batch_dev_off32" if compact else "rns_csum_batch_dev"
+        seed_ptr = _per_packet(seed, "seed", n, dev)
+        out = _out(out, n, dev)
+        head = (arena.data_ptr(), arena.numel(), off.data_ptr(), length.data_ptr(), seed_ptr, out.data_ptr(), n,
+                _flags(complement))
+        keep = (arena, off, length, seed, out, bad)
         if shape is None:
-            self._fn = getattr(lib, self._name)
-            self._args = (arena.data_ptr(), arena.numel(), off.data_ptr(), length.data_ptr(), seed_ptr,
-                          out.data_ptr(), n, flags, int(len_hint), bad_ptr, stream)
+            self._bind("rns_csum_batch_dev_off32" if compact else "rns_csum_batch_dev",
+                       head + (int(len_hint), _bad_ptr(bad, dev)), keep, out, n, dev)
         else:
             var, g, u, mb = shape
-            self._fn = lib.rns_csum_batch_dev_cfg
-            self._args = (arena.data_ptr(), arena.numel(), off.data_ptr(), length.data_ptr(), seed_ptr,
-                          out.data_ptr(), n, flags, var, g, u, mb, bad_ptr, stream)
-
-    def __call__(self) -> torch.Tensor:
-        if self.n:
-            # The bound stream handle belongs to self.device (the null stream is 0): launch
-            # with that device current even if the caller has switched devices since.
-            if torch.cuda.current_device() != self.device.index:
-                with torch.cuda.device(self.device):
-                    st = self._fn(*self._args)
-            else:
-                st = self._fn(*self._args)
-            if st != _lib.RNS_OK:
-                raise _lib.ChecksumError(st, self._name)
-        return self.out
+            self._bind("rns_csum_batch_dev_cfg", head + (var, g, u, mb, _bad_ptr(bad, dev)), keep, out, n, dev)
 
 
 def packed_layout(length, align_log2: int = 4, first_off: int = 0):
     """Offsets of the packed form (rns_packed_layout): packets back to back in index
     order, each starting at the next multiple of 2**align_log2.  ``length``: lengths
     (< 65536).  Returns (blk_off uint64 [ceil(n/64)], off uint64 [n], end)."""
-    import numpy as np
     ln = np.asarray(length)
     if ln.size and (int(ln.max()) > 0xFFFF or int(ln.min()) < 0):
         raise ValueError("packed descriptors hold u16 lengths (< 65536)")
@@ -170,7 +235,7 @@ def packed_layout(length, align_log2: int = 4, first_off: int = 0):
     return blk[:(n + 63) // 64], off[:n], int(end.value)
 
 
-class PackedBatch:
+class PackedBatch(_BoundBatch):
     """A device-resident batch in the packed form (rns_csum_batch_packed_dev), bound
     once like PreparedBatch: ``blk_off`` int64 [ceil(n/64)] (the offset of every 64th
     packet), ``len16`` int16/uint16 [n] (lengths as unsigned 16-bit), packets back to
@@ -179,49 +244,13 @@ class PackedBatch:
     def __init__(self, arena: torch.Tensor, blk_off: torch.Tensor, len16: torch.Tensor,
                  seed: torch.Tensor | None = None, *, align_log2: int = 4, complement: bool = False,
                  out: torch.Tensor | None = None, len_hint: int = 0, bad: torch.Tensor | None = None):
-        _require_cuda(arena, "arena", (torch.uint8,))
-        _require_cuda(blk_off, "blk_off", (torch.int64,))
-        _require_cuda(len16, "len16", _U16)
-        n = len16.numel()
-        if blk_off.numel() != (n + 63) // 64:
-            raise ValueError("blk_off must have one entry per 64 packets")
-        if not 0 <= align_log2 <= 12:
-            raise ValueError("align_log2 must be in 0..12")
-        dev = arena.device
-        for name, t in (("blk_off", blk_off), ("len16", len16)):
-            if t.device != dev:
-                raise ValueError(f"{name} is on {t.device}, arena on {dev}")
-        seed_ptr = None
-        if seed is not None:
-            _require_cuda(seed, "seed", _U16)
-            if seed.numel() != n or seed.device != dev:
-                raise ValueError("seed must have one entry per packet on the arena's device")
-            seed_ptr = seed.data_ptr()
-        if out is None:
-            out = torch.empty(n, dtype=torch.uint16, device=dev)
-        else:
-            _require_cuda(out, "out", _U16)
-            if out.numel() != n or out.device != dev:
-                raise ValueError("out must have one entry per packet on the arena's device")
-        bad_ptr = _bad_ptr(bad, arena.device)
-        lib = _lib.load()
-        self._keep = (arena, blk_off, len16, seed, out, bad)
-        self.out, self.n, self.device = out, n, dev
-        self._fn = lib.rns_csum_batch_packed_dev
-        self._args = (arena.data_ptr(), arena.numel(), blk_off.data_ptr(), len16.data_ptr(), int(align_log2),
-                      seed_ptr, out.data_ptr(), n, _lib.RNS_FLAG_COMPLEMENT if complement else 0, int(len_hint),
-                      bad_ptr, _stream_handle(dev))
-
-    def __call__(self) -> torch.Tensor:
-        if self.n:
-            if torch.cuda.current_device() != self.device.index:
-                with torch.cuda.device(self.device):
-                    st = self._fn(*self._args)
-            else:
-                st = self._fn(*self._args)
-            if st != _lib.RNS_OK:
-                raise _lib.ChecksumError(st, "rns_csum_batch_packed_dev")
-        return self.out
+        n, dev = _packed(arena, blk_off, len16, align_log2, (0, 12), exact=True)
+        seed_ptr = _per_packet(seed, "seed", n, dev)
+        out = _out(out, n, dev)
+        self._bind("rns_csum_batch_packed_dev",
+                   (arena.data_ptr(), arena.numel(), blk_off.data_ptr(), len16.data_ptr(), int(align_log2), seed_ptr,
+                    out.data_ptr(), n, _flags(complement), int(len_hint), _bad_ptr(bad, dev)),
+                   (arena, blk_off, len16, seed, out, bad), out, n, dev)
 
 
 def csum_batch_packed(arena: torch.Tensor, blk_off: torch.Tensor, len16: torch.Tensor,
@@ -229,7 +258,7 @@ def csum_batch_packed(arena: torch.Tensor, blk_off: torch.Tensor, len16: torch.T
                       out: torch.Tensor | None = None, len_hint: int = 0,
                       bad: torch.Tensor | None = None) -> torch.Tensor:
     """Checksum a batch in the packed form (offsets implied by lengths; see PackedBatch)."""
-    _require_cuda(arena, "arena", (torch.uint8,))
+    _require_cuda(arena, "arena", _U8)
     with torch.cuda.device(arena.device):
         return PackedBatch(arena, blk_off, len16, seed, align_log2=align_log2, complement=complement, out=out,
                            len_hint=len_hint, bad=bad)()
@@ -247,13 +276,13 @@ def csum_batch(arena: torch.Tensor, off: torch.Tensor, length: torch.Tensor, see
     lanes_per_packet, unroll, max_blocks) overrides the kernel shape (tuning).
     ``compact=True``: ``off`` holds unsigned 32-bit offsets in an int32 tensor.
     """
-    _require_cuda(arena, "arena", (torch.uint8,))
+    _require_cuda(arena, "arena", _U8)
     with torch.cuda.device(arena.device):
         return PreparedBatch(arena, off, length, seed, complement=complement, out=out, len_hint=len_hint, bad=bad,
                              shape=shape, compact=compact)()
 
 
-class StridedBatch:
+class StridedBatch(_BoundBatch):
     """A device-resident batch of equal-length packets at a fixed stride
     (rns_csum_batch_strided_dev), bound once like PreparedBatch: packet i =
     arena[first_off + i*stride : + length].  No offset or length descriptors travel."""
@@ -261,48 +290,23 @@ class StridedBatch:
     def __init__(self, arena: torch.Tensor, n: int, stride: int, length: int, *, first_off: int = 0,
                  seed: torch.Tensor | None = None, complement: bool = False,
                  out: torch.Tensor | None = None, bad: torch.Tensor | None = None):
-        _require_cuda(arena, "arena", (torch.uint8,))
-        dev = arena.device
+        dev = _descriptors(arena)
         if n < 0 or n >= 2 ** 32 or stride < 0 or not 0 <= length < 2 ** 32 or first_off < 0:
             raise ValueError("n, stride, length and first_off must be non-negative (n, length < 2^32)")
-        seed_ptr = None
-        if seed is not None:
-            _require_cuda(seed, "seed", _U16)
-            if seed.numel() != n or seed.device != dev:
-                raise ValueError("seed must have one entry per packet on the arena's device")
-            seed_ptr = seed.data_ptr()
-        if out is None:
-            out = torch.empty(n, dtype=torch.uint16, device=dev)
-        else:
-            _require_cuda(out, "out", _U16)
-            if out.numel() != n or out.device != dev:
-                raise ValueError("out must have one entry per packet on the arena's device")
-        bad_ptr = _bad_ptr(bad, arena.device)
-        lib = _lib.load()
-        self._keep = (arena, seed, out, bad)
-        self.out, self.n, self.device = out, int(n), dev
-        self._fn = lib.rns_csum_batch_strided_dev
-        self._args = (arena.data_ptr(), arena.numel(), int(first_off), int(stride), int(length), seed_ptr,
-                      out.data_ptr(), int(n), _lib.RNS_FLAG_COMPLEMENT if complement else 0, bad_ptr,
-                      _stream_handle(dev))
-
-    def __call__(self) -> torch.Tensor:
-        if self.n:
-            if torch.cuda.current_device() != self.device.index:
-                with torch.cuda.device(self.device):
-                    st = self._fn(*self._args)
-            else:
-                st = self._fn(*self._args)
-            if st != _lib.RNS_OK:
-                raise _lib.ChecksumError(st, "rns_csum_batch_strided_dev")
-        return self.out
+        n = int(n)
+        seed_ptr = _per_packet(seed, "seed", n, dev)
+        out = _out(out, n, dev)
+        self._bind("rns_csum_batch_strided_dev",
+                   (arena.data_ptr(), arena.numel(), int(first_off), int(stride), int(length), seed_ptr,
+                    out.data_ptr(), n, _flags(complement), _bad_ptr(bad, dev)),
+                   (arena, seed, out, bad), out, n, dev)
 
 
 def csum_batch_strided(arena: torch.Tensor, n: int, stride: int, length: int, *, first_off: int = 0,
                        seed: torch.Tensor | None = None, complement: bool = False,
                        out: torch.Tensor | None = None, bad: torch.Tensor | None = None) -> torch.Tensor:
     """Packets at a fixed stride: packet i = arena[first_off + i*stride : + length]."""
-    _require_cuda(arena, "arena", (torch.uint8,))
+    _require_cuda(arena, "arena", _U8)
     with torch.cuda.device(arena.device):
         return StridedBatch(arena, n, stride, length, first_off=first_off, seed=seed, complement=complement,
                             out=out, bad=bad)()
@@ -321,37 +325,22 @@ def csum_chain(arena: torch.Tensor, frag_off: torch.Tensor, frag_len: torch.Tens
     views of one buffer (same results either way).  ``tx_packed``: RNS_FLAG_CHAIN_TX_PACKED
     (see csum_chain_fill).
     """
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(frag_off, "frag_off", (torch.int64,))
-    _require_cuda(frag_len, "frag_len", (torch.int32,))
-    _require_cuda(first, "first", (torch.int32,))
-    nf = frag_off.numel()
-    n = first.numel() - 1
-    if frag_len.numel() != nf or n < 0:
-        raise ValueError("frag_off/frag_len sizes differ or first is empty")
-    if n > _lib.RNS_CHAIN_MAX_PACKETS or nf >= 2 ** 32:
-        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} packets and 2^32-1 fragments per chain call")
-    dev = arena.device
-    seed_ptr = None
-    if seed is not None:
-        _require_cuda(seed, "seed", _U16)
-        if seed.numel() != n:
-            raise ValueError("seed must have one entry per packet")
-        seed_ptr = seed.data_ptr()
-    if out is None:
-        out = torch.empty(max(n, 0), dtype=torch.uint16, device=dev)
-    bad_ptr = _bad_ptr(bad, arena.device)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = lib.rns_csum_chain_dev(arena.data_ptr(), arena.numel(), frag_off.data_ptr(), frag_len.data_ptr(), nf,
-                                    first.data_ptr(), seed_ptr, out.data_ptr(), n,
-                                    (_lib.RNS_FLAG_COMPLEMENT if complement else 0) |
-                                    (_lib.RNS_FLAG_CHAIN_RUNS if runs else 0) |
-                                    (_lib.RNS_FLAG_CHAIN_TX_PACKED if tx_packed else 0), frag_len_hint,
-                                    frag_sums.data_ptr() if frag_sums is not None else None, bad_ptr,
-                                    _stream_handle(dev))
-    _lib.check(st, "rns_csum_chain_dev")
+    n, nf, dev = _chain(arena, frag_off, frag_len, first)
+    seed_ptr = _per_packet(seed, "seed", n, dev)
+    out = _out(out, n, dev)
+    _call("rns_csum_chain_dev", dev, arena.data_ptr(), arena.numel(), frag_off.data_ptr(), frag_len.data_ptr(), nf,
+          first.data_ptr(), seed_ptr, out.data_ptr(), n, _flags(complement, runs, tx_packed), int(frag_len_hint),
+          frag_sums.data_ptr() if frag_sums is not None else None, _bad_ptr(bad, dev))
     return out
+
+
+def _fill_ptrs(seed, field, field_off, out, n: int, dev: torch.device, max_field_off: int | None = None):
+    """The fills' optional per-packet tensors: (seed, field, out) pointers; ``max_field_off``
+    bounds a ``field_off`` that applies to every packet."""
+    ptrs = tuple(_per_packet(t, name, n, dev) for name, t in (("seed", seed), ("field", field), ("out", out)))
+    if max_field_off is not None and field is None and not 0 <= int(field_off) <= max_field_off:
+        raise ValueError(f"field_off must be in 0..{max_field_off}")
+    return ptrs
 
 
 def csum_chain_fill(arena: torch.Tensor, frag_off: torch.Tensor, frag_len: torch.Tensor, first: torch.Tensor,
@@ -366,40 +355,11 @@ def csum_chain_fill(arena: torch.Tensor, frag_off: torch.Tensor, frag_len: torch
     ``tx_packed``: RNS_FLAG_CHAIN_TX_PACKED, the hint that packets are [head <= 4 chunks,
     payload run] with the payloads packed at 16-byte starts (same results either way).
     Returns ``out`` if given."""
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(frag_off, "frag_off", (torch.int64,))
-    _require_cuda(frag_len, "frag_len", (torch.int32,))
-    _require_cuda(first, "first", (torch.int32,))
-    nf = frag_off.numel()
-    n = first.numel() - 1
-    if frag_len.numel() != nf or n < 0:
-        raise ValueError("frag_off/frag_len sizes differ or first is empty")
-    if n > _lib.RNS_CHAIN_MAX_PACKETS or nf >= 2 ** 32:
-        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} packets and 2^32-1 fragments per chain call")
-    dev = arena.device
-    for name, t in (("frag_off", frag_off), ("frag_len", frag_len), ("first", first)):
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, arena on {dev}")
-    ptrs = []
-    for name, t in (("seed", seed), ("field", field), ("out", out)):
-        if t is None:
-            ptrs.append(None)
-            continue
-        _require_cuda(t, name, _U16)
-        if t.numel() != n or t.device != dev:
-            raise ValueError(f"{name} must have one entry per packet on the arena's device")
-        ptrs.append(t.data_ptr())
-    if field is None and not 0 <= int(field_off) < 2 ** 32:
-        raise ValueError("field_off must be a u32")
-    bad_ptr = _bad_ptr(bad, arena.device)
-    flags = (_lib.RNS_FLAG_COMPLEMENT if complement else 0) | (_lib.RNS_FLAG_CHAIN_RUNS if runs else 0) | \
-        (_lib.RNS_FLAG_CHAIN_TX_PACKED if tx_packed else 0)
-    with torch.cuda.device(dev):
-        st = _lib.load().rns_csum_chain_fill_dev(arena.data_ptr(), arena.numel(), frag_off.data_ptr(),
-                                                 frag_len.data_ptr(), nf, first.data_ptr(), ptrs[0], ptrs[1],
-                                                 int(field_off), ptrs[2], n, flags, int(frag_len_hint), bad_ptr,
-                                                 _stream_handle(dev))
-    _lib.check(st, "rns_csum_chain_fill_dev")
+    n, nf, dev = _chain(arena, frag_off, frag_len, first)
+    seed_ptr, field_ptr, out_ptr = _fill_ptrs(seed, field, field_off, out, n, dev, max_field_off=2 ** 32 - 1)
+    _call("rns_csum_chain_fill_dev", dev, arena.data_ptr(), arena.numel(), frag_off.data_ptr(), frag_len.data_ptr(),
+          nf, first.data_ptr(), seed_ptr, field_ptr, int(field_off), out_ptr, n, _flags(complement, runs, tx_packed),
+          int(frag_len_hint), _bad_ptr(bad, dev))
     return out
 
 
@@ -412,29 +372,10 @@ def csum_fill(arena: torch.Tensor, off: torch.Tensor, length: torch.Tensor, seed
     ``field`` (int16/uint16 [n]) gives per-packet field offsets, else ``field_off``
     for all (TCP 16, UDP 6, ICMP 2, IPv4 header 10).  Returns ``out`` if given.
     """
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(off, "off", (torch.int64,))
-    _require_cuda(length, "length", (torch.int32,))
-    n = off.numel()
-    if length.numel() != n:
-        raise ValueError("off and length must have the same number of packets")
-    dev = arena.device
-    ptrs = []
-    for name, t in (("seed", seed), ("field", field), ("out", out)):
-        if t is None:
-            ptrs.append(None)
-            continue
-        _require_cuda(t, name, _U16)
-        if t.numel() != n or t.device != dev:
-            raise ValueError(f"{name} must have one entry per packet on the arena's device")
-        ptrs.append(t.data_ptr())
-    bad_ptr = _bad_ptr(bad, arena.device)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = lib.rns_csum_fill_dev(arena.data_ptr(), arena.numel(), off.data_ptr(), length.data_ptr(), ptrs[0],
-                                   ptrs[1], int(field_off), ptrs[2], n,
-                                   _lib.RNS_FLAG_COMPLEMENT if complement else 0, bad_ptr, _stream_handle(dev))
-    _lib.check(st, "rns_csum_fill_dev")
+    n, dev = _explicit(arena, off, length)
+    seed_ptr, field_ptr, out_ptr = _fill_ptrs(seed, field, field_off, out, n, dev)
+    _call("rns_csum_fill_dev", dev, arena.data_ptr(), arena.numel(), off.data_ptr(), length.data_ptr(), seed_ptr,
+          field_ptr, int(field_off), out_ptr, n, _flags(complement), _bad_ptr(bad, dev))
     return out
 
 
@@ -444,39 +385,13 @@ def csum_fill_packed(arena: torch.Tensor, blk_off: torch.Tensor, len16: torch.Te
                      len_hint: int = 0, bad: torch.Tensor | None = None) -> torch.Tensor | None:
     """Transmit in-place fill of a packed arena (rns_csum_fill_packed_dev): ``csum_fill``'s
     result and stores, with the packed form's descriptors (see PackedBatch; align_log2 >= 4)."""
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(blk_off, "blk_off", (torch.int64,))
-    _require_cuda(len16, "len16", _U16)
-    n = len16.numel()
-    if blk_off.numel() != (n + 63) // 64:
-        raise ValueError("blk_off must have one entry per 64 packets")
-    if not 4 <= align_log2 <= 12:
-        raise ValueError("the packed fill needs align_log2 in 4..12")
-    if field is None and not 0 <= int(field_off) <= 0xFFFD:
-        # packed lengths are u16: no packet can hold a field past byte 65533 (the C ABI itself
-        # rejects every packet of such a call and leaves the arena unchanged)
-        raise ValueError("field_off must be in 0..65533 for the packed form")
-    dev = arena.device
-    ptrs = []
-    for name, t in (("blk_off", blk_off), ("len16", len16)):
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, arena on {dev}")
-    for name, t in (("seed", seed), ("field", field), ("out", out)):
-        if t is None:
-            ptrs.append(None)
-            continue
-        _require_cuda(t, name, _U16)
-        if t.numel() != n or t.device != dev:
-            raise ValueError(f"{name} must have one entry per packet on the arena's device")
-        ptrs.append(t.data_ptr())
-    bad_ptr = _bad_ptr(bad, arena.device)
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        st = lib.rns_csum_fill_packed_dev(arena.data_ptr(), arena.numel(), blk_off.data_ptr(), len16.data_ptr(),
-                                          int(align_log2), ptrs[0], ptrs[1], int(field_off), ptrs[2], n,
-                                          _lib.RNS_FLAG_COMPLEMENT if complement else 0, int(len_hint), bad_ptr,
-                                          _stream_handle(dev))
-    _lib.check(st, "rns_csum_fill_packed_dev")
+    n, dev = _packed(arena, blk_off, len16, align_log2, (4, 12), exact=True)
+    # packed lengths are u16: no packet can hold a field past byte 65533 (the C ABI itself
+    # rejects every packet of such a call and leaves the arena unchanged)
+    seed_ptr, field_ptr, out_ptr = _fill_ptrs(seed, field, field_off, out, n, dev, max_field_off=0xFFFD)
+    _call("rns_csum_fill_packed_dev", dev, arena.data_ptr(), arena.numel(), blk_off.data_ptr(), len16.data_ptr(),
+          int(align_log2), seed_ptr, field_ptr, int(field_off), out_ptr, n, _flags(complement), int(len_hint),
+          _bad_ptr(bad, dev))
     return out
 
 
@@ -484,22 +399,11 @@ def rx_verify(arena: torch.Tensor, off: torch.Tensor, length: torch.Tensor, loca
               *, status: torch.Tensor | None = None, l4_sum: torch.Tensor | None = None) -> torch.Tensor:
     """Receive verify of a batch of IP datagrams (rns_rx_verify_dev): returns a uint8
     status per packet (RNS_RX_* bits; RNS_RX_ACCEPT = the stack would deliver it)."""
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(off, "off", (torch.int64,))
-    _require_cuda(length, "length", (torch.int32,))
-    if len(local_ipv4) != 4 or len(local_ipv6) != 16:
-        raise ValueError("local_ipv4 must be 4 bytes and local_ipv6 16 bytes")
-    n = off.numel()
-    if length.numel() != n:
-        raise ValueError("off and length must have the same number of datagrams")
-    dev = arena.device
-    lib = _lib.load()
-    status, l4_ptr = _rx_outputs(dev, n, status, l4_sum, (("off", off), ("length", length)))
-    with torch.cuda.device(dev):
-        st = lib.rns_rx_verify_dev(arena.data_ptr(), arena.numel(), off.data_ptr(), length.data_ptr(), n,
-                                   bytes(local_ipv4), bytes(local_ipv6), status.data_ptr(), l4_ptr,
-                                   _stream_handle(dev))
-    _lib.check(st, "rns_rx_verify_dev")
+    n, dev = _explicit(arena, off, length)
+    ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
+    status = _status(status, n, dev)
+    _call("rns_rx_verify_dev", dev, arena.data_ptr(), arena.numel(), off.data_ptr(), length.data_ptr(), n, ip4, ip6,
+          status.data_ptr(), _per_packet(l4_sum, "l4_sum", n, dev))
     return status
 
 
@@ -512,27 +416,11 @@ def rx_verify_chain(arena: torch.Tensor, frag_off: torch.Tensor, frag_len: torch
     first fragment, trim_head, the L4 sum folded fragment by fragment).  Nothing is written to
     the arena.  Returns ``(status, l4_sum)``: uint8 RNS_RX_* bits per datagram, and the
     ``l4_sum`` tensor passed in (complemented L4 sums) or None."""
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(frag_off, "frag_off", (torch.int64,))
-    _require_cuda(frag_len, "frag_len", (torch.int32,))
-    _require_cuda(first, "first", (torch.int32,))
-    if len(local_ipv4) != 4 or len(local_ipv6) != 16:
-        raise ValueError("local_ipv4 must be 4 bytes and local_ipv6 16 bytes")
-    nf = frag_off.numel()
-    n = first.numel() - 1
-    if frag_len.numel() != nf or n < 0:
-        raise ValueError("frag_off/frag_len sizes differ or first is empty")
-    if n > _lib.RNS_CHAIN_MAX_PACKETS or nf >= 2 ** 32:
-        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} packets and 2^32-1 fragments per chain call")
-    dev = arena.device
-    lib = _lib.load()
-    status, l4_ptr = _rx_outputs(dev, n, status, l4_sum,
-                                 (("frag_off", frag_off), ("frag_len", frag_len), ("first", first)))
-    with torch.cuda.device(dev):
-        st = lib.rns_rx_verify_chain_dev(arena.data_ptr(), arena.numel(), frag_off.data_ptr(), frag_len.data_ptr(),
-                                         nf, first.data_ptr(), n, bytes(local_ipv4), bytes(local_ipv6),
-                                         status.data_ptr(), l4_ptr, _stream_handle(dev))
-    _lib.check(st, "rns_rx_verify_chain_dev")
+    n, nf, dev = _chain(arena, frag_off, frag_len, first)
+    ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
+    status = _status(status, n, dev)
+    _call("rns_rx_verify_chain_dev", dev, arena.data_ptr(), arena.numel(), frag_off.data_ptr(), frag_len.data_ptr(),
+          nf, first.data_ptr(), n, ip4, ip6, status.data_ptr(), _per_packet(l4_sum, "l4_sum", n, dev))
     return status, l4_sum
 
 
@@ -542,22 +430,11 @@ def rx_verify_packed(arena: torch.Tensor, blk_off: torch.Tensor, len16: torch.Te
     """Receive verify of a PACKED arena of datagrams (rns_rx_verify_packed_dev: u16 lengths,
     one offset per 64 datagrams, 16-byte-aligned starts): the same uint8 status per datagram
     as rx_verify."""
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(blk_off, "blk_off", (torch.int64,))
-    _require_cuda(len16, "len16", _U16)
-    if len(local_ipv4) != 4 or len(local_ipv6) != 16:
-        raise ValueError("local_ipv4 must be 4 bytes and local_ipv6 16 bytes")
-    n = len16.numel()
-    if blk_off.numel() < (n + 63) // 64:
-        raise ValueError("blk_off needs one offset per 64 datagrams")
-    dev = arena.device
-    lib = _lib.load()
-    status, l4_ptr = _rx_outputs(dev, n, status, l4_sum, (("blk_off", blk_off), ("len16", len16)))
-    with torch.cuda.device(dev):
-        st = lib.rns_rx_verify_packed_dev(arena.data_ptr(), arena.numel(), blk_off.data_ptr(), len16.data_ptr(),
-                                          int(align_log2), n, bytes(local_ipv4), bytes(local_ipv6),
-                                          status.data_ptr(), l4_ptr, _stream_handle(dev))
-    _lib.check(st, "rns_rx_verify_packed_dev")
+    n, dev = _packed(arena, blk_off, len16, align_log2, None)  # align_log2 (4..12): the C ABI's check
+    ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
+    status = _status(status, n, dev)
+    _call("rns_rx_verify_packed_dev", dev, arena.data_ptr(), arena.numel(), blk_off.data_ptr(), len16.data_ptr(),
+          int(align_log2), n, ip4, ip6, status.data_ptr(), _per_packet(l4_sum, "l4_sum", n, dev))
     return status
 
 
@@ -567,23 +444,16 @@ def rx_verify_strided(arena: torch.Tensor, stride: int, len16: torch.Tensor, loc
     """Receive verify of datagrams at a fixed stride (rns_rx_verify_strided_dev): datagram i
     = ``arena[first_off + i*stride : + len16[i]]``, a ring of fixed-size receive slots.  The
     same uint8 status per datagram as rx_verify."""
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(len16, "len16", _U16)
-    if len(local_ipv4) != 4 or len(local_ipv6) != 16:
-        raise ValueError("local_ipv4 must be 4 bytes and local_ipv6 16 bytes")
+    dev = _descriptors(arena, ("len16", len16, _U16))
+    ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
     if not (0 <= int(first_off) < 2 ** 64 and 0 <= int(stride) < 2 ** 64):
         raise ValueError("first_off and stride must be u64")
     n = len16.numel()
     if n >= 2 ** 32:
         raise ValueError("at most 2^32-1 datagrams per call")
-    dev = arena.device
-    lib = _lib.load()
-    status, l4_ptr = _rx_outputs(dev, n, status, l4_sum, (("len16", len16),))
-    with torch.cuda.device(dev):
-        st = lib.rns_rx_verify_strided_dev(arena.data_ptr(), arena.numel(), int(first_off), int(stride),
-                                           len16.data_ptr(), n, bytes(local_ipv4), bytes(local_ipv6),
-                                           status.data_ptr(), l4_ptr, _stream_handle(dev))
-    _lib.check(st, "rns_rx_verify_strided_dev")
+    status = _status(status, n, dev)
+    _call("rns_rx_verify_strided_dev", dev, arena.data_ptr(), arena.numel(), int(first_off), int(stride),
+          len16.data_ptr(), n, ip4, ip6, status.data_ptr(), _per_packet(l4_sum, "l4_sum", n, dev))
     return status
 
 
@@ -592,31 +462,10 @@ def tx_fill_packed(arena: torch.Tensor, blk_off: torch.Tensor, len16: torch.Tens
     """Transmit finalize of a PACKED arena of outgoing datagrams (rns_tx_fill_packed_dev: u16
     lengths, one offset per 64 datagrams, starts at 2^align_log2 boundaries, align_log2 >= 4):
     the bytes and the uint8 status per datagram of ``tx_fill``."""
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(blk_off, "blk_off", (torch.int64,))
-    _require_cuda(len16, "len16", _U16)
-    n = len16.numel()
-    if blk_off.numel() < (n + 63) // 64:
-        raise ValueError("blk_off needs one offset per 64 datagrams")
-    if not 4 <= align_log2 <= 12:
-        raise ValueError("the packed transmit finalize needs align_log2 in 4..12")
-    if n >= 2 ** 32:
-        raise ValueError("at most 2^32-1 datagrams per call")
-    dev = arena.device
-    for name, t in (("blk_off", blk_off), ("len16", len16)):
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, arena on {dev}")
-    if status is None:
-        status = torch.empty(n, dtype=torch.uint8, device=dev)
-    else:
-        _require_cuda(status, "status", (torch.uint8,))
-        if status.numel() != n or status.device != dev:
-            raise ValueError(f"status must be {n} uint8 entries on {dev}")
-    with torch.cuda.device(dev):
-        st = _lib.load().rns_tx_fill_packed_dev(arena.data_ptr(), arena.numel(), blk_off.data_ptr(),
-                                               len16.data_ptr(), int(align_log2), n, status.data_ptr(),
-                                               int(len_hint), _stream_handle(dev))
-    _lib.check(st, "rns_tx_fill_packed_dev")
+    n, dev = _packed(arena, blk_off, len16, align_log2, (4, 12))
+    status = _status(status, n, dev)
+    _call("rns_tx_fill_packed_dev", dev, arena.data_ptr(), arena.numel(), blk_off.data_ptr(), len16.data_ptr(),
+          int(align_log2), n, status.data_ptr(), int(len_hint))
     return status
 
 
@@ -628,31 +477,10 @@ def tx_fill_chain(arena: torch.Tensor, frag_off: torch.Tensor, frag_len: torch.T
     the rest its payload.  The L4 checksum over [head[hdr:], payload...] (folded per fragment,
     tcp.rs:957-973, udp.rs:151-171, icmp.rs:87-112) and the IPv4 header checksum
     (ip.rs:140-160) are stored into the head.  Returns a uint8 status per datagram (RNS_TX_*)."""
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(frag_off, "frag_off", (torch.int64,))
-    _require_cuda(frag_len, "frag_len", (torch.int32,))
-    _require_cuda(first, "first", (torch.int32,))
-    nf = frag_off.numel()
-    n = first.numel() - 1
-    if frag_len.numel() != nf or n < 0:
-        raise ValueError("frag_off/frag_len sizes differ or first is empty")
-    if n > _lib.RNS_CHAIN_MAX_PACKETS or nf >= 2 ** 32:
-        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} datagrams and 2^32-1 fragments per chain call")
-    dev = arena.device
-    for name, t in (("frag_off", frag_off), ("frag_len", frag_len), ("first", first)):
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, arena on {dev}")
-    if status is None:
-        status = torch.empty(n, dtype=torch.uint8, device=dev)
-    else:
-        _require_cuda(status, "status", (torch.uint8,))
-        if status.numel() != n or status.device != dev:
-            raise ValueError(f"status must be {n} uint8 entries on {dev}")
-    with torch.cuda.device(dev):
-        st = _lib.load().rns_tx_fill_chain_dev(arena.data_ptr(), arena.numel(), frag_off.data_ptr(),
-                                              frag_len.data_ptr(), nf, first.data_ptr(), n, status.data_ptr(),
-                                              _stream_handle(dev))
-    _lib.check(st, "rns_tx_fill_chain_dev")
+    n, nf, dev = _chain(arena, frag_off, frag_len, first)
+    status = _status(status, n, dev)
+    _call("rns_tx_fill_chain_dev", dev, arena.data_ptr(), arena.numel(), frag_off.data_ptr(), frag_len.data_ptr(), nf,
+          first.data_ptr(), n, status.data_ptr())
     return status
 
 
@@ -695,11 +523,8 @@ def tx_fill_chain_packed(arena: torch.Tensor, head_blk_off: torch.Tensor, head_l
     head offset and one payload offset per 64 datagrams (see ``tx_chain_packed_layout``) — 3 B per
     datagram + 16 B per 64 instead of the CSR form's 28 B.  The bytes and the uint8 status per
     datagram of ``tx_fill_chain`` on the chains the lengths imply."""
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(head_blk_off, "head_blk_off", (torch.int64,))
-    _require_cuda(head_len8, "head_len8", (torch.uint8,))
-    _require_cuda(pay_blk_off, "pay_blk_off", (torch.int64,))
-    _require_cuda(pay_len16, "pay_len16", _U16)
+    dev = _descriptors(arena, ("head_blk_off", head_blk_off, _I64), ("head_len8", head_len8, _U8),
+                       ("pay_blk_off", pay_blk_off, _I64), ("pay_len16", pay_len16, _U16))
     n = head_len8.numel()
     if pay_len16.numel() != n:
         raise ValueError("head_len8 and pay_len16 must have one entry per datagram each")
@@ -709,23 +534,10 @@ def tx_fill_chain_packed(arena: torch.Tensor, head_blk_off: torch.Tensor, head_l
         raise ValueError("the compact chain finalize needs pay_align_log2 in 4..12")
     if n > _lib.RNS_CHAIN_MAX_PACKETS:
         raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} datagrams per chain call")
-    dev = arena.device
-    for name, t in (("head_blk_off", head_blk_off), ("head_len8", head_len8), ("pay_blk_off", pay_blk_off),
-                    ("pay_len16", pay_len16)):
-        if t.device != dev:
-            raise ValueError(f"{name} is on {t.device}, arena on {dev}")
-    if status is None:
-        status = torch.empty(n, dtype=torch.uint8, device=dev)
-    else:
-        _require_cuda(status, "status", (torch.uint8,))
-        if status.numel() != n or status.device != dev:
-            raise ValueError(f"status must be {n} uint8 entries on {dev}")
-    with torch.cuda.device(dev):
-        st = _lib.load().rns_tx_fill_chain_packed_dev(arena.data_ptr(), arena.numel(), head_blk_off.data_ptr(),
-                                                     head_len8.data_ptr(), pay_blk_off.data_ptr(),
-                                                     pay_len16.data_ptr(), int(pay_align_log2), n,
-                                                     status.data_ptr(), _stream_handle(dev))
-    _lib.check(st, "rns_tx_fill_chain_packed_dev")
+    status = _status(status, n, dev)
+    _call("rns_tx_fill_chain_packed_dev", dev, arena.data_ptr(), arena.numel(), head_blk_off.data_ptr(),
+          head_len8.data_ptr(), pay_blk_off.data_ptr(), pay_len16.data_ptr(), int(pay_align_log2), n,
+          status.data_ptr())
     return status
 
 
@@ -735,35 +547,18 @@ def tx_fill(arena: torch.Tensor, off: torch.Tensor, length: torch.Tensor, *,
     IPv4 header checksum and the TCP / UDP / ICMP checksum of every datagram stored in
     place, pseudo-headers formed on the device (tcp.rs:957-973, udp.rs:151-171,
     icmp.rs:87-112, ip.rs:140-160).  Returns a uint8 status per datagram (RNS_TX_*)."""
-    _require_cuda(arena, "arena", (torch.uint8,))
-    _require_cuda(off, "off", (torch.int64,))
-    _require_cuda(length, "length", (torch.int32,))
-    n = off.numel()
-    if length.numel() != n:
-        raise ValueError("off and length must have the same number of datagrams")
-    dev = arena.device
-    if status is None:
-        status = torch.empty(n, dtype=torch.uint8, device=dev)
-    else:
-        _require_cuda(status, "status", (torch.uint8,))
-        if status.numel() != n:
-            raise ValueError("status must have one entry per datagram")
-    with torch.cuda.device(dev):
-        st = _lib.load().rns_tx_fill_dev(arena.data_ptr(), arena.numel(), off.data_ptr(), length.data_ptr(), n,
-                                        status.data_ptr(), _stream_handle(dev))
-    _lib.check(st, "rns_tx_fill_dev")
+    n, dev = _explicit(arena, off, length)
+    status = _status(status, n, dev)
+    _call("rns_tx_fill_dev", dev, arena.data_ptr(), arena.numel(), off.data_ptr(), length.data_ptr(), n,
+          status.data_ptr())
     return status
 
 
 def fill_splitmix64(buf: torch.Tensor, seed: int) -> torch.Tensor:
     """Fill a device uint8 buffer with the splitmix64 byte stream (same bytes as
     oracle.splitmix64_bytes(seed, n))."""
-    _require_cuda(buf, "buf", (torch.uint8,))
-    lib = _lib.load()
-    with torch.cuda.device(buf.device):
-        st = lib.rns_fill_splitmix64_dev(buf.data_ptr(), buf.numel(), seed & 0xFFFFFFFFFFFFFFFF,
-                                         _stream_handle(buf.device))
-    _lib.check(st, "rns_fill_splitmix64_dev")
+    _require_cuda(buf, "buf", _U8)
+    _call("rns_fill_splitmix64_dev", buf.device, buf.data_ptr(), buf.numel(), seed & 0xFFFFFFFFFFFFFFFF)
     return buf
 
 
@@ -912,6 +707,8 @@ class HostBatcher:
     """Host-resident batches: chunked H2D, kernel, D2H of results overlapped on
     ``nstreams`` streams (rns_csum_batch_host).  Offsets must be ascending."""
 
+    _run, _destroy = "rns_csum_batch_host", "rns_host_ctx_destroy"
+
     def __init__(self, device: int = 0, chunk_bytes: int = 64 << 20, nstreams: int = 3):
         lib = _lib.load()
         ctx = ctypes.c_void_p()
@@ -930,15 +727,14 @@ class HostBatcher:
         if seed is not None:
             seed = np.ascontiguousarray(seed, dtype=np.uint16)
             sp = seed.ctypes.data
-        st = _lib.load().rns_csum_batch_host(self.ctx, arena.ctypes.data, arena.shape[0], off.ctypes.data,
-                                             length.ctypes.data, sp, out.ctypes.data, n,
-                                             _lib.RNS_FLAG_COMPLEMENT if complement else 0)
-        _lib.check(st, "rns_csum_batch_host")
+        st = getattr(_lib.load(), self._run)(self.ctx, arena.ctypes.data, arena.shape[0], off.ctypes.data,
+                                             length.ctypes.data, sp, out.ctypes.data, n, _flags(complement))
+        _lib.check(st, self._run)
         return out
 
     def close(self) -> None:
         if self.ctx:
-            _lib.load().rns_host_ctx_destroy(self.ctx)
+            getattr(_lib.load(), self._destroy)(self.ctx)
             self.ctx = None
 
     def __del__(self):
@@ -953,6 +749,8 @@ class MultiHostBatcher(HostBatcher):
     batch is cut into contiguous packet ranges of about equal bytes, one per entry
     of ``devices`` (a device may repeat), each through its own staging context."""
 
+    _run, _destroy = "rns_csum_batch_multi_host", "rns_multi_ctx_destroy"
+
     def __init__(self, devices, chunk_bytes: int = 64 << 20, nstreams: int = 3):
         lib = _lib.load()
         devs = (ctypes.c_int * len(devices))(*devices)
@@ -961,29 +759,6 @@ class MultiHostBatcher(HostBatcher):
                    "rns_multi_ctx_create")
         self.ctx = ctx.value
         self.devices = list(devices)
-
-    def run(self, arena: np.ndarray, off: np.ndarray, length: np.ndarray, seed: np.ndarray | None = None,
-            complement: bool = False, out: np.ndarray | None = None) -> np.ndarray:
-        arena = np.ascontiguousarray(arena, dtype=np.uint8)
-        off = np.ascontiguousarray(off, dtype=np.uint64)
-        length = np.ascontiguousarray(length, dtype=np.uint32)
-        n = off.shape[0]
-        if out is None:
-            out = np.empty(n, dtype=np.uint16)
-        sp = None
-        if seed is not None:
-            seed = np.ascontiguousarray(seed, dtype=np.uint16)
-            sp = seed.ctypes.data
-        st = _lib.load().rns_csum_batch_multi_host(self.ctx, arena.ctypes.data, arena.shape[0], off.ctypes.data,
-                                                   length.ctypes.data, sp, out.ctypes.data, n,
-                                                   _lib.RNS_FLAG_COMPLEMENT if complement else 0)
-        _lib.check(st, "rns_csum_batch_multi_host")
-        return out
-
-    def close(self) -> None:
-        if self.ctx:
-            _lib.load().rns_multi_ctx_destroy(self.ctx)
-            self.ctx = None
 
 
 def csum_batch_multi_dev(shards, *, complement: bool = False) -> None:

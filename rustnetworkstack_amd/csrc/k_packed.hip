@@ -4,16 +4,35 @@
 #ifndef RNS_ROWS_DEEP_FROM  // typical lengths from this take D = 16 rows in flight at 4 waves/SIMD
 #define RNS_ROWS_DEEP_FROM 1024u
 #endif
+#ifndef RNS_TX_ROWS_DEEP_FROM  // typical lengths from this take D = 16 rows at 4 waves/SIMD
+#define RNS_TX_ROWS_DEEP_FROM 1024u
+#endif
+#ifndef RNS_RX_ROWS_D  // rows in flight of the receive form
+#define RNS_RX_ROWS_D 8
+#endif
 
 namespace rns {
+
+constexpr bool kStreamNT = RNS_STREAM_NT != 0;
+
+// The rows kernels' launch, one wave per 64 packets: D = 16 rows in flight for typical lengths
+// from `deep_from`, else 8, on the buffer path where the arena allows it.  `kernel(D, buf)`
+// names the instantiation.
+template <class Kernel>
+static int launch_rows(const CsumArgs &a, uint32_t deep_from, hipStream_t st, Kernel kernel)
+{
+    return with_flags(
+        [&](auto deep, auto buf) {
+            return launch(kernel(std::integral_constant<int, deep() ? 16 : 8>{}, buf), dim3(waves64(a.n)), dim3(64), 0,
+                          st, a);
+        },
+        a.len_hint >= deep_from, buf_ok(a));
+}
 
 // The packed form's kernels (separate instantiations, so the explicit-descriptor
 // kernels carry no packed-form code): the mixed kernel, or for tiny packets the
 // rounds kernel with pick_shape's G=4, U=1 shape.
 // Receive verify's stream launch: one wave per 64-datagram unit.
-#ifndef RNS_RX_ROWS_D  // rows in flight of the receive form
-#define RNS_RX_ROWS_D 8
-#endif
 // Packed receive verify: the rows receive kernel (round 5: IMIX 468.1 -> 449.2-450.3 us, c3
 // 230.4 -> 225.0-226.2 per step against the stream kernel), except for arenas of ACK-sized
 // datagrams (at most 128 arena bytes per datagram), where the stream kernel's ACK path measured
@@ -21,23 +40,19 @@ namespace rns {
 // its own, 1 or 2 units per wave at 6-8 waves/SIMD: 15.2-19.5 against 14.7-14.9, r05n).
 int launch_stream_rx(const CsumArgs &a, hipStream_t st)
 {
-    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(a.n) + 63) / 64)), block(64);
-    constexpr bool NT = RNS_STREAM_NT != 0;
-    const bool ack = a.arena_bytes / a.n <= 128, buf = buf_records(a) < kOobOffset;
-    if (ack && buf)
-        hipLaunchKernelGGL((csum_stream_kernel<NT, true>), grid, block, 0, st, a);
-    else if (ack)
-        hipLaunchKernelGGL((csum_stream_kernel<NT, false>), grid, block, 0, st, a);
-    else if (buf)
-        hipLaunchKernelGGL((csum_rows_rx_kernel<NT, true, RNS_RX_ROWS_D>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((csum_rows_rx_kernel<NT, false, RNS_RX_ROWS_D>), grid, block, 0, st, a);
-    return hip_status(hipGetLastError());
+    return with_flags(
+        [&](auto ack, auto buf) {
+            if constexpr (ack())
+                return launch(csum_stream_kernel<kStreamNT, buf()>, dim3(waves64(a.n)), dim3(64), 0, st, a);
+            else
+                return launch(csum_rows_rx_kernel<kStreamNT, buf(), RNS_RX_ROWS_D>, dim3(waves64(a.n)), dim3(64), 0, st,
+                              a);
+        },
+        a.arena_bytes / a.n <= 128, buf_ok(a));
 }
 
 int dispatch_packed(const CsumArgs &a, const Shape &sh, hipStream_t st)
 {
-    const bool nt = (sh.variant & 2u) != 0, buf = buf_records(a) < kOobOffset;
     // 16-byte-aligned packets (align_log2 >= 4) of any typical length above the tiny rounds
     // kernel's, or unknown: the rows kernel.  Measured against the kernels it replaced (session
     // r04d, isolated dispatch): c3 1500 B 231.5 vs 238.5-239.2 us (class kernel), c4 9000 B
@@ -47,53 +62,29 @@ int dispatch_packed(const CsumArgs &a, const Shape &sh, hipStream_t st)
     // (tiny packets through the rows kernel: c2 19.6 vs 13.8 us per isolated dispatch, a 4 KiB unit
     // is all prologue: profiles/r04_unit_size_and_tiny.json)
     const bool tiny = (sh.variant & ~16u) == 3u && sh.G == 4u && sh.U == 1u;
-    if (a.align_mask >= 15u && !tiny) {
-        constexpr bool NT = RNS_STREAM_NT != 0;
-        const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(a.n) + 63) / 64)), block(64);
-        if (a.len_hint >= RNS_ROWS_DEEP_FROM) {
-            if (buf)
-                hipLaunchKernelGGL((csum_rows_kernel<NT, true, 16>), grid, block, 0, st, a);
-            else
-                hipLaunchKernelGGL((csum_rows_kernel<NT, false, 16>), grid, block, 0, st, a);
-        } else {
-            if (buf)
-                hipLaunchKernelGGL((csum_rows_kernel<NT, true, 8>), grid, block, 0, st, a);
-            else
-                hipLaunchKernelGGL((csum_rows_kernel<NT, false, 8>), grid, block, 0, st, a);
-        }
-        return hip_status(hipGetLastError());
-    }
-    const uint64_t batches = (static_cast<uint64_t>(a.n) + 63) / 64;  // one wave per 64 packets
-    const uint64_t wpb = ((sh.variant & 4u) ? kMixedBlock<false> : kBlock) / 64;  // waves per workgroup
+    if (a.align_mask >= 15u && !tiny)
+        return launch_rows(a, RNS_ROWS_DEEP_FROM, st,
+                           [](auto D, auto buf) { return csum_rows_kernel<kStreamNT, buf(), D()>; });
+    const bool mixed = (sh.variant & 4u) != 0;
+    if (!mixed && !tiny)
+        return RNS_E_INVALID;
+    const uint64_t batches = waves64(a.n);  // one wave per 64 packets
+    const uint64_t wpb = (mixed ? kMixedBlock<false> : kBlock) / 64;  // waves per workgroup
     uint64_t blocks = (batches + wpb - 1) / wpb;
     if (sh.max_blocks != 0 && blocks > sh.max_blocks)
         blocks = sh.max_blocks;
-    const dim3 grid(static_cast<uint32_t>(blocks)), block((sh.variant & 4u) ? kMixedBlock<false> : kBlock);
-    if (sh.variant & 4u) {
-        if (nt && buf)
-            hipLaunchKernelGGL((csum_mixed_kernel<false, true, true, false, false, false, true>), grid, block, 0, st, a);
-        else if (nt)
-            hipLaunchKernelGGL((csum_mixed_kernel<false, true, false, false, false, false, true>), grid, block, 0, st, a);
-        else if (buf)
-            hipLaunchKernelGGL((csum_mixed_kernel<false, false, true, false, false, false, true>), grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL((csum_mixed_kernel<false, false, false, false, false, false, true>), grid, block, 0, st,
-                               a);
-    } else if ((sh.variant & ~16u) == 3u && sh.G == 4u && sh.U == 1u) {  // c2: 13.46 -> 13.36 us with prefetch
-        const bool pf = (sh.variant & 16u) != 0;
-        if (buf && pf)
-            hipLaunchKernelGGL((csum_rounds_kernel<4, 1, false, true, true, 1, true, true>), grid, block, 0,
-                               st, a);
-        else if (buf)
-            hipLaunchKernelGGL((csum_rounds_kernel<4, 1, false, true, true, 1, true>), grid, block, 0, st, a);
-        else if (pf)
-            hipLaunchKernelGGL((csum_rounds_kernel<4, 1, false, true, false, 1, true, true>), grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL((csum_rounds_kernel<4, 1, false, true, false, 1, true>), grid, block, 0, st, a);
-    } else {
-        return RNS_E_INVALID;
-    }
-    return hip_status(hipGetLastError());
+    const dim3 grid(static_cast<uint32_t>(blocks)), block(mixed ? kMixedBlock<false> : kBlock);
+    if (mixed)
+        return with_flags(
+            [&](auto nt, auto buf) {
+                return launch(csum_mixed_kernel<false, nt(), buf(), false, false, false, true>, grid, block, 0, st, a);
+            },
+            (sh.variant & 2u) != 0, buf_ok(a));
+    return with_flags(  // c2: 13.46 -> 13.36 us with prefetch
+        [&](auto buf, auto pf) {
+            return launch(csum_rounds_kernel<4, 1, false, true, buf(), 1, true, pf()>, grid, block, 0, st, a);
+        },
+        buf_ok(a), (sh.variant & 16u) != 0);
 }
 
 // Transmit fill of a packed arena (align_log2 >= 4): the rows kernel in fill mode, D by the
@@ -103,45 +94,16 @@ int dispatch_packed(const CsumArgs &a, const Shape &sh, hipStream_t st)
 // 303.8 / 764.2 and 306.7 / 810.9 with nontemporal rows; session r06d.)
 int launch_fill_packed(const CsumArgs &a, hipStream_t st)
 {
-    constexpr bool NT = RNS_STREAM_NT != 0;
-    const bool buf = buf_records(a) < kOobOffset;
-    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(a.n) + 63) / 64)), block(64);
-    if (a.len_hint >= RNS_ROWS_DEEP_FROM) {
-        if (buf)
-            hipLaunchKernelGGL((csum_rows_kernel<NT, true, 16, true>), grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL((csum_rows_kernel<NT, false, 16, true>), grid, block, 0, st, a);
-    } else {
-        if (buf)
-            hipLaunchKernelGGL((csum_rows_kernel<NT, true, 8, true>), grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL((csum_rows_kernel<NT, false, 8, true>), grid, block, 0, st, a);
-    }
-    return hip_status(hipGetLastError());
+    return launch_rows(a, RNS_ROWS_DEEP_FROM, st,
+                       [](auto D, auto buf) { return csum_rows_kernel<kStreamNT, buf(), D(), true>; });
 }
 
 // Transmit finalize of a packed arena (align_log2 >= 4): the rows transmit kernel, D by the
 // typical length as for the plain checksum.
-#ifndef RNS_TX_ROWS_DEEP_FROM  // typical lengths from this take D = 16 rows at 4 waves/SIMD
-#define RNS_TX_ROWS_DEEP_FROM 1024u
-#endif
 int launch_tx_packed(const CsumArgs &a, hipStream_t st)
 {
-    constexpr bool NT = RNS_STREAM_NT != 0;
-    const bool buf = buf_records(a) < kOobOffset;
-    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(a.n) + 63) / 64)), block(64);
-    if (a.len_hint >= RNS_TX_ROWS_DEEP_FROM) {
-        if (buf)
-            hipLaunchKernelGGL((csum_rows_tx_kernel<NT, true, 16>), grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL((csum_rows_tx_kernel<NT, false, 16>), grid, block, 0, st, a);
-    } else {
-        if (buf)
-            hipLaunchKernelGGL((csum_rows_tx_kernel<NT, true, 8>), grid, block, 0, st, a);
-        else
-            hipLaunchKernelGGL((csum_rows_tx_kernel<NT, false, 8>), grid, block, 0, st, a);
-    }
-    return hip_status(hipGetLastError());
+    return launch_rows(a, RNS_TX_ROWS_DEEP_FROM, st,
+                       [](auto D, auto buf) { return csum_rows_tx_kernel<kStreamNT, buf(), D()>; });
 }
 
 // Receive verify of datagrams at a fixed stride: B batches of 64 per one-wave workgroup (one:
@@ -150,12 +112,9 @@ int launch_tx_packed(const CsumArgs &a, hipStream_t st)
 int launch_strided_rx(const CsumArgs &a, hipStream_t st)
 {
     constexpr int B = kStridedRxB;
-    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(a.n) + 64 * B - 1) / (64 * B))), block(64);
-    if (buf_records(a) < kOobOffset)
-        hipLaunchKernelGGL((csum_strided_rx_kernel<true, B>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((csum_strided_rx_kernel<false, B>), grid, block, 0, st, a);
-    return hip_status(hipGetLastError());
+    const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(a.n) + 64 * B - 1) / (64 * B)));
+    return with_flags([&](auto buf) { return launch(csum_strided_rx_kernel<buf(), B>, grid, dim3(64), 0, st, a); },
+                      buf_ok(a));
 }
 
 }  // namespace rns

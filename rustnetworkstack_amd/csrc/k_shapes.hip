@@ -14,7 +14,7 @@ int launch_shape(const CsumArgs &a, uint32_t variant, uint32_t max_blocks, hipSt
         constexpr uint32_t kGroups = kBlock / G;
         blocks = (static_cast<uint64_t>(a.n) + kGroups - 1) / kGroups;
     } else {
-        const uint64_t batches = (static_cast<uint64_t>(a.n) + 63) / 64;  // one wave per 64 packets
+        const uint64_t batches = waves64(a.n);  // one wave per 64 packets
         const uint64_t wpb = ((variant & 4) ? kMixedBlock<false> : kBlock) / 64;  // waves per workgroup
         blocks = (batches + wpb - 1) / wpb;
     }
@@ -24,68 +24,32 @@ int launch_shape(const CsumArgs &a, uint32_t variant, uint32_t max_blocks, hipSt
         return RNS_OK;
     const dim3 grid(static_cast<uint32_t>(blocks)), block((variant & 4) ? kMixedBlock<false> : kBlock);
     const bool nt = (variant & 2) != 0;
-    const bool buf = buf_records(a) < kOobOffset;  // buffer loads need a 32-bit offset range
     // Variant bits 8-11 (tuning): at most that many workgroups per CU, i.e. waves per
     // SIMD for 4-wave workgroups, by reserving LDS (160 KB per CU on gfx950).
     const uint32_t cap = (variant >> 8) & 15u;
     const size_t lds = cap ? ((160u << 10) / cap) - (2u << 10) : 0u;
     variant &= 0xffu;
-    if (variant & 4) {
-        if (nt && buf)
-            hipLaunchKernelGGL((csum_mixed_kernel<S, true, true, false>), grid, block, lds, st, a);
-        else if (nt)
-            hipLaunchKernelGGL((csum_mixed_kernel<S, true, false, false>), grid, block, lds, st, a);
-        else if (buf)
-            hipLaunchKernelGGL((csum_mixed_kernel<S, false, true, false>), grid, block, lds, st, a);
-        else
-            hipLaunchKernelGGL((csum_mixed_kernel<S, false, false, false>), grid, block, lds, st, a);
-    } else if ((variant & 1) == 0) {
-        if constexpr (G >= 4) {
-            if (nt)
-                hipLaunchKernelGGL((csum_batch_kernel<G, U, S, true>), grid, block, lds, st, a);
-            else
-                hipLaunchKernelGGL((csum_batch_kernel<G, U, S, false>), grid, block, lds, st, a);
-        } else {
-            return RNS_E_INVALID;
-        }
-    } else if (variant & 8) {  // rounds kernel, every round in flight (tiny packets)
-        if constexpr (G <= 8 && U <= 2) {
-            if (nt && buf)
-                hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, true, true, G>), grid, block, lds, st, a);
-            else if (nt)
-                hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, true, false, G>), grid, block, lds, st, a);
-            else if (buf)
-                hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, false, true, G>), grid, block, lds, st, a);
-            else
-                hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, false, false, G>), grid, block, lds, st, a);
-        } else {
-            return RNS_E_INVALID;
-        }
-    } else if (variant & 16) {  // rounds kernel, next batch's descriptors prefetched (tiny packets)
-        if constexpr (G <= 8 && U <= 2) {
-            if (nt && buf)
-                hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, true, true, 1, false, true>), grid, block, lds, st, a);
-            else if (nt)
-                hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, true, false, 1, false, true>), grid, block, lds, st, a);
-            else if (buf)
-                hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, false, true, 1, false, true>), grid, block, lds, st, a);
-            else
-                hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, false, false, 1, false, true>), grid, block, lds, st,
-                                   a);
-        } else {
-            return RNS_E_INVALID;
-        }
-    } else {
-        if (nt && buf)
-            hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, true, true>), grid, block, lds, st, a);
-        else if (nt)
-            hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, true, false>), grid, block, lds, st, a);
-        else if (buf)
-            hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, false, true>), grid, block, lds, st, a);
-        else
-            hipLaunchKernelGGL((csum_rounds_kernel<G, U, S, false, false>), grid, block, lds, st, a);
+    if ((variant & 5) == 0) {  // the group kernel: no buffer loads
+        if constexpr (G >= 4)
+            return with_flags([&](auto NT) { return launch(csum_batch_kernel<G, U, S, NT()>, grid, block, lds, st, a); },
+                              nt);
+        return RNS_E_INVALID;
     }
-    return hip_status(hipGetLastError());
+    return with_flags(
+        [&](auto NT, auto BUF) {
+            if (variant & 4)
+                return launch(csum_mixed_kernel<S, NT(), BUF(), false>, grid, block, lds, st, a);
+            if constexpr (G <= 8 && U <= 2) {
+                if (variant & 8)  // rounds kernel, every round in flight (tiny packets)
+                    return launch(csum_rounds_kernel<G, U, S, NT(), BUF(), G>, grid, block, lds, st, a);
+                if (variant & 16)  // rounds kernel, next batch's descriptors prefetched (tiny packets)
+                    return launch(csum_rounds_kernel<G, U, S, NT(), BUF(), 1, false, true>, grid, block, lds, st, a);
+            } else if (variant & 24) {
+                return static_cast<int>(RNS_E_INVALID);
+            }
+            return launch(csum_rounds_kernel<G, U, S, NT(), BUF()>, grid, block, lds, st, a);
+        },
+        nt, buf_ok(a));
 }
 
 template <bool S>
@@ -121,11 +85,8 @@ int launch_strided_tiny(const CsumArgs &a, hipStream_t st)
     // (10.76-11.5 / 10.97-11.14); four: 13.55-13.65 (session r05h)
     constexpr int B = 2;
     const dim3 grid(static_cast<uint32_t>((static_cast<uint64_t>(a.n) + 64 * B - 1) / (64 * B))), block(64);
-    if (buf_records(a) < kOobOffset)
-        hipLaunchKernelGGL((csum_strided_tiny_kernel<true, B>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((csum_strided_tiny_kernel<false, B>), grid, block, 0, st, a);
-    return hip_status(hipGetLastError());
+    return with_flags([&](auto buf) { return launch(csum_strided_tiny_kernel<buf(), B>, grid, block, 0, st, a); },
+                      buf_ok(a));
 }
 
 }  // namespace rns

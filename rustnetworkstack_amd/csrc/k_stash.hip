@@ -4,34 +4,22 @@
 
 namespace rns {
 
-int launch_fill(const CsumArgs &a, dim3 grid, hipStream_t st)
+// FILL / RX / TX: the mode's flag of csum_mixed_kernel; NT: nontemporal loads.
+template <bool NT, bool FILL, bool RX, bool TX>
+static int launch_stash(const CsumArgs &a, dim3 grid, hipStream_t st)
 {
-    const dim3 block(kMixedBlock<true>);
-    if (buf_records(a) < kOobOffset)
-        hipLaunchKernelGGL((csum_mixed_kernel<false, false, true, true>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((csum_mixed_kernel<false, false, false, true>), grid, block, 0, st, a);
-    return hip_status(hipGetLastError());
+    return with_flags(
+        [&](auto buf) {
+            return launch(csum_mixed_kernel<false, NT, buf(), FILL, RX, TX>, grid, dim3(kMixedBlock<true>), 0, st, a);
+        },
+        buf_ok(a));
 }
 
-int launch_rx(const CsumArgs &a, dim3 grid, hipStream_t st)
-{
-    const dim3 block(kMixedBlock<true>);
-    if (buf_records(a) < kOobOffset)  // nontemporal loads
-        hipLaunchKernelGGL((csum_mixed_kernel<false, true, true, false, true>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((csum_mixed_kernel<false, true, false, false, true>), grid, block, 0, st, a);
-    return hip_status(hipGetLastError());
-}
+int launch_fill(const CsumArgs &a, dim3 grid, hipStream_t st) { return launch_stash<false, true, false, false>(a, grid, st); }
 
-int launch_tx(const CsumArgs &a, dim3 grid, hipStream_t st)
-{
-    const dim3 block(kMixedBlock<true>);
-    if (buf_records(a) < kOobOffset)
-        hipLaunchKernelGGL((csum_mixed_kernel<false, false, true, false, false, true>), grid, block, 0, st, a);
-    else
-        hipLaunchKernelGGL((csum_mixed_kernel<false, false, false, false, false, true>), grid, block, 0, st, a);
-    return hip_status(hipGetLastError());
-}
+// nontemporal loads
+int launch_rx(const CsumArgs &a, dim3 grid, hipStream_t st) { return launch_stash<true, false, true, false>(a, grid, st); }
+
+int launch_tx(const CsumArgs &a, dim3 grid, hipStream_t st) { return launch_stash<false, false, false, true>(a, grid, st); }
 
 }  // namespace rns

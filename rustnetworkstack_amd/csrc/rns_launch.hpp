@@ -2,8 +2,11 @@
 // kernel family so the build compiles them in parallel: k_shapes.hip (the explicit-descriptor
 // shapes and the tuning entry), k_packed.hip (the packed form), k_chain.hip (fragment chains),
 // k_stash.hip (transmit fill / receive verify / transmit finalize).  rns_checksum.hip holds the
-// C ABI.
+// device entry points of the C ABI, rns_pipeline.hip the host-resident pipeline and the
+// multi-GPU contexts.
 #pragma once
+
+#include <type_traits>
 
 #include "rns_kernels.hpp"
 
@@ -60,6 +63,45 @@ inline void set_arena(CsumArgs &a, const uint8_t *arena, uint64_t arena_bytes)
     a.arena_bytes = arena_bytes + a.base_adjust;
 }
 
+// Buffer loads need a 32-bit offset range: arenas below 4 GiB take the BUF instantiations.
+inline bool buf_ok(const CsumArgs &a) { return buf_records(a) < kOobOffset; }
+
+// Grid of the kernels that give one wave a 64-packet batch.
+inline uint32_t waves64(uint64_t n) { return static_cast<uint32_t>((n + 63) / 64); }
+
+// Runtime flags to template arguments: with_flags(f, b0, b1, ...) calls
+// f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...).  Every combination of the flags
+// is instantiated, so a launcher normalises its flags first and cuts the combinations that
+// have no kernel with `if constexpr`.
+template <class F>
+int with_flags(F &&f)
+{
+    return f();
+}
+template <class F, class... Rest>
+int with_flags(F &&f, bool b, Rest... rest)
+{
+    auto bind = [&](auto c) { return with_flags([&](auto... cs) { return f(c, cs...); }, rest...); };
+    return b ? bind(std::true_type{}) : bind(std::false_type{});
+}
+
+// The same for a packets-per-lane bound: with_kmax<1, 2, 8>(K, f) calls f with the first listed
+// bound >= K as a std::integral_constant (the last one for any larger K).
+template <uint32_t KM, uint32_t... More, class F>
+int with_kmax(uint32_t K, F &&f)
+{
+    if constexpr (sizeof...(More) == 0)
+        return f(std::integral_constant<uint32_t, KM>{});
+    else
+        return K <= KM ? f(std::integral_constant<uint32_t, KM>{}) : with_kmax<More...>(K, f);
+}
+
+// One kernel launch and its status.
+inline int launch(void (*kernel)(const CsumArgs), dim3 grid, dim3 block, size_t lds, hipStream_t st, const CsumArgs &a)
+{
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, a);
+    return hip_status(hipGetLastError());
+}
 
 // k_shapes.hip: the explicit-descriptor kernels by (variant, lanes per packet, chunks in flight)
 template <bool S>
@@ -73,17 +115,18 @@ int launch_fill_packed(const CsumArgs &a, hipStream_t st);
 int launch_stream_rx(const CsumArgs &a, hipStream_t st);
 int launch_tx_packed(const CsumArgs &a, hipStream_t st);
 int launch_strided_rx(const CsumArgs &a, hipStream_t st);
-// k_chain.hip: K packets per lane (1..kChainMaxK); FILL = the head-fragment fill
+// k_chain.hip: K packets per lane (1..kChainMaxK); FILL = the head-fragment fill; deep = 4 waves/SIMD
 template <bool FILL>
-int launch_chain(const CsumArgs &a, uint32_t K, bool nt, bool runs, hipStream_t st);
-extern template int launch_chain<false>(const CsumArgs &, uint32_t, bool, bool, hipStream_t);
-extern template int launch_chain<true>(const CsumArgs &, uint32_t, bool, bool, hipStream_t);
-template <bool FILL>
+int launch_chain(const CsumArgs &a, uint32_t K, bool nt, bool runs, bool deep, hipStream_t st);
+extern template int launch_chain<false>(const CsumArgs &, uint32_t, bool, bool, bool, hipStream_t);
+extern template int launch_chain<true>(const CsumArgs &, uint32_t, bool, bool, bool, hipStream_t);
+// the transmit-rows kernel: checksum / head-fragment fill (FILL), chain finalize (FIN), compact finalize (FIN, CPT)
+template <bool FILL, bool FIN = false, bool CPT = false>
 int launch_txrows(const CsumArgs &a, hipStream_t st);
-extern template int launch_txrows<false>(const CsumArgs &, hipStream_t);
-extern template int launch_txrows<true>(const CsumArgs &, hipStream_t);
-int launch_txfin(const CsumArgs &a, hipStream_t st);
-int launch_txfin_packed(const CsumArgs &a, hipStream_t st);
+extern template int launch_txrows<false, false, false>(const CsumArgs &, hipStream_t);
+extern template int launch_txrows<true, false, false>(const CsumArgs &, hipStream_t);
+extern template int launch_txrows<false, true, false>(const CsumArgs &, hipStream_t);
+extern template int launch_txrows<false, true, true>(const CsumArgs &, hipStream_t);
 int launch_rx_chain(const CsumArgs &a, uint32_t K, bool nt, hipStream_t st);  // receive verify over chains
 // k_stash.hip: the class kernel's stash modes on one-wave workgroups
 int launch_fill(const CsumArgs &a, dim3 grid, hipStream_t st);

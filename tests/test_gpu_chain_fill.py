@@ -13,6 +13,7 @@ from oracle import oracle as O
 from rustnetworkstack_amd import _lib
 from rustnetworkstack_amd.batch import csum_chain, csum_chain_fill
 from rustnetworkstack_amd.workloads import tx_chain_layout
+from test_gpu_chains import CHAIN_SHAPES, chain_shape_first
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -367,3 +368,23 @@ def test_full_size_transmit_chains(oracle, name, frag):
             assert np.array_equal(host_u16(out)[:sample], want)
     del a
     torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("hint", [383, 384])
+@pytest.mark.parametrize("pattern,n", CHAIN_SHAPES)
+def test_k_branches(oracle, pattern, n, hint):
+    """Every K branch of the chain launcher in fill mode (the fill has no deep form: the same
+    kernel either way), temporal and nontemporal: heads of 18-60 bytes (any start parity) with
+    the field at 16 / 6 / 2, then scattered payload fragments of 1-700 bytes."""
+    first = chain_shape_first(pattern, n)
+    nf = int(first[-1])
+    fw = O.splitmix64_words(0xCF60 + n + len(pattern), nf)
+    ln = (fw % np.uint64(700) + np.uint64(1)).astype(np.uint32)
+    ln[first[:-1]] = (fw[first[:-1]] % np.uint64(43) + np.uint64(18)).astype(np.uint32)   # the heads
+    off = np.zeros(nf, dtype=np.uint64)
+    off[1:] = np.cumsum(ln[:-1].astype(np.uint64) + (fw[:-1] >> np.uint64(40)) % np.uint64(29))  # gaps of 0-28 B
+    arena_np = O.splitmix64_bytes(0xCF61, int(off[-1]) + int(ln[-1]) + 64)
+    seeds = (O.splitmix64_words(0xCF62, n) & np.uint64(0xFFFF)).astype(np.uint16)
+    field = np.array([16, 6, 2], dtype=np.uint16)[np.arange(n) % 3]
+    want, fits = check(oracle, arena_np, off, ln, first.astype(np.uint32), seeds, field, hint=hint)
+    assert fits.all()

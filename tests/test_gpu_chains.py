@@ -414,3 +414,40 @@ def test_runs_tiling_a_region(oracle, max_gap, max_len, align):
                 got = host_u16(csum_chain(a, dev(offs, np.int64), dev(lens, np.int32), dev(first, np.int32),
                                           dev(seeds, np.int16), complement=complement, frag_len_hint=hint, runs=runs))
                 assert np.array_equal(got, expect), (complement, runs, hint, int(np.flatnonzero(got != expect)[0]))
+
+
+# The chain launchers' branches by the mean fragment count (chain_pick_k in rns_checksum.hip):
+# K packets per lane, and for the temporal checksum the form at 4 waves/SIMD ("deep": K >= 3,
+# or K == 2 with 2+ fragments per packet).  (fragment counts repeated over the batch, packets):
+# a wave takes 64 * K packets, so each batch is two full waves and a partial one.
+CHAIN_SHAPES = [pytest.param((1,), 130, id="mean1.0-K1"), pytest.param((1, 2), 260, id="mean1.5-K2"),
+                pytest.param((2, 3), 260, id="mean2.5-K2-deep"), pytest.param((1, 1, 1, 2), 516, id="mean1.25-K4-deep")]
+
+
+def chain_shape_first(pattern, n):
+    """CSR ``first`` (int64 [n+1]) for n packets whose fragment counts repeat ``pattern``."""
+    assert n % len(pattern) == 0
+    first = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(np.tile(pattern, n // len(pattern)), out=first[1:])
+    return first
+
+
+@pytest.mark.parametrize("hint", [383, 384])
+@pytest.mark.parametrize("pattern,n", CHAIN_SHAPES)
+def test_k_and_depth_branches(oracle, pattern, n, hint):
+    """Every K / depth branch of the chain launcher, on both sides of the fragment-length hint
+    that selects nontemporal loads (383: temporal, where the deep form lives; 384): scattered
+    fragments of 1-700 bytes (odd sizes, any alignment), with and without the run check."""
+    first = chain_shape_first(pattern, n)
+    nf = int(first[-1])
+    fw = O.splitmix64_words(0xC6A0 + n + len(pattern), nf)
+    lens = (fw % np.uint64(700) + np.uint64(1)).astype(np.uint32)
+    offs = ((fw >> np.uint64(20)) % np.uint64((1 << 20) - 1024)).astype(np.uint64)
+    seeds = (O.splitmix64_words(0xC6A1, n) & np.uint64(0xFFFF)).astype(np.uint16)
+    arena_np = O.splitmix64_bytes(0xC6A2, 1 << 20)
+    expect = oracle.chain_batch(arena_np, offs, lens, first, seeds, complement=True)
+    a = torch.from_numpy(arena_np).to(DEV)
+    for runs in (False, True):
+        got = host_u16(csum_chain(a, dev(offs, np.int64), dev(lens, np.int32), dev(first.astype(np.uint32), np.int32),
+                                  dev(seeds, np.int16), complement=True, frag_len_hint=hint, runs=runs))
+        assert np.array_equal(got, expect), (runs, int(np.flatnonzero(got != expect)[0]))

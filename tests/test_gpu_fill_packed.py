@@ -164,3 +164,15 @@ def test_misaligned_packing_is_invalid():
     st = _lib.load().rns_csum_fill_packed_dev(arena.data_ptr(), 256, arena.data_ptr(), arena.data_ptr(), 3, None,
                                               None, 16, None, 4, 0, 0, None, None)
     assert st == _lib.RNS_E_INVALID
+
+
+@pytest.mark.parametrize("len_hint", [1023, 1024])
+def test_rows_depth_threshold(oracle, len_hint):
+    """len_hint 1023 / 1024: either side of the fill's D = 8 / D = 16 choice, on two full
+    64-packet batches and a partial one."""
+    n = 130
+    ln = (O.splitmix64_words(0x1F23, n) % np.uint64(2100)).astype(np.uint16)
+    ln[::17] = 0
+    ln[3::19] = 17
+    field = np.array([16, 6, 2, 10, 15], dtype=np.uint16)[np.arange(n) % 5]
+    check_fill(oracle, ln, field, first_off=16, seed_salt=len_hint, len_hint=len_hint)

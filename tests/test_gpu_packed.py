@@ -174,3 +174,17 @@ def test_stream_rows_many_ends_and_empties(oracle, pattern):
         expect = oracle.batch(arena, poff, ln, sd, complement=False)
         got = run_packed(arena, blk, ln, sd, 4, len_hint=340)
         assert np.array_equal(got, expect)
+
+
+@pytest.mark.parametrize("len_hint", [1023, 1024])
+def test_rows_depth_threshold(oracle, len_hint):
+    """len_hint 1023 / 1024: either side of the rows kernel's D = 8 / D = 16 choice, on two
+    full 64-packet batches and a partial one (empty, odd and multi-row packets)."""
+    n = 130
+    ln = (O.splitmix64_words(0x1023, n) % np.uint64(2100)).astype(np.uint32)
+    ln[::17] = 0
+    sd = (O.splitmix64_words(0x1024, n) & np.uint64(0xFFFF)).astype(np.uint16)
+    blk, poff, end = packed_layout(ln, 4, 16)
+    arena = O.splitmix64_bytes(0x1025, end + 16)
+    expect = oracle.batch(arena, poff, ln, sd, complement=True)
+    assert np.array_equal(run_packed(arena, blk, ln, sd, 4, complement=True, len_hint=len_hint), expect)

@@ -378,3 +378,35 @@ def test_strided_full_size_64B_equals_packed_entry():
     assert int(((got & _lib.RNS_RX_ACCEPT) == 0).sum().item()) == b.expected_bad
     del b
     torch.cuda.empty_cache()
+
+
+@pytest.mark.parametrize("bytes_per_datagram", [128, 129])
+def test_packed_ack_arena_threshold(oracle, bytes_per_datagram):
+    """An arena of exactly 128 bytes per datagram (the stream kernel's ACK path) and of 129 (the
+    rows receive kernel): 130 datagrams of 40..128 bytes, two full 64-datagram units and a
+    partial one; every status and L4 sum against the reference's receive path."""
+    from rustnetworkstack_amd.batch import packed_layout, rx_verify_packed
+    n = 130
+    w = O.splitmix64_words(0xAC8, n)
+    pkts = []
+    for i in range(n):
+        body = O.splitmix64_bytes(0xAC9 + i, int(w[i] % np.uint64(89))).tobytes()
+        p = bytearray([ipv4(6, tcp_seg(R4, L4, body)), ipv4(17, body + b"\x00" * 8), ipv4(1, icmp4(body[:60])),
+                       ipv6(6, tcp_seg(R6, L6, body[:68]))][i % 4])
+        if i % 7 == 3:
+            p[int(w[i] >> np.uint64(8)) % len(p)] ^= 0x04
+        pkts.append(bytes(p))
+    ln = np.array([len(p) for p in pkts], dtype=np.uint32)
+    assert ln.max() <= 128
+    blk, poff, end = packed_layout(ln, 4, 0)
+    arena = np.full(bytes_per_datagram * n, 0xA5, dtype=np.uint8)   # padding never counts
+    assert end <= arena.size
+    for o, p in zip(poff.tolist(), pkts):
+        arena[o:o + len(p)] = np.frombuffer(p, dtype=np.uint8)
+    l4 = torch.empty(n, dtype=torch.uint16, device=DEV)
+    st = rx_verify_packed(torch.from_numpy(arena).to(DEV), dev(blk.astype(np.uint64), np.int64),
+                          dev(ln.astype(np.uint16), np.int16), L4, L6, l4_sum=l4)
+    got = list(zip(st.cpu().numpy().tolist(), l4.view(torch.int16).cpu().numpy().view(np.uint16).tolist()))
+    expect = [tuple(O.rx_verify_ref(p, L4, L6, ones_comp=oracle.compute_ones_comp)) for p in pkts]
+    bad = [(i, len(pkts[i]), got[i], expect[i]) for i in range(n) if got[i] != expect[i]]
+    assert not bad, bad[:5]

@@ -15,6 +15,7 @@ from rustnetworkstack_amd import _lib
 from rustnetworkstack_amd.batch import recv_batch_chain, rx_verify, rx_verify_chain
 from rx_chain_helper import (hdr_len, ipv4_long, lay_chains, make_datagrams, netbuffers, rx_verify_chain_ref,
                              split_any)
+from test_gpu_chains import CHAIN_SHAPES
 from test_rx_oracle import L4, L6, R4, R6, icmp4, ipv4, ipv6, tcp_seg
 
 pytestmark = pytest.mark.gpu
@@ -345,3 +346,25 @@ def test_socket_to_verdict(oracle):
     chains = [netbuffers(p) for p in pkts]
     assert [int(x) for x in np.diff(first.astype(np.int64))] == [len(c) for c in chains]
     same(run(pool, off, ln, first), expect(chains, oracle), chains)
+
+
+@pytest.mark.parametrize("pattern,n", CHAIN_SHAPES)
+def test_k_branches(oracle, pattern, n):
+    """Every K branch of the receive launcher (K = 1, 2 and the general form; it has no deep
+    form): datagrams of every kind cut into exactly the pattern's fragment counts (the first
+    fragment holds the IP header and a few bytes more, the rest is cut evenly, odd pieces
+    included), at arbitrary byte alignment."""
+    pkts = make_datagrams(n, 0x4B1 + n, max_body=900)
+    chains = []
+    for i, p in enumerate(pkts):
+        k = pattern[i % len(pattern)]
+        if k == 1 or len(p) < 2 * k:
+            cuts = [0] + [len(p)] * k      # short datagrams: trailing empty fragments keep the count
+        else:
+            h = min(hdr_len(p) + i % 5, len(p) - (k - 1))
+            step = -(-(len(p) - h) // (k - 1))
+            cuts = [0] + [min(h + j * step, len(p)) for j in range(k)]
+        chains.append([p[a:b] for a, b in zip(cuts[:-1], cuts[1:])])
+    assert sum(len(c) for c in chains) * len(pattern) == n * sum(pattern)
+    arena, off, ln, first = lay_chains(chains, seed=n)
+    same(run(arena, off, ln, first), expect(chains, oracle), chains)

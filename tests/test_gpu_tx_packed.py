@@ -175,3 +175,12 @@ def test_packed_tx_argument_checks():
     st = tx_fill_packed(arena, blk, len16)  # all-zero datagrams: version 0, malformed, untouched
     assert int((st != _lib.RNS_TX_MALFORMED).sum().item()) == 0
     assert int(arena.sum().item()) == 0
+
+
+@pytest.mark.parametrize("len_hint", [1023, 1024])
+def test_packed_tx_rows_depth_threshold(oracle, len_hint):
+    """len_hint 1023 / 1024: either side of the finalize's D = 8 / D = 16 choice, on two full
+    64-datagram batches and a partial one."""
+    pkts = outgoing(130, 0x7D16)
+    got, want, got_st, want_st = run_packed_tx(oracle, pkts, len_hint=len_hint)
+    assert_same(got, want, got_st, want_st, pkts)
