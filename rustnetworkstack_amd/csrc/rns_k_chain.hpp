@@ -337,11 +337,7 @@ __global__ __launch_bounds__(kChainBlock, (chain_occ<NT, BUF, KMAX, RUNS, FILL, 
             }
             if (p < a.n && (!FILL || a.out))
                 a.out[p] = static_cast<uint16_t>(ok ? r : 0u);  // 64 consecutive u16: one 128-byte store
-            if (a.bad) {
-                const uint64_t rejected = __ballot(p < a.n && !ok);
-                if (rejected && lane == 0)
-                    atomicAdd(a.bad, static_cast<uint32_t>(__popcll(rejected)));
-            }
+            count_rejected(a, lane, p < a.n && !ok);
         }
         wave_lds_fence();  // the next batch rewrites pk
         const uint64_t next = static_cast<uint64_t>(base) + step;

@@ -81,11 +81,11 @@ __device__ __forceinline__ uint32_t dpp_or_zero(uint32_t v)
         __builtin_amdgcn_update_dpp(0, static_cast<int>(v), CTRL, ROW_MASK, BANK_MASK, true));
 }
 
-// Exclusive prefix sum over the 64 lanes (the total must fit 32 bits): the classic
+// Inclusive prefix sum over the 64 lanes (the total must fit 32 bits): the classic
 // gfx9 DPP scan (row_shr 1,2,3 / 4 / 8 within each row of 16, then row_bcast:15 and
-// row_bcast:31 across rows) — VALU only, no LDS round trip.  packed_scan applies it
-// to the lanes' padded lengths.
-__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v)
+// row_bcast:31 across rows) — VALU only, no LDS round trip.  packed_scan applies the
+// exclusive form to the lanes' padded lengths.
+__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
 {
     uint32_t x = v;
     x += dpp_or_zero<0x111>(v);              // row_shr:1
@@ -95,19 +95,53 @@ __device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v)
     x += dpp_or_zero<0x118, 0xF, 0xC>(x);    // row_shr:8, banks 2-3
     x += dpp_or_zero<0x142, 0xA, 0xF>(x);    // row_bcast:15 into rows 1 and 3
     x += dpp_or_zero<0x143, 0xC, 0xF>(x);    // row_bcast:31 into rows 2 and 3
-    return x - v;
+    return x;
 }
 
-__device__ __forceinline__ uint32_t packed_scan(const CsumArgs &a, uint32_t lane, uint32_t len)
+__device__ __forceinline__ uint32_t wave_excl_scan(uint32_t v) { return wave_incl_scan(v) - v; }
+
+__device__ __forceinline__ uint32_t packed_scan(const CsumArgs &a, uint32_t len)
 {
-    (void)lane;
     const uint32_t pad = (len + a.align_mask) & ~a.align_mask;  // < 2^17: the block's sum fits 32 bits
     return wave_excl_scan(pad);
 }
 
-__device__ __forceinline__ uint64_t packed_off(const CsumArgs &a, uint64_t base, uint32_t lane, uint32_t len)
+__device__ __forceinline__ uint64_t packed_off(const CsumArgs &a, uint64_t base, uint32_t len)
 {
-    return a.blk_off[base >> 6] + packed_scan(a, lane, len);
+    return a.blk_off[base >> 6] + packed_scan(a, len);
+}
+
+// A 64-bit value of another lane: lane l (wave-uniform l), the first active lane, the lane
+// below (lane 0 reads its own).  (The lane intrinsics return int: widen through uint32_t, or
+// an offset past 2 GiB sign-extends.)
+__device__ __forceinline__ uint64_t lane_u64(uint64_t v, uint32_t l)
+{
+    return (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<uint32_t>(v >> 32), l))) << 32) |
+           static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<uint32_t>(v), l));
+}
+
+__device__ __forceinline__ uint64_t first_lane_u64(uint64_t v)
+{
+    return (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v >> 32)))) << 32) |
+           static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(v)));
+}
+
+__device__ __forceinline__ uint64_t lane_below_u64(uint64_t v, uint32_t lane)
+{
+    return (static_cast<uint64_t>(static_cast<uint32_t>(__shfl(static_cast<int>(v >> 32), static_cast<int>(lane) - 1, 64))) << 32) |
+           static_cast<uint32_t>(__shfl(static_cast<int>(v), static_cast<int>(lane) - 1, 64));
+}
+
+// Rejected descriptors of the wave, counted with one atomic (lane = the lane's index in its wave).
+// (csum_rows_kernel and csum_strided_tiny_kernel keep the spelled-out form: through this function
+// their register counts move, SGPRs 38 -> 40 and VGPRs 48 -> 50.)
+__device__ __forceinline__ void count_rejected(const CsumArgs &a, uint32_t lane, bool rejected_lane)
+{
+    if (a.bad) {
+        const uint64_t rejected = __ballot(rejected_lane);
+        if (rejected && lane == 0)
+            atomicAdd(a.bad, static_cast<uint32_t>(__popcll(rejected)));
+    }
 }
 
 // Cache-policy bits of the "nontemporal" buffer loads (gfx950 CPol: 1 = sc0, 2 = nt,
@@ -138,6 +172,16 @@ __device__ __forceinline__ uint32_t keep_bytes(uint32_t d, int lo, int hi, int j
     const uint32_t hm = static_cast<uint32_t>((1ull << (8 * b)) - 1);
     const uint32_t lm = static_cast<uint32_t>((1ull << (8 * a)) - 1);
     return d & hm & ~lm;  // b <= a gives 0
+}
+
+// Little-endian 16-bit word sum of one chunk (v_sad_u16: lo16 + hi16 + acc, one op per dword).
+__device__ __forceinline__ uint32_t sad4(uint4 v, uint32_t acc)
+{
+    acc = __builtin_amdgcn_sad_u16(v.x, 0, acc);
+    acc = __builtin_amdgcn_sad_u16(v.y, 0, acc);
+    acc = __builtin_amdgcn_sad_u16(v.z, 0, acc);
+    acc = __builtin_amdgcn_sad_u16(v.w, 0, acc);
+    return acc;
 }
 
 // Lanes of one wave exchanging data through LDS: the hardware executes a wave's LDS

@@ -275,10 +275,7 @@ __device__ __forceinline__ void run_tiny(const CsumArgs &a, __amdgpu_buffer_rsrc
             const uint4 one[1] = {x};
             stash_chunks<MODE, G, 1, 1>(k[q], sub, one, st);
         }
-        uint32_t s = __builtin_amdgcn_sad_u16(x.x, 0, 0u);  // <= 64 bytes: never the BE path
-        s = __builtin_amdgcn_sad_u16(x.y, 0, s);
-        s = __builtin_amdgcn_sad_u16(x.z, 0, s);
-        s = __builtin_amdgcn_sad_u16(x.w, 0, s);
+        const uint32_t s = sad4(x, 0u);  // <= 64 bytes: never the BE path
         const uint32_t words = group_allreduce<G>(s);
         sel = (sub == static_cast<uint32_t>(q)) ? words : sel;
     }
@@ -617,7 +614,7 @@ __device__ __forceinline__ Desc<BUF> load_desc(const CsumArgs &a, uint64_t p)
         d.len = a.fixed_len;
     } else if constexpr (PACKED) {  // lengths only, offsets from the wave's scan
         d.len = live ? a.len16[q] : 0u;
-        off = packed_off(a, p & ~63ull, static_cast<uint32_t>(p & 63), d.len);
+        off = packed_off(a, p & ~63ull, d.len);
     } else {
         off = desc_off(a, q);
         d.len = a.len[q];
@@ -704,7 +701,7 @@ csum_mixed_kernel(const CsumArgs a)
         Desc<BUF> cd;
         if constexpr (kPf) {
             cd.len = live ? nx_len : 0u;
-            const uint64_t off = nx_blk + packed_scan(a, lane, cd.len);
+            const uint64_t off = nx_blk + packed_scan(a, cd.len);
             cd.off = BUF ? (off > 0xFFFFFFFFull ? 0xFFFFFFFFu : static_cast<uint32_t>(off)) : off;
             cd.off = live ? cd.off : 0;
             cd.field = 0xFFFFFFFFu;
@@ -878,11 +875,7 @@ csum_mixed_kernel(const CsumArgs a)
             if (live && d_ok)  // set_be16(&mut header[f..f+2], checksum), after the wave read its 64 packets
                 fill_store(a, fs, d_start, d_field, res, st + pos * kNS);
         }
-        if (a.bad) {
-            const uint64_t rejected = __ballot(live && !d_ok);
-            if (rejected && lane == 0)
-                atomicAdd(a.bad, static_cast<uint32_t>(__popcll(rejected)));
-        }
+        count_rejected(a, lane, live && !d_ok);
     }
 }
 

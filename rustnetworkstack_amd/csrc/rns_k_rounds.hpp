@@ -66,6 +66,22 @@ constexpr uint32_t kOobOffset = 0xFFFFF000u;
 // bytes, and are masked away like every byte outside a packet).
 __host__ __device__ __forceinline__ uint64_t buf_records(const CsumArgs &a) { return (a.arena_bytes + 15) & ~15ull; }
 
+// The 16 bytes at arena offset off when `in`, else zeros: a buffer load at an out-of-range
+// offset (no memory traffic), or a flat load of the arena's first chunk with the result
+// selected away — branch-free either way, so the compiler counts the loads in flight exactly.
+template <bool BUF, bool NT>
+__device__ __forceinline__ uint4 load16(const CsumArgs &a, __amdgpu_buffer_rsrc_t rsrc, uint64_t off, bool in)
+{
+    if constexpr (BUF) {
+        const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(rsrc, in ? static_cast<uint32_t>(off) : kOobOffset, 0,
+                                                              NT ? kNtAux : 0);
+        return make_uint4(x.x, x.y, x.z, x.w);
+    } else {
+        const uint4 x = load_chunk<NT>(a.arena + (in ? off : 0));
+        return in ? x : make_uint4(0, 0, 0, 0);
+    }
+}
+
 // Chunk stash (receive verify and transmit fill).  The word sum is linear in the
 // bytes, so verify and fill run the PLAIN data pass over the whole packet; the few
 // chunks their finish needs (a datagram's header, a packet's checksum field) are
@@ -367,7 +383,7 @@ __global__ __launch_bounds__(kBlock) void csum_rounds_kernel(const CsumArgs a)
                 d_len = live ? a.fixed_len : 0u;
             } else if constexpr (PACKED) {
                 d_len = live ? c_len : 0u;
-                d_start = c_off + packed_scan(a, lane, d_len);
+                d_start = c_off + packed_scan(a, d_len);
             } else {
                 d_start = live ? c_off : 0;
                 d_len = live ? c_len : 0u;
@@ -385,7 +401,7 @@ __global__ __launch_bounds__(kBlock) void csum_rounds_kernel(const CsumArgs a)
             }
             if constexpr (PACKED) {  // lengths only, offsets from the wave's scan
                 d_len = live ? a.len16[p] : 0u;
-                d_start = packed_off(a, base, lane, d_len);
+                d_start = packed_off(a, base, d_len);
             }
         }
         d_start += a.base_adjust;
@@ -442,11 +458,7 @@ __global__ __launch_bounds__(kBlock) void csum_rounds_kernel(const CsumArgs a)
         // c2, r03; the ordinary policy stays)
         if (live)
             a.out[p] = static_cast<uint16_t>(acc);
-        if (a.bad) {
-            const uint64_t rejected = __ballot(live && !d_ok);
-            if (rejected && lane == 0)
-                atomicAdd(a.bad, static_cast<uint32_t>(__popcll(rejected)));
-        }
+        count_rejected(a, lane, live && !d_ok);
     }
 }
 

@@ -1,5 +1,6 @@
-// The packed form's row machinery: the stream kernel (v4, receive verify of ACK-sized units) and
-// the rows decomposition (rows_region_sum) the round-4/5 kernels share.
+// The packed form's row machinery: the stream kernel (v4, receive verify of ACK-sized units), the
+// rows decomposition (rows_region_sum) the round-4/5 kernels share, and the packed kernels' common
+// unit prologue and cold paths (packed_unit, wave_serial_sums, ack_unit_sum, unaligned_head).
 // (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
 #pragma once
 
@@ -31,20 +32,6 @@ namespace rns {
 // A block whose region does not start 16-byte aligned (a first packet at an unaligned
 // offset, or an unaligned arena base) takes a simple per-packet wave loop instead.
 // ---------------------------------------------------------------------------
-// Inclusive prefix sum over the 64 lanes (wave_excl_scan's DPP sequence).
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v)
-{
-    uint32_t x = v;
-    x += dpp_or_zero<0x111>(v);              // row_shr:1
-    x += dpp_or_zero<0x112>(v);              // row_shr:2
-    x += dpp_or_zero<0x113>(v);              // row_shr:3
-    x += dpp_or_zero<0x114, 0xF, 0xE>(x);    // row_shr:4, banks 1-3
-    x += dpp_or_zero<0x118, 0xF, 0xC>(x);    // row_shr:8, banks 2-3
-    x += dpp_or_zero<0x142, 0xA, 0xF>(x);    // row_bcast:15 into rows 1 and 3
-    x += dpp_or_zero<0x143, 0xC, 0xF>(x);    // row_bcast:31 into rows 2 and 3
-    return x;
-}
-
 // Keep the first c (1..16) bytes of a chunk: the 128-bit mask (1 << 8c) - 1 as two
 // 64-bit halves (shift counts stay in 0..63).
 __device__ __forceinline__ uint4 keep_first(uint4 v, uint32_t c)
@@ -81,16 +68,126 @@ __device__ __forceinline__ uint4 own_chunk(const CsumArgs &a, __amdgpu_buffer_rs
                                            uint32_t len, uint32_t i)
 {
     const uint64_t o = off + 16u * i;
-    const bool in = 16u * i < len && o + 16 <= recs;
-    uint4 x;
-    if constexpr (BUF) {
-        const u32x4 y = __builtin_amdgcn_raw_buffer_load_b128(rsrc, in ? static_cast<uint32_t>(o) : kOobOffset, 0, 0);
-        x = make_uint4(y.x, y.y, y.z, y.w);
-    } else {
-        const uint4 y = load_chunk<false>(a.arena + (in ? o : 0));
-        x = in ? y : make_uint4(0, 0, 0, 0);
+    return load16<BUF, false>(a, rsrc, o, 16u * i < len && o + 16 <= recs);
+}
+
+// Receive verify's results for datagram p: the status byte and, where asked for, the L4 sum.
+__device__ __forceinline__ void store_rx_status(const CsumArgs &a, uint64_t p, uint8_t stv, uint32_t l4_res)
+{
+    a.status[p] = stv;
+    if (a.l4_out)
+        a.l4_out[p] = static_cast<uint16_t>(l4_res);
+}
+
+// The whole wave sums one packet at a time (the packed kernels' unaligned regions, the strided
+// receive form's longer datagrams): for each lane o of todo, in order, the packet at lane o's
+// start with lane o's len, its LE word sum left in lane o's mine.  (csum_rows_kernel keeps its
+// own copy of this loop: through this function its SGPR count moves, 38 -> 40 at BUF, D = 8.)
+template <bool NT, bool BUF>
+__device__ __forceinline__ void wave_serial_sums(const CsumArgs &a, __amdgpu_buffer_rsrc_t rsrc, uint32_t lane,
+                                                 uint64_t todo, uint64_t start, uint32_t len, uint32_t &mine)
+{
+    while (todo) {
+        const uint32_t o = static_cast<uint32_t>(__builtin_ctzll(todo));
+        todo &= todo - 1;
+        const Pkt k = make_pkt(lane_u64(start, o), __builtin_amdgcn_readlane(len, o));
+        uint32_t acc = 0;
+        for (uint32_t cc = 0; cc < k.nch; cc += 64) {
+            uint4 w[1];
+            issue_pass<64, 1, NT, BUF, 1>(a, rsrc, k, cc + lane, w);
+            mask_edges<64, 1, 1>(k, cc + lane, w);
+            acc = sum_le<1, 1>(w, acc);
+        }
+        const uint32_t sum = group_allreduce<64>(acc);
+        mine = lane == o ? sum : mine;
     }
-    return x;
+}
+
+// A wave's 64-packet unit of the packed form (one wave per block of 64 threads): the lane's
+// packet p (q: its index clamped into the batch, for branch-free descriptor loads), its length
+// (0 past the batch) and seed (0 without a.seed; loaded with the length, dropped by the compiler
+// in the kernels that take none), the unit's first byte r0, the lane's offset excl in the unit
+// and the unit's padded bytes total.  start() = the packet's arena offset and ok() = whether it
+// lies in the arena are formed where a kernel asks for them (formed in packed_unit they stay
+// live over the row loop of a path that needs them only after it: 2 VGPRs in csum_stream_kernel).
+struct PackedUnit {
+    uint64_t p, q;
+    bool live;
+    uint32_t len, seed;
+    uint64_t r0;
+    uint32_t excl, total;
+    __device__ __forceinline__ uint64_t start() const { return r0 + excl; }
+    __device__ __forceinline__ bool ok(const CsumArgs &a) const
+    {
+        return start() <= a.arena_bytes && len <= a.arena_bytes - start();
+    }
+};
+
+__device__ __forceinline__ PackedUnit packed_unit(const CsumArgs &a, uint32_t lane)
+{
+    PackedUnit u;
+    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * 64;
+    u.p = base + lane;
+    u.live = u.p < a.n;
+    u.q = u.live ? u.p : a.n - 1;  // branch-free descriptor loads
+    // (the block offset is loaded per lane at an index the compiler cannot prove uniform: a
+    // uniform load is moved to SGPRs right away, with a vmcnt(0) wait for every row in flight)
+    const uint32_t zero_v = __builtin_amdgcn_mbcnt_lo(0u, 0u);
+    const uint64_t r0v = a.blk_off[(base >> 6) + zero_v];
+    u.len = u.live ? static_cast<uint32_t>(a.len16[u.q]) : 0u;
+    u.seed = (a.seed && u.live) ? static_cast<uint32_t>(a.seed[u.q]) : 0u;
+    u.r0 = first_lane_u64(r0v) + a.base_adjust;  // the wave's first packet
+    const uint32_t pad = (u.len + a.align_mask) & ~a.align_mask;
+    const uint32_t incl = wave_incl_scan(pad);
+    u.excl = incl - pad;
+    u.total = __builtin_amdgcn_readlane(incl, 63);  // the region's bytes
+    return u;
+}
+
+// ACK-sized unit (every packet at most 64 bytes, 16-byte-aligned starts): the owner loads its
+// packet's 4 chunks, all in flight before the first is used, and sums them masked to the packet.
+// MASKED: own[] gets the masked chunks (the receive finish reads zeros past the end), else the raw ones.
+template <bool BUF, bool MASKED, int N>
+__device__ __forceinline__ uint32_t ack_unit_sum(const CsumArgs &a, __amdgpu_buffer_rsrc_t rsrc, uint64_t recs,
+                                                 uint64_t start, uint32_t len, uint4 (&own)[N])
+{
+    static_assert(N >= 4, "four chunks hold an ACK-sized packet");
+    uint32_t mine = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        own[i] = own_chunk<BUF>(a, rsrc, recs, start, len, i);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        uint4 x = own[i];
+        if (16u * i + 16u > len)  // the sum sees none of the bytes past the end
+            x = 16u * i < len ? keep_first(x, len - 16u * i) : make_uint4(0, 0, 0, 0);
+        if constexpr (MASKED)
+            own[i] = x;
+        mine = sad4(x, mine);
+    }
+    return mine;
+}
+
+// The first N chunks of a packet from the 16-byte boundary below its unaligned start (N = 5
+// hold its first 65-80 bytes), masked to the packet (none loaded when not present).  Returns
+// start & 15.  (csum_strided_rx_kernel keeps its own copy: through this function it takes 58-60
+// VGPRs instead of 48.)
+template <bool BUF, int N>
+__device__ __forceinline__ uint32_t unaligned_head(const CsumArgs &a, __amdgpu_buffer_rsrc_t rsrc, uint64_t recs,
+                                                   uint64_t start, uint32_t len, bool present, uint4 (&own)[N])
+{
+    const uint64_t b0 = start & ~15ull;
+    const uint32_t s0 = static_cast<uint32_t>(start & 15);
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+        own[i] = own_chunk<BUF>(a, rsrc, recs, b0, present ? s0 + len : 0u, i);
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const int lo = static_cast<int>(s0) - 16 * i, hi = static_cast<int>(s0 + len) - 16 * i;
+        own[i] = make_uint4(keep_bytes(own[i].x, lo, hi, 0), keep_bytes(own[i].y, lo, hi, 4),
+                            keep_bytes(own[i].z, lo, hi, 8), keep_bytes(own[i].w, lo, hi, 12));
+    }
+    return s0;
 }
 
 // Receive verify (rns_rx_verify_packed_dev).  The lanes that load a datagram's first 4
@@ -116,55 +213,24 @@ __global__ __launch_bounds__(64, kStreamRxOcc) void csum_stream_kernel(const Csu
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint8_t *>(a.arena), static_cast<short>(0), static_cast<int>(BUF ? buf_records(a) : 0), 0x00020000);
     const uint64_t recs = buf_records(a);
-    const uint64_t base = static_cast<uint64_t>(blockIdx.x) * 64;
-    const uint64_t p = base + lane;
-    const bool live = p < a.n;
-    const uint64_t q = live ? p : a.n - 1;  // branch-free descriptor loads
-    // (the block offset is loaded per lane at an index the compiler cannot prove uniform: a
-    // uniform load is moved to SGPRs right away, with a vmcnt(0) wait for every row in flight)
-    const uint32_t zero_v = __builtin_amdgcn_mbcnt_lo(0u, 0u);
-    const uint64_t r0v = a.blk_off[(base >> 6) + zero_v];
-    const uint32_t len = live ? static_cast<uint32_t>(a.len16[q]) : 0u;
-    // (the lane intrinsics return int: widen through uint32_t, or an offset past 2 GiB sign-extends)
-    const uint64_t r0 =
-        ((static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(r0v >> 32))))
-          << 32) |
-         static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<uint32_t>(r0v)))) +
-        a.base_adjust;  // the wave's first packet
-    const uint32_t pad = (len + a.align_mask) & ~a.align_mask;
-    const uint32_t incl = wave_incl_scan(pad);
-    const uint32_t excl = incl - pad;
-    const uint32_t total = __builtin_amdgcn_readlane(incl, 63);  // the region's bytes
+    const PackedUnit u = packed_unit(a, lane);
+    const uint64_t p = u.p, r0 = u.r0;
+    const uint32_t len = u.len, excl = u.excl, total = u.total;
+    const bool live = u.live;
     uint32_t mine = 0;
     bool odd = false;
 
     if ((r0 & 15) == 0 && !__ballot(len > 64)) {
         // ---- ACK-sized unit: every owner takes its datagram whole ----
-        const uint64_t start = r0 + excl;
-        const bool ok = start <= a.arena_bytes && len <= a.arena_bytes - start;
+        const uint64_t start = u.start();
+        const bool ok = u.ok(a);
         uint4 own[kNS + 1];
-#pragma unroll
-        for (int i = 0; i < 4; ++i)  // all four loads in flight before the first is used
-            own[i] = own_chunk<BUF>(a, rsrc, recs, start, len, i);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            uint4 x = own[i];
-            if (16u * i + 16u > len)  // rx_finish sees zeros past the end, as from the stash
-                x = 16u * i < len ? keep_first(x, len - 16u * i) : make_uint4(0, 0, 0, 0);
-            own[i] = x;
-            mine = __builtin_amdgcn_sad_u16(x.x, 0, mine);
-            mine = __builtin_amdgcn_sad_u16(x.y, 0, mine);
-            mine = __builtin_amdgcn_sad_u16(x.z, 0, mine);
-            mine = __builtin_amdgcn_sad_u16(x.w, 0, mine);
-        }
+        mine = ack_unit_sum<BUF, true>(a, rsrc, recs, start, len, own);  // (zeros past the end, as from the stash)
         own[4] = make_uint4(0, 0, 0, 0);
         uint32_t l4_res = 0;
         const uint8_t stv = rx_finish<kNS + 1>(a, own, mine, 0u, len, false, false, live && ok && len != 0, l4_res);
-        if (live) {
-            a.status[p] = stv;
-            if (a.l4_out)
-                a.l4_out[p] = static_cast<uint16_t>(l4_res);
-        }
+        if (live)
+            store_rx_status(a, p, stv, l4_res);
         return;
     }
     if ((r0 & 15) == 0) {
@@ -180,15 +246,7 @@ __global__ __launch_bounds__(64, kStreamRxOcc) void csum_stream_kernel(const Csu
         uint4 v[kStreamD];
         auto issue = [&](uint32_t k, uint4 &dst) {  // row k: chunk 64k + lane of the region
             const uint64_t off = rb + (static_cast<uint64_t>(k) << 10) + (lane << 4);
-            const bool in = k < nrows && off + 16 <= recs;
-            if constexpr (BUF) {
-                const u32x4 x = __builtin_amdgcn_raw_buffer_load_b128(
-                    rsrc, in ? static_cast<uint32_t>(off) : kOobOffset, 0, NT ? kNtAux : 0);
-                dst = make_uint4(x.x, x.y, x.z, x.w);
-            } else {
-                const uint4 x = load_chunk<NT>(a.arena + (in ? off : 0));
-                dst = in ? x : make_uint4(0, 0, 0, 0);
-            }
+            dst = load16<BUF, NT>(a, rsrc, off, k < nrows && off + 16 <= recs);
         };
         // (issue order pinned: the loop consumes v[0] first, so its load must be the oldest
         // on entry as on the back edge, or the compiler waits for all of them)
@@ -228,10 +286,7 @@ __global__ __launch_bounds__(64, kStreamRxOcc) void csum_stream_kernel(const Csu
                     x = keep_first(x, is_end ? (t & 15u) + 1u : 16u);
                 if (mark && (t & kHead))
                     stash[pk * kNS + ((t >> 14) & 3u)] = x;
-                uint32_t s = __builtin_amdgcn_sad_u16(x.x, 0, 0u);
-                s = __builtin_amdgcn_sad_u16(x.y, 0, s);
-                s = __builtin_amdgcn_sad_u16(x.z, 0, s);
-                s = __builtin_amdgcn_sad_u16(x.w, 0, s);
+                const uint32_t s = sad4(x, 0u);
                 // the row D ahead into the registers this row just freed (past the region: no
                 // memory traffic).  Issued only after the row is consumed, so the loop-carried
                 // registers need no copy — a copy at the back edge waits for every load in flight.
@@ -252,63 +307,28 @@ __global__ __launch_bounds__(64, kStreamRxOcc) void csum_stream_kernel(const Csu
         mine = len ? pend[lane] - pstart[lane] : 0u;
     } else {
         // ---- unaligned region (rare): the whole wave sums one packet at a time ----
-        const uint64_t start = r0 + excl;
-        const bool ok = start <= a.arena_bytes && len <= a.arena_bytes - start;
-        uint64_t todo = __ballot(len != 0 && ok);
-        while (todo) {
-            const uint32_t o = static_cast<uint32_t>(__builtin_ctzll(todo));
-            todo &= todo - 1;
-            const uint64_t st =
-                (static_cast<uint64_t>(static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<uint32_t>(start >> 32), o)))
-                 << 32) |
-                static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<uint32_t>(start), o));
-            const uint32_t L = __builtin_amdgcn_readlane(len, o);
-            const Pkt k = make_pkt(st, L);
-            uint32_t acc = 0;
-            for (uint32_t cc = 0; cc < k.nch; cc += 64) {
-                uint4 w[1];
-                issue_pass<64, 1, NT, BUF, 1>(a, rsrc, k, cc + lane, w);
-                mask_edges<64, 1, 1>(k, cc + lane, w);
-                acc = sum_le<1, 1>(w, acc);
-            }
-            const uint32_t sum = group_allreduce<64>(acc);
-            mine = lane == o ? sum : mine;
-        }
+        const uint64_t start = u.start();
+        const bool ok = u.ok(a);
+        wave_serial_sums<NT, BUF>(a, rsrc, lane, __ballot(len != 0 && ok), start, len, mine);
         odd = r0 & 1;  // every packet of the range shares the region start's misalignment
         // each owner takes its header from the 16-byte boundary below its start: 5 chunks hold
         // its first 65-80 bytes, masked to the datagram
-        const uint64_t b0 = start & ~15ull;
-        const uint32_t s0 = static_cast<uint32_t>(start & 15);
         uint4 own[5];
-#pragma unroll
-        for (int i = 0; i < 5; ++i)
-            own[i] = own_chunk<BUF>(a, rsrc, recs, b0, (len && ok) ? s0 + len : 0u, i);
-#pragma unroll
-        for (int i = 0; i < 5; ++i) {
-            const int lo = static_cast<int>(s0) - 16 * i, hi = static_cast<int>(s0 + len) - 16 * i;
-            own[i] = make_uint4(keep_bytes(own[i].x, lo, hi, 0), keep_bytes(own[i].y, lo, hi, 4),
-                                keep_bytes(own[i].z, lo, hi, 8), keep_bytes(own[i].w, lo, hi, 12));
-        }
+        const uint32_t s0 = unaligned_head<BUF>(a, rsrc, recs, start, len, len && ok, own);
         uint32_t l4_res = 0;
         const uint8_t stv = rx_finish<5>(a, own, mine, s0, len, odd, false, live && ok && len != 0, l4_res);
-        if (live) {
-            a.status[p] = stv;
-            if (a.l4_out)
-                a.l4_out[p] = static_cast<uint16_t>(l4_res);
-        }
+        if (live)
+            store_rx_status(a, p, stv, l4_res);
         return;
     }
     wave_lds_fence();
-    const uint64_t start = r0 + excl;
-    const bool ok = start <= a.arena_bytes && len <= a.arena_bytes - start;
+    const uint64_t start = u.start();
+    const bool ok = u.ok(a);
     uint32_t l4_res = 0;
     const uint8_t stv = rx_finish<kNS>(a, stash + lane * kNS, mine, static_cast<uint32_t>(start & 15), len, odd, false,
                                        live && ok && len != 0, l4_res);
-    if (live) {
-        a.status[p] = stv;
-        if (a.l4_out)
-            a.l4_out[p] = static_cast<uint16_t>(l4_res);
-    }
+    if (live)
+        store_rx_status(a, p, stv, l4_res);
 }
 
 // Three measured choices shape the row stream (round 4; the losing forms are gone):
@@ -321,7 +341,9 @@ __global__ __launch_bounds__(64, kStreamRxOcc) void csum_stream_kernel(const Csu
 // The rows decomposition over one region that starts 16-byte aligned at r0 (an offset from
 // a.arena) and holds total bytes (a multiple of 16; ceil(total / 1 KiB) rows): the lane's packet covers chunks c0..e of the region (its
 // start 16-byte aligned, len bytes, len 0: none).  Returns the packet's LE word sum (pairs by
-// absolute parity).  Used by csum_rows_kernel, csum_rows_rx_kernel and csum_txrows_kernel (rns_k_rows.hpp).
+// absolute parity).  Used by csum_rows_kernel (rns_k_rows.hpp),
+// csum_rows_rx_kernel (rns_k_rows_rx.hpp), csum_rows_tx_kernel (rns_k_rows_tx.hpp) and csum_txrows_kernel
+// (rns_k_txrows.hpp).
 struct NoHook {
     __device__ __forceinline__ void operator()() const {}
 };
@@ -403,10 +425,7 @@ __device__ __forceinline__ uint32_t rows_stream(const CsumArgs &a, const __amdgp
         uint32_t part = 0;
         if (len) {
             const uint4 x = keep_first(endv, ((len - 1) & 15u) + 1u);
-            part = __builtin_amdgcn_sad_u16(x.x, 0, 0u);
-            part = __builtin_amdgcn_sad_u16(x.y, 0, part);
-            part = __builtin_amdgcn_sad_u16(x.z, 0, part);
-            part = __builtin_amdgcn_sad_u16(x.w, 0, part);
+            part = sad4(x, 0u);
         }
         return part;
     };
@@ -424,10 +443,7 @@ __device__ __forceinline__ uint32_t rows_stream(const CsumArgs &a, const __amdgp
         for (int j = 0; j < D; ++j) {
             const uint32_t k = k0 + j;
             const uint4 x = v[j];
-            uint32_t s = __builtin_amdgcn_sad_u16(x.x, 0, 0u);
-            s = __builtin_amdgcn_sad_u16(x.y, 0, s);
-            s = __builtin_amdgcn_sad_u16(x.z, 0, s);
-            s = __builtin_amdgcn_sad_u16(x.w, 0, s);
+            const uint32_t s = sad4(x, 0u);
             // the row D ahead into the registers this row just freed (issued after the row
             // is consumed: no loop-carried copy, exact vmcnt(D-1) waits)
             __builtin_amdgcn_sched_barrier(0);

@@ -33,3 +33,6 @@
 #include "rns_k_chain_rx.hpp"
 #include "rns_k_stream.hpp"
 #include "rns_k_rows.hpp"
+#include "rns_k_rows_rx.hpp"
+#include "rns_k_rows_tx.hpp"
+#include "rns_k_txrows.hpp"

@@ -410,3 +410,48 @@ def test_packed_ack_arena_threshold(oracle, bytes_per_datagram):
     expect = [tuple(O.rx_verify_ref(p, L4, L6, ones_comp=oracle.compute_ones_comp)) for p in pkts]
     bad = [(i, len(pkts[i]), got[i], expect[i]) for i in range(n) if got[i] != expect[i]]
     assert not bad, bad[:5]
+
+
+def small_datagrams(n, seed, longest):
+    """Datagrams of at most `longest` bytes (64: ACK-sized), every kind, some corrupted."""
+    w = O.splitmix64_words(seed, n)
+    pkts = []
+    for i in range(n):
+        body = O.splitmix64_bytes(seed + 1 + i, int(w[i] % np.uint64(longest - 39))).tobytes()
+        p = bytearray([ipv4(6, tcp_seg(R4, L4, body[:longest - 40])), ipv4(17, body[:longest - 28] + b"\x00" * 8),
+                       ipv4(6, tcp_seg(R4, L4, body[:longest - 48]), ihl=7), ipv6(6, tcp_seg(R6, L6, body[:longest - 60])),
+                       ipv4(1, icmp4(body[:longest - 28]))][i % 5])
+        if i % 7 == 3:
+            p[int(w[i] >> np.uint64(8)) % len(p)] ^= 0x04
+        pkts.append(bytes(p[:longest]))
+    return pkts
+
+
+def test_packed_rows_receive_ack_unit(oracle):
+    """The rows receive kernel (more than 128 arena bytes per datagram) with a unit of ACK-sized
+    datagrams only (its owners load their datagrams whole), a unit that holds 1400-byte
+    datagrams (the rows) and a partial unit: 129 datagrams against the reference's receive path."""
+    pkts = small_datagrams(129, 0xAD0, 64)
+    for i in range(64, 128, 5):
+        pkts[i] = bytes(ipv4(6, tcp_seg(R4, L4, O.splitmix64_bytes(i, 1360).tobytes())))
+    assert max(len(p) for p in pkts[:64]) <= 64 and (sum((len(p) + 15) // 16 * 16 for p in pkts) + 16) // len(pkts) > 128
+    expect = [O.rx_verify_ref(p, L4, L6, ones_comp=oracle.compute_ones_comp) for p in pkts]
+    st, l4 = run_packed_rx(pkts, 4, 0)
+    got = list(zip(st.tolist(), l4.tolist()))
+    bad = [(i, len(pkts[i]), got[i], expect[i]) for i in range(len(pkts)) if got[i] != tuple(expect[i])]
+    assert not bad, bad[:5]
+
+
+@pytest.mark.parametrize("first_off,base_shift", [(5, 0), (0, 3)])
+def test_packed_ack_arena_unaligned(oracle, first_off, base_shift):
+    """An arena of at most 128 bytes per datagram (the stream kernel) whose units do not start
+    16-byte aligned (an unaligned first offset, an unaligned arena base): every unit takes the
+    per-datagram wave loop with its header chunks from the boundary below.  129 datagrams of up
+    to 100 bytes against the reference's receive path."""
+    pkts = small_datagrams(129, 0xAD8 + first_off, 100)
+    assert sum((len(p) + 15) // 16 * 16 for p in pkts) + first_off + 16 + base_shift <= 128 * len(pkts)
+    expect = [O.rx_verify_ref(p, L4, L6, ones_comp=oracle.compute_ones_comp) for p in pkts]
+    st, l4 = run_packed_rx(pkts, 4, first_off, base_shift)
+    got = list(zip(st.tolist(), l4.tolist()))
+    bad = [(i, len(pkts[i]), got[i], expect[i]) for i in range(len(pkts)) if got[i] != tuple(expect[i])]
+    assert not bad, bad[:5]
