@@ -10,9 +10,11 @@ BUILD    := $(PKG)/build
 LIB      := $(PKG)/librns_checksum.so
 
 # Plain C callers of the C ABI (no torch): built here, run on a GPU by tests/test_c_caller.py
-# (test_batch_abi), tests/test_c_caller_tx_chain_packed.py (the compact-descriptor chain finalize)
-# and tests/test_c_caller_rx_chain.py (the receive verify over fragment chains).
-CABI_TESTS := tests/c/test_batch_abi tests/c/test_tx_chain_packed_abi tests/c/test_rx_chain_abi
+# (test_batch_abi), tests/test_c_caller_tx_chain_packed.py (the compact-descriptor chain finalize),
+# tests/test_c_caller_rx_chain.py (the receive verify over fragment chains) and
+# tests/test_c_caller_rx_pool.py (the receive verify over pool buffers).
+CABI_TESTS := tests/c/test_batch_abi tests/c/test_tx_chain_packed_abi tests/c/test_rx_chain_abi \
+              tests/c/test_rx_pool_abi
 
 all: $(LIB) oracle $(CABI_TESTS)
 

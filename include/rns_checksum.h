@@ -316,6 +316,44 @@ int rns_rx_verify_chain_dev(const uint8_t *d_arena, uint64_t arena_bytes, const 
                             const uint8_t *local_ipv4, const uint8_t *local_ipv6, uint8_t *d_status,
                             uint16_t *d_l4_sum /* optional */, void *stream);
 
+/* Receive verify of datagrams held in fixed-size POOL BUFFERS (recv_packet's chains):
+ * buffers of 2^buf_log2 bytes (6 <= buf_log2 <= 15; the reference's FRAGMENT_SIZE is 2^9),
+ * buffer k = d_pool[k << buf_log2 .. ).  Datagram i has length d_len16[i] and occupies
+ * nf_i = ceil(len_i / 2^buf_log2) buffers, all full but the last; their indices are
+ * d_buf_idx[first_i .. first_i + nf_i), where first_i = d_blk_first[i / 64] + the sum of nf_k over
+ * the datagrams k of i's 64-datagram block before i.  (The blocks' entries are independent of each
+ * other, as the block offsets of rns_csum_batch_packed_dev are.)  Descriptors: 2 B per datagram,
+ * 4 B per buffer, 4 B per 64 datagrams — 14 B for a 1500-byte datagram in 512-byte buffers
+ * against the CSR form's 40 B.
+ * The form is defined by the CSR chain it expands to: fragment j of datagram i at offset
+ * (uint64_t)d_buf_idx[first_i + j] << buf_log2, of 2^buf_log2 bytes, the last one of the remainder.
+ * d_status[i] and d_l4_sum[i] are exactly what rns_rx_verify_chain_dev gives for that chain on the
+ * same pool.  It follows that
+ *   - a datagram with d_len16[i] == 0 has no fragments: RNS_RX_MALFORMED, d_l4_sum 0 (header()
+ *     asserts in the reference, so parity is unpinned there, as for the other len == 0 cases);
+ *   - a fragment whose bytes end past pool_bytes makes its datagram, and that one only,
+ *     RNS_RX_MALFORMED;
+ *   - first_i + nf_i > n_frags is RNS_RX_MALFORMED;
+ *   - two datagrams may name the same buffer: nothing is written to the pool.
+ * Because every buffer starts 16-byte aligned and holds at least 64 bytes, the header lies in the
+ * first buffer at an aligned start and every fragment before the last has even length: the kernel
+ * has neither the chain kernel's unaligned head path nor its exact per-datagram loop.
+ * n_pkts == 0 is RNS_OK; buf_log2 outside 6..15, a NULL d_pool / d_blk_first / d_len16 / d_status /
+ * local address, a NULL d_buf_idx with n_frags > 0, n_pkts > RNS_CHAIN_MAX_PACKETS or a d_pool that
+ * is not 16-byte aligned is RNS_E_INVALID, all before the device is touched. */
+int rns_rx_verify_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2,
+                           const uint32_t *d_buf_idx, uint32_t n_frags,
+                           const uint32_t *d_blk_first,   /* (n_pkts + 63) / 64 entries */
+                           const uint16_t *d_len16, uint32_t n_pkts,
+                           const uint8_t *local_ipv4, const uint8_t *local_ipv6,
+                           uint8_t *d_status, uint16_t *d_l4_sum /* optional */, void *stream);
+
+/* Host helper for the pool form (CPU only): from the n lengths, blk_first ((n + 63) / 64 entries),
+ * optionally first[0..n] (the CSR index of the expanded chains) and *n_frags.  RNS_E_INVALID if the
+ * fragment total does not fit 32 bits or buf_log2 is outside 6..15. */
+int rns_rx_pool_layout(const uint16_t *len16, uint64_t n, uint32_t buf_log2,
+                       uint32_t *blk_first, uint32_t *first /* optional, n + 1 */, uint64_t *n_frags);
+
 /* Transmit finalize (SURVEY a6, §8f row 2 for whole datagrams): for each finished
  * outgoing IP datagram d_arena[d_off[i] .. + d_len[i]), the checksums the stack's
  * transmit path stores — tcp_output (tcp.rs:957-973: pseudo-header from the header's
@@ -524,6 +562,15 @@ int rns_io_recv_batch_packed(int fd, uint8_t *h_arena, uint64_t arena_bytes, uin
 int rns_io_recv_batch_chain(int fd, uint8_t *h_pool, uint32_t buf_bytes, uint32_t *h_free, uint32_t n_free,
                             uint32_t mru, uint32_t max_pkts, uint64_t *h_frag_off, uint32_t *h_frag_len,
                             uint32_t *h_first /* max_pkts + 1 */, uint32_t *n_frags_out, int timeout_ms);
+
+/* rns_io_recv_batch_chain with the compact outputs of rns_rx_verify_pool_dev, buffers of
+ * 2^buf_log2 bytes (6..15): h_free is permuted exactly as there, and its first *n_frags_out entries
+ * ARE d_buf_idx; h_len16[i] (max_pkts entries) = datagram i's length, h_blk_first[b]
+ * ((max_pkts + 63) / 64 entries) = the first fragment of datagram 64*b.  The same receive loop: the
+ * same drops, skips, caps and return values.  mru <= 65535, else RNS_E_INVALID. */
+int rns_io_recv_batch_pool(int fd, uint8_t *h_pool, uint32_t buf_log2, uint32_t *h_free, uint32_t n_free,
+                           uint32_t mru, uint32_t max_pkts, uint16_t *h_len16, uint32_t *h_blk_first,
+                           uint32_t *n_frags_out, int timeout_ms);
 
 /* Pinned host memory for arenas handed to rns_csum_batch_host. */
 int rns_host_alloc(uint64_t bytes, void **out);

@@ -4,16 +4,17 @@
 
 * ``util``      — the reference's `netstack::util` checksum surface, same names and errors;
 * ``batch``     — device-resident / host-resident batch API (torch tensors, numpy arrays);
+* ``pool``      — receive verify of pool-buffer chains over compact descriptors (also ``batch.*``);
 * ``workloads`` — the synthetic packet batches BASELINE.json's configs name.
 """
 from . import _lib, util  # noqa: F401
 from ._lib import ChecksumError, ChecksumLibraryMissing  # noqa: F401
 
-__all__ = ["util", "batch", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
+__all__ = ["util", "batch", "pool", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
 
 
 def __getattr__(name):
-    if name in ("batch", "workloads"):
+    if name in ("batch", "pool", "workloads"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

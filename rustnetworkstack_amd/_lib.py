@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = (
     "rns_rx_verify_packed_dev",
     "rns_rx_verify_strided_dev",
     "rns_rx_verify_chain_dev",
+    "rns_rx_verify_pool_dev",
+    "rns_rx_pool_layout",
     "rns_tx_fill_dev",
     "rns_tx_fill_packed_dev",
     "rns_tx_fill_chain_dev",
@@ -77,6 +79,7 @@ EXPORTED_SYMBOLS = (
     "rns_io_send_batch_chain",
     "rns_io_recv_batch_packed",
     "rns_io_recv_batch_chain",
+    "rns_io_recv_batch_pool",
     "rns_host_alloc",
     "rns_host_free",
     "rns_fill_splitmix64_dev",
@@ -143,6 +146,8 @@ _SIGNATURES = {
     "rns_rx_verify_packed_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "rns_rx_verify_strided_dev": (_int, [_vp, _u64, _u64, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "rns_rx_verify_chain_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "rns_rx_verify_pool_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "rns_rx_pool_layout": (_int, [_vp, _u64, _u32, _vp, _vp, ctypes.POINTER(_u64)]),
     "rns_tx_fill_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _vp]),
     "rns_tx_fill_packed_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _u32, _vp, _u32, _vp]),
     "rns_tx_fill_chain_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),
@@ -162,6 +167,7 @@ _SIGNATURES = {
     "rns_io_recv_batch_packed": (_int, [_int, _vp, _u64, _u32, _u32, _vp, _vp, ctypes.POINTER(_u64), _int]),
     "rns_io_recv_batch_chain": (_int, [_int, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _vp, ctypes.POINTER(_u32),
                                        _int]),
+    "rns_io_recv_batch_pool": (_int, [_int, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, ctypes.POINTER(_u32), _int]),
     "rns_host_alloc": (_int, [_u64, ctypes.POINTER(_vp)]),
     "rns_host_free": (_int, [_vp]),
     "rns_fill_splitmix64_dev": (_int, [_vp, _u64, _u64, _vp]),

@@ -605,15 +605,8 @@ def recv_batch_packed(fd: int, arena: np.ndarray, mru: int = 2048, max_pkts: int
     return ln[:r], blk[:(r + 63) // 64], int(end.value)
 
 
-def recv_batch_chain(fd: int, pool: np.ndarray, free: np.ndarray, buf_bytes: int = 512, mru: int = 2048,
-                     max_pkts: int | None = None, timeout_ms: int = 0):
-    """Read every queued datagram (after waiting up to ``timeout_ms`` for the first) into
-    NetBuffer chains (rns_io_recv_batch_chain; batched recv_packet, netif.rs:65-83): ``pool`` is
-    a uint8 pool of ``buf_bytes``-byte buffers, ``free`` (uint32, contiguous, permuted IN PLACE)
-    the indices of the free ones.  Each datagram is offered ``ceil(mru / buf_bytes)`` buffers and
-    keeps those it filled.  Returns ``(n, frag_off uint64, frag_len uint32, first uint32 [n+1],
-    n_frags)``: on return ``free[:n_frags]`` are the buffers in use, in fragment order, and
-    ``free[n_frags:]`` are still free."""
+def _recv_chain_args(pool: np.ndarray, free: np.ndarray, buf_bytes: int, mru: int, max_pkts: int | None):
+    """The checks recv_batch_chain and recv_batch_pool share: (buf_bytes, mru, n_free, max_pkts)."""
     if pool.dtype != np.uint8 or not pool.flags["C_CONTIGUOUS"]:
         raise ValueError("pool must be a contiguous uint8 array")
     if free.dtype != np.uint32 or not free.flags["C_CONTIGUOUS"] or not free.flags["WRITEABLE"]:
@@ -629,7 +622,19 @@ def recv_batch_chain(fd: int, pool: np.ndarray, free: np.ndarray, buf_bytes: int
         raise ValueError("free names a buffer outside the pool")
     cap = max(n_free - need + 1, 0)  # a datagram keeps at least one buffer and is offered `need`
     max_pkts = cap if max_pkts is None else min(int(max_pkts), cap)
-    max_pkts = min(max_pkts, 2 ** 31 - 1)
+    return buf_bytes, mru, n_free, min(max_pkts, 2 ** 31 - 1)
+
+
+def recv_batch_chain(fd: int, pool: np.ndarray, free: np.ndarray, buf_bytes: int = 512, mru: int = 2048,
+                     max_pkts: int | None = None, timeout_ms: int = 0):
+    """Read every queued datagram (after waiting up to ``timeout_ms`` for the first) into
+    NetBuffer chains (rns_io_recv_batch_chain; batched recv_packet, netif.rs:65-83): ``pool`` is
+    a uint8 pool of ``buf_bytes``-byte buffers, ``free`` (uint32, contiguous, permuted IN PLACE)
+    the indices of the free ones.  Each datagram is offered ``ceil(mru / buf_bytes)`` buffers and
+    keeps those it filled.  Returns ``(n, frag_off uint64, frag_len uint32, first uint32 [n+1],
+    n_frags)``: on return ``free[:n_frags]`` are the buffers in use, in fragment order, and
+    ``free[n_frags:]`` are still free."""
+    buf_bytes, mru, n_free, max_pkts = _recv_chain_args(pool, free, buf_bytes, mru, max_pkts)
     frag_off = np.empty(max(n_free, 1), dtype=np.uint64)
     frag_len = np.empty(max(n_free, 1), dtype=np.uint32)
     first = np.zeros(max(max_pkts, 0) + 1, dtype=np.uint32)
@@ -793,3 +798,15 @@ def csum_batch_multi_dev(shards, *, complement: bool = False) -> None:
         keep.append(sh)
     flags = _lib.RNS_FLAG_COMPLEMENT if complement else 0
     _lib.check(_lib.load().rns_csum_batch_multi_dev(arr, len(shards), flags), "rns_csum_batch_multi_dev")
+
+
+# The pool-buffer receive path (pool.py builds on the checks above) is part of this module's
+# interface: batch.rx_pool_layout, batch.rx_verify_pool, batch.recv_batch_pool.
+_POOL_API = ("recv_batch_pool", "rx_pool_layout", "rx_verify_pool")
+
+
+def __getattr__(name):
+    if name in _POOL_API:
+        from . import pool
+        return getattr(pool, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

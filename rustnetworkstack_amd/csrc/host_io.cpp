@@ -85,6 +85,127 @@ int recv_round(int fd, uint8_t *const *bufs, uint64_t cap, unsigned k, uint32_t 
     return r;
 }
 
+// The receive loop of rns_io_recv_batch_chain and rns_io_recv_batch_pool (rns_checksum.h describes
+// it there): datagrams into the next free buffers, h_free permuted so that its first *n_frags_out
+// entries are the buffers in use, in fragment order.  `out` records the descriptors of its form:
+// begin() once the arguments are valid; frag(j, buf, len) for fragment j = buffer `buf` holding len
+// bytes; datagram(i, first, cnt, len) for datagram i = fragments [first, first + cnt), len bytes.
+template <class Out>
+int recv_chain_loop(int fd, uint8_t *h_pool, uint32_t buf_bytes, uint32_t *h_free, uint32_t n_free, uint32_t mru,
+                    uint32_t max_pkts, uint32_t *n_frags_out, int timeout_ms, Out out)
+{
+    if (fd < 0 || !h_pool || !h_free || !n_frags_out || buf_bytes == 0 || mru == 0 || max_pkts == 0)
+        return RNS_E_INVALID;
+    // new_prealloc(mru): the buffers a datagram is offered, the last one cut so they hold mru bytes
+    const uint64_t need64 = (static_cast<uint64_t>(mru) + buf_bytes - 1) / buf_bytes;
+    if (need64 > kChainIov)
+        return RNS_E_INVALID;
+    const uint32_t need = static_cast<uint32_t>(need64);
+    const uint32_t last_cap = mru - (need - 1) * buf_bytes;  // 1..buf_bytes
+    if (max_pkts > static_cast<uint32_t>(INT_MAX))
+        max_pkts = static_cast<uint32_t>(INT_MAX);
+    *n_frags_out = 0;
+    out.begin();
+    if (n_free < need)
+        return 0;
+    const int pr = wait_first(fd, timeout_ms);
+    if (pr <= 0)
+        return pr;
+    uint32_t n = 0, used = 0;  // datagrams kept; h_free[0..used) in use, in fragment order
+    int status = 0;
+    // trim_tail: datagram n of len bytes lies in the buffers h_free[at..at + need).  It keeps the
+    // ceil(len / buf_bytes) it filled; they move to h_free[used..] (used <= at: the swaps run
+    // upwards, so every source entry is still in place when it is read) and the rest stay free.
+    auto keep = [&](uint32_t at, uint32_t len) {
+        const uint32_t cnt = (len + buf_bytes - 1) / buf_bytes;
+        for (uint32_t j = 0; j < cnt; ++j) {
+            const uint32_t b = h_free[at + j];
+            h_free[at + j] = h_free[used + j];
+            h_free[used + j] = b;
+            out.frag(used + j, b, j + 1 < cnt ? buf_bytes : len - j * buf_bytes);
+        }
+        out.datagram(n++, used, cnt, len);
+        used += cnt;
+    };
+    auto fill_iov = [&](struct iovec *v, uint32_t at) {
+        for (uint32_t j = 0; j < need; ++j) {
+            v[j].iov_base = h_pool + static_cast<uint64_t>(h_free[at + j]) * buf_bytes;
+            v[j].iov_len = j + 1 < need ? buf_bytes : last_cap;
+        }
+    };
+    bool sock = true;
+    while (sock && n < max_pkts) {  // sockets: recvmmsg, each message one datagram's buffers
+        unsigned k = max_pkts - n < kMmsg ? max_pkts - n : kMmsg;
+        if ((n_free - used) / need < k)
+            k = (n_free - used) / need;
+        if (k == 0)
+            break;
+        struct mmsghdr mh[kMmsg];
+        struct iovec iov[kMmsg * kChainIov];
+        std::memset(mh, 0, sizeof(mh));
+        const uint32_t at0 = used;
+        for (unsigned i = 0; i < k; ++i) {
+            fill_iov(iov + i * kChainIov, at0 + i * need);
+            mh[i].msg_hdr.msg_iov = iov + i * kChainIov;
+            mh[i].msg_hdr.msg_iovlen = need;
+        }
+        int r;
+        do {
+            r = recvmmsg(fd, mh, k, MSG_DONTWAIT | MSG_TRUNC, nullptr);
+        } while (r < 0 && errno == EINTR);
+        if (r < 0) {
+            if (errno == ENOTSOCK) {
+                sock = false;
+                break;
+            }
+            if (errno != EAGAIN && errno != EWOULDBLOCK)
+                status = RNS_E_IO;
+            break;
+        }
+        bool any = false;
+        for (int i = 0; i < r; ++i) {
+            const uint32_t len = mh[i].msg_len;
+            if (len == 0)  // an empty datagram: skipped, those after it are kept
+                continue;
+            any = true;
+            if ((mh[i].msg_hdr.msg_flags & MSG_TRUNC) || len > mru)  // longer than mru: dropped, takes no buffer
+                continue;
+            keep(at0 + static_cast<uint32_t>(i) * need, len);
+        }
+        // the queue is drained; a round of nothing but empty reads also ends the call (a closed
+        // stream peer reads as empty datagrams for ever)
+        if (static_cast<unsigned>(r) < k || !any)
+            break;
+    }
+    if (!sock) {
+        NonBlocking nb(fd);  // a TUN fd: one readv per datagram, like tun_recv
+        if (!nb.ok())
+            return RNS_E_IO;
+        uint8_t spill;  // the byte past mru: a longer datagram shows as mru + 1
+        while (n < max_pkts && n_free - used >= need) {
+            struct iovec v[kChainIov + 1];
+            fill_iov(v, used);
+            v[need].iov_base = &spill;
+            v[need].iov_len = 1;
+            const ssize_t r = readv(fd, v, static_cast<int>(need + 1));
+            if (r < 0) {
+                if (errno == EINTR)
+                    continue;
+                if (errno != EAGAIN && errno != EWOULDBLOCK)
+                    status = RNS_E_IO;
+                break;
+            }
+            if (r == 0)
+                break;
+            if (static_cast<uint64_t>(r) > mru)
+                continue;
+            keep(used, static_cast<uint32_t>(r));
+        }
+    }
+    *n_frags_out = used;
+    return (n == 0 && status) ? status : static_cast<int>(n);
+}
+
 }  // namespace
 
 extern "C" {
@@ -255,118 +376,41 @@ int rns_io_recv_batch_chain(int fd, uint8_t *h_pool, uint32_t buf_bytes, uint32_
                             uint32_t mru, uint32_t max_pkts, uint64_t *h_frag_off, uint32_t *h_frag_len,
                             uint32_t *h_first, uint32_t *n_frags_out, int timeout_ms)
 {
-    if (fd < 0 || !h_pool || !h_free || !h_frag_off || !h_frag_len || !h_first || !n_frags_out || buf_bytes == 0 ||
-        mru == 0 || max_pkts == 0)
+    if (!h_frag_off || !h_frag_len || !h_first)
         return RNS_E_INVALID;
-    // new_prealloc(mru): the buffers a datagram is offered, the last one cut so they hold mru bytes
-    const uint64_t need64 = (static_cast<uint64_t>(mru) + buf_bytes - 1) / buf_bytes;
-    if (need64 > kChainIov)
+    struct {
+        uint64_t *off;
+        uint32_t *len, *first, buf_bytes;
+        void begin() { first[0] = 0; }
+        void frag(uint32_t j, uint32_t buf, uint32_t flen)
+        {
+            off[j] = static_cast<uint64_t>(buf) * buf_bytes;
+            len[j] = flen;
+        }
+        void datagram(uint32_t i, uint32_t at, uint32_t cnt, uint32_t) { first[i + 1] = at + cnt; }
+    } out = {h_frag_off, h_frag_len, h_first, buf_bytes};
+    return recv_chain_loop(fd, h_pool, buf_bytes, h_free, n_free, mru, max_pkts, n_frags_out, timeout_ms, out);
+}
+
+int rns_io_recv_batch_pool(int fd, uint8_t *h_pool, uint32_t buf_log2, uint32_t *h_free, uint32_t n_free, uint32_t mru,
+                           uint32_t max_pkts, uint16_t *h_len16, uint32_t *h_blk_first, uint32_t *n_frags_out,
+                           int timeout_ms)
+{
+    if (!h_len16 || !h_blk_first || buf_log2 < 6 || buf_log2 > 15 || mru > 0xFFFFu)
         return RNS_E_INVALID;
-    const uint32_t need = static_cast<uint32_t>(need64);
-    const uint32_t last_cap = mru - (need - 1) * buf_bytes;  // 1..buf_bytes
-    if (max_pkts > static_cast<uint32_t>(INT_MAX))
-        max_pkts = static_cast<uint32_t>(INT_MAX);
-    *n_frags_out = 0;
-    h_first[0] = 0;
-    if (n_free < need)
-        return 0;
-    const int pr = wait_first(fd, timeout_ms);
-    if (pr <= 0)
-        return pr;
-    uint32_t n = 0, used = 0;  // datagrams kept; h_free[0..used) in use, in fragment order
-    int status = 0;
-    // trim_tail: datagram n of len bytes lies in the buffers h_free[at..at + need).  It keeps the
-    // ceil(len / buf_bytes) it filled; they move to h_free[used..] (used <= at: the swaps run
-    // upwards, so every source entry is still in place when it is read) and the rest stay free.
-    auto keep = [&](uint32_t at, uint32_t len) {
-        const uint32_t cnt = (len + buf_bytes - 1) / buf_bytes;
-        for (uint32_t j = 0; j < cnt; ++j) {
-            const uint32_t b = h_free[at + j];
-            h_free[at + j] = h_free[used + j];
-            h_free[used + j] = b;
-            h_frag_off[used + j] = static_cast<uint64_t>(b) * buf_bytes;
-            h_frag_len[used + j] = j + 1 < cnt ? buf_bytes : len - j * buf_bytes;
+    struct {
+        uint16_t *len16;
+        uint32_t *blk_first;
+        void begin() {}
+        void frag(uint32_t, uint32_t, uint32_t) {}  // h_free[j] is the descriptor
+        void datagram(uint32_t i, uint32_t at, uint32_t, uint32_t len)
+        {
+            if ((i & 63u) == 0)
+                blk_first[i >> 6] = at;
+            len16[i] = static_cast<uint16_t>(len);
         }
-        used += cnt;
-        h_first[++n] = used;
-    };
-    auto fill_iov = [&](struct iovec *v, uint32_t at) {
-        for (uint32_t j = 0; j < need; ++j) {
-            v[j].iov_base = h_pool + static_cast<uint64_t>(h_free[at + j]) * buf_bytes;
-            v[j].iov_len = j + 1 < need ? buf_bytes : last_cap;
-        }
-    };
-    bool sock = true;
-    while (sock && n < max_pkts) {  // sockets: recvmmsg, each message one datagram's buffers
-        unsigned k = max_pkts - n < kMmsg ? max_pkts - n : kMmsg;
-        if ((n_free - used) / need < k)
-            k = (n_free - used) / need;
-        if (k == 0)
-            break;
-        struct mmsghdr mh[kMmsg];
-        struct iovec iov[kMmsg * kChainIov];
-        std::memset(mh, 0, sizeof(mh));
-        const uint32_t at0 = used;
-        for (unsigned i = 0; i < k; ++i) {
-            fill_iov(iov + i * kChainIov, at0 + i * need);
-            mh[i].msg_hdr.msg_iov = iov + i * kChainIov;
-            mh[i].msg_hdr.msg_iovlen = need;
-        }
-        int r;
-        do {
-            r = recvmmsg(fd, mh, k, MSG_DONTWAIT | MSG_TRUNC, nullptr);
-        } while (r < 0 && errno == EINTR);
-        if (r < 0) {
-            if (errno == ENOTSOCK) {
-                sock = false;
-                break;
-            }
-            if (errno != EAGAIN && errno != EWOULDBLOCK)
-                status = RNS_E_IO;
-            break;
-        }
-        bool any = false;
-        for (int i = 0; i < r; ++i) {
-            const uint32_t len = mh[i].msg_len;
-            if (len == 0)  // an empty datagram: skipped, those after it are kept
-                continue;
-            any = true;
-            if ((mh[i].msg_hdr.msg_flags & MSG_TRUNC) || len > mru)  // longer than mru: dropped, takes no buffer
-                continue;
-            keep(at0 + static_cast<uint32_t>(i) * need, len);
-        }
-        // the queue is drained; a round of nothing but empty reads also ends the call (a closed
-        // stream peer reads as empty datagrams for ever)
-        if (static_cast<unsigned>(r) < k || !any)
-            break;
-    }
-    if (!sock) {
-        NonBlocking nb(fd);  // a TUN fd: one readv per datagram, like tun_recv
-        if (!nb.ok())
-            return RNS_E_IO;
-        uint8_t spill;  // the byte past mru: a longer datagram shows as mru + 1
-        while (n < max_pkts && n_free - used >= need) {
-            struct iovec v[kChainIov + 1];
-            fill_iov(v, used);
-            v[need].iov_base = &spill;
-            v[need].iov_len = 1;
-            const ssize_t r = readv(fd, v, static_cast<int>(need + 1));
-            if (r < 0) {
-                if (errno == EINTR)
-                    continue;
-                if (errno != EAGAIN && errno != EWOULDBLOCK)
-                    status = RNS_E_IO;
-                break;
-            }
-            if (r == 0)
-                break;
-            if (static_cast<uint64_t>(r) > mru)
-                continue;
-            keep(used, static_cast<uint32_t>(r));
-        }
-    }
-    *n_frags_out = used;
-    return (n == 0 && status) ? status : static_cast<int>(n);
+    } out = {h_len16, h_blk_first};
+    return recv_chain_loop(fd, h_pool, 1u << buf_log2, h_free, n_free, mru, max_pkts, n_frags_out, timeout_ms, out);
 }
 
 int rns_io_send_batch(int fd, const uint8_t *h_arena, const uint64_t *h_off, const uint32_t *h_len, uint32_t n)

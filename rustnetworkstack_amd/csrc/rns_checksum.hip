@@ -402,6 +402,30 @@ int rns_rx_verify_chain_dev(const uint8_t *d_arena, uint64_t arena_bytes, const 
                  });
 }
 
+int rns_rx_verify_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2, const uint32_t *d_buf_idx,
+                           uint32_t n_frags, const uint32_t *d_blk_first, const uint16_t *d_len16, uint32_t n_pkts,
+                           const uint8_t *local_ipv4, const uint8_t *local_ipv6, uint8_t *d_status, uint16_t *d_l4_sum,
+                           void *stream)
+{
+    return entry(n_pkts,
+                 buf_log2 >= kPoolMinLog2 && buf_log2 <= kPoolMaxLog2 && d_blk_first && d_len16 &&
+                     (!n_frags || d_buf_idx) && n_pkts <= RNS_CHAIN_MAX_PACKETS &&
+                     (reinterpret_cast<uintptr_t>(d_pool) & 15) == 0 && rx_valid(d_status, local_ipv4, local_ipv6),
+                 d_pool, pool_bytes, RNS_FLAG_COMPLEMENT, stream, [&](CsumArgs &a, hipStream_t st) {
+                     // the compact descriptors in CsumArgs: off32 = buffer indices, first = d_blk_first,
+                     // len16 = datagram lengths, align_mask = buffer bytes - 1 (rns_k_pool_rx.hpp)
+                     a.off32 = d_buf_idx;
+                     a.n_frags = n_frags;
+                     a.first = d_blk_first;
+                     a.len16 = d_len16;
+                     a.align_mask = (1u << buf_log2) - 1u;
+                     set_rx(a, d_status, d_l4_sum, local_ipv4, local_ipv6);
+                     const double mean = chain_mean(a);
+                     a.chain_k = chain_pick_k(mean);
+                     return launch_rx_pool(a, a.chain_k, chain_nt_from_arena(pool_bytes, n_frags, mean), st);
+                 });
+}
+
 int rns_tx_fill_packed_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_blk_off, const uint16_t *d_len16,
                            uint32_t align_log2, uint32_t n, uint8_t *d_status, uint32_t len_hint, void *stream)
 {

@@ -31,6 +31,7 @@
 #include "rns_k_mixed.hpp"
 #include "rns_k_chain.hpp"
 #include "rns_k_chain_rx.hpp"
+#include "rns_k_pool_rx.hpp"
 #include "rns_k_stream.hpp"
 #include "rns_k_rows.hpp"
 #include "rns_k_rows_rx.hpp"

@@ -10,6 +10,10 @@ datagrams built as the reference builds them — NetBuffer chains of a head frag
 headers) and a payload — with the heads in a header region and the payloads in a payload region:
 only used bytes cross PCIe to the GPU, only the header region comes back, and each datagram leaves
 gathered from its two fragments (rns_io_send_batch_chain, like send_packet's writev).
+RxPoolPipeline receives as the reference does — into a pool of fixed-size buffers that stay held
+until the stack releases them (rns_io_recv_batch_pool) — and verifies the chains where they lie
+(rns_rx_verify_pool_dev): a batch costs one copy of the buffers it used and 14 B of descriptors per
+MTU datagram.
 
 The reference handles one packet per loop iteration on its receive thread
 (packet_receive_thread lib.rs:26-31 -> recv_packet netif.rs:65-83 -> ip_input
@@ -32,6 +36,7 @@ import torch
 
 from .batch import (PinnedBuffer, recv_batch, recv_batch_packed, rx_verify, rx_verify_packed, send_batch,
                     send_batch_chain, tx_fill, tx_fill_chain, tx_fill_chain_packed)
+from .pool import recv_batch_pool, rx_verify_pool
 
 MRU = 2048  # netif.rs:66
 
@@ -539,3 +544,111 @@ class TxChainPipeline:
     def close(self):
         for s in self._sets:
             s.close()
+
+
+class PoolChains:
+    """The datagrams of one RxPoolPipeline batch: ``c[i]`` = (buffer indices uint32, length) of
+    datagram i, ``c.bytes(i)`` its bytes gathered from the host pool (valid while its buffers are
+    held)."""
+
+    def __init__(self, pool: np.ndarray, buf_bytes: int, idx: np.ndarray, first: np.ndarray, length: np.ndarray):
+        self.pool, self.buf_bytes, self.idx, self.first, self.length = pool, buf_bytes, idx, first, length
+
+    def __len__(self) -> int:
+        return int(self.length.shape[0])
+
+    def __getitem__(self, i: int) -> tuple[np.ndarray, int]:
+        return self.idx[int(self.first[i]):int(self.first[i + 1])], int(self.length[i])
+
+    def bytes(self, i: int) -> bytes:
+        idx, n = self[i]
+        rows = self.pool.reshape(-1, self.buf_bytes)[idx]
+        return rows.tobytes()[:n]
+
+
+class RxPoolPipeline:
+    """Batched receive into a buffer pool and verify in place: datagram fd -> pinned pool of
+    ``pool_bufs`` buffers of ``buf_bytes`` (recv_packet's NetBuffer chains, netif.rs:65-83) -> the
+    same offsets of a device mirror -> rns_rx_verify_pool_dev.  Buffers a batch used stay held, as a
+    TCP reassembly queue holds them, until ``release`` returns them to the free list; the next
+    batch takes free buffers only.  ``h2d_bytes``: the pool bytes the last ``receive`` copied (the
+    covering span of the buffers it used), ``desc_bytes``: its descriptor bytes."""
+
+    def __init__(self, local_ipv4: bytes, local_ipv6: bytes, device: int = 0, pool_bufs: int | None = None,
+                 buf_bytes: int = 512, mru: int = MRU, max_pkts: int = 65536):
+        self.local_ipv4, self.local_ipv6 = bytes(local_ipv4), bytes(local_ipv6)
+        self.buf_bytes, self.mru, self.max_pkts = int(buf_bytes), int(mru), int(max_pkts)
+        need = -(-self.mru // self.buf_bytes)
+        self.pool_bufs = int(pool_bufs) if pool_bufs is not None else self.max_pkts * need
+        self.dev = torch.device(f"cuda:{device}")
+        nblk = (self.max_pkts + 63) // 64
+        self.host = PinnedBuffer(self.pool_bufs * self.buf_bytes)
+        self._h_idx, self._h_len = PinnedBuffer(4 * self.pool_bufs), PinnedBuffer(2 * self.max_pkts)
+        self._h_blk, self._h_status = PinnedBuffer(4 * nblk), PinnedBuffer(self.max_pkts)
+        self._h_l4 = PinnedBuffer(2 * self.max_pkts)
+        self.d_pool = torch.empty(self.pool_bufs * self.buf_bytes, dtype=torch.uint8, device=self.dev)
+        self._d_idx = torch.empty(self.pool_bufs, dtype=torch.int32, device=self.dev)
+        self._d_len = torch.empty(self.max_pkts, dtype=torch.int16, device=self.dev)
+        self._d_blk = torch.empty(nblk, dtype=torch.int32, device=self.dev)
+        self._d_status = torch.empty(self.max_pkts, dtype=torch.uint8, device=self.dev)
+        self._d_l4 = torch.empty(self.max_pkts, dtype=torch.int16, device=self.dev)
+        self._done = torch.cuda.Event()
+        self._free = np.arange(self.pool_bufs, dtype=np.uint32)
+        self._held = np.zeros(self.pool_bufs, dtype=bool)
+        self.h2d_bytes = 0
+        self.desc_bytes = 0
+
+    @property
+    def free_bufs(self) -> int:
+        return int(self._free.shape[0])
+
+    def receive(self, fd: int, timeout_ms: int = 0) -> tuple[np.ndarray, np.ndarray, PoolChains]:
+        """One batch: (status uint8 [n], l4_sum uint16 [n], chains)."""
+        free = self._free
+        n, len16, blk, nf = recv_batch_pool(fd, self.host.array, free, self.buf_bytes, self.mru, self.max_pkts,
+                                            timeout_ms)
+        self.h2d_bytes = self.desc_bytes = 0
+        idx = free[:nf].copy()
+        first = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(-(-len16.astype(np.int64) // self.buf_bytes), out=first[1:])
+        chains = PoolChains(self.host.array, self.buf_bytes, idx, first, len16.copy())
+        if n == 0:
+            return np.empty(0, dtype=np.uint8), np.empty(0, dtype=np.uint16), chains
+        self._free = free[nf:].copy()
+        self._held[idx] = True
+        nb = blk.shape[0]
+        h_idx, h_len = self._h_idx.array.view(np.int32)[:nf], self._h_len.array.view(np.int16)[:n]
+        h_blk = self._h_blk.array.view(np.int32)[:nb]
+        h_idx[:], h_len[:], h_blk[:] = idx.view(np.int32), len16.view(np.int16), blk.view(np.int32)
+        lo, hi = int(idx.min()) * self.buf_bytes, (int(idx.max()) + 1) * self.buf_bytes
+        with torch.cuda.device(self.dev):
+            # pinned host memory (rns_host_alloc): every copy is a DMA transfer
+            self.d_pool[lo:hi].copy_(torch.from_numpy(self.host.array[lo:hi]), non_blocking=True)
+            self._d_idx[:nf].copy_(torch.from_numpy(h_idx), non_blocking=True)
+            self._d_len[:n].copy_(torch.from_numpy(h_len), non_blocking=True)
+            self._d_blk[:nb].copy_(torch.from_numpy(h_blk), non_blocking=True)
+            self.h2d_bytes, self.desc_bytes = hi - lo, 4 * nf + 2 * n + 4 * nb
+            rx_verify_pool(self.d_pool, self._d_idx[:nf], self._d_blk[:nb], self._d_len[:n], self.local_ipv4,
+                           self.local_ipv6, buf_bytes=self.buf_bytes, status=self._d_status[:n],
+                           l4_sum=self._d_l4[:n])
+            torch.from_numpy(self._h_status.array[:n]).copy_(self._d_status[:n], non_blocking=True)
+            torch.from_numpy(self._h_l4.array.view(np.int16)[:n]).copy_(self._d_l4[:n], non_blocking=True)
+            self._done.record()
+            self._done.synchronize()
+        return self._h_status.array[:n].copy(), self._h_l4.array.view(np.uint16)[:n].copy(), chains
+
+    def release(self, indices) -> None:
+        """Return held buffers to the free list (each index once, and only while it is held).  The list
+        is kept in index order: the next batch takes the lowest free buffers, so the span it copies
+        stays close to the buffers it uses instead of wrapping round the pool."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+        if idx.size == 0:
+            return
+        if int(idx.max()) >= self.pool_bufs or not self._held[idx].all() or np.unique(idx).size != idx.size:
+            raise ValueError("release takes indices of held buffers, each once")
+        self._held[idx] = False
+        self._free = np.sort(np.concatenate([self._free, idx]))
+
+    def close(self):
+        for b in (self.host, self._h_idx, self._h_len, self._h_blk, self._h_status, self._h_l4):
+            b.free()

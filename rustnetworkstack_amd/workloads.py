@@ -523,6 +523,11 @@ class RxChainBatch:
         self.d_off = torch.from_numpy(lay.frag_off.view(np.int64)).to(self.device)
         self.d_len = torch.from_numpy(lay.frag_len.view(np.int32)).to(self.device)
         self.d_first = torch.from_numpy(lay.first.view(np.int32)).to(self.device)
+        # the same chains in the pool form (rns_rx_verify_pool_dev): buffer indices, u16 lengths, the
+        # first fragment of every 64th datagram
+        self.d_buf_idx = torch.from_numpy(lay.buf.astype(np.uint32).view(np.int32)).to(self.device)
+        self.d_len16 = torch.from_numpy(lay.flat.length.astype(np.uint16)).to(self.device)
+        self.d_blk_first = torch.from_numpy(np.ascontiguousarray(lay.first[:-1:64]).view(np.int32)).to(self.device)
         self.status = torch.empty(lay.n, dtype=torch.uint8, device=self.device)
         self.l4_sum = torch.empty(lay.n, dtype=torch.uint16, device=self.device)
         ok = _lib.RNS_RX_IP_OK | _lib.RNS_RX_L4_OK | _lib.RNS_RX_ACCEPT

@@ -1,0 +1,392 @@
+"""Receive verify of datagrams in fixed-size pool buffers (rns_rx_verify_pool_dev /
+batch.rx_verify_pool) on the GPU.  Status bytes and L4 values are compared exactly with the chain
+restatement (tests/rx_chain_helper.py over recv_packet's chains) and with rns_rx_verify_chain_dev on
+the CSR chains the compact form expands to, over the same pool tensor.  Every call also checks that
+the pool is unchanged."""
+import socket
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import oracle as O
+from rustnetworkstack_amd import _lib
+from rustnetworkstack_amd.batch import recv_batch_pool, rx_pool_layout, rx_verify_chain, rx_verify_pool
+from rustnetworkstack_amd.pipeline import RxPoolPipeline
+from rustnetworkstack_amd.workloads import LOCAL4, LOCAL6, RxChainBatch
+from rx_chain_helper import make_datagrams, netbuffers, rx_verify_chain_ref
+from test_rx_oracle import L4, L6, R4, R6, ipv4, ipv6, tcp_seg
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+MAL = O.RX_MALFORMED
+BUFS = (64, 512, 2048)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def gpu_present():
+    if not torch.cuda.is_available() or _lib.load().rns_device_count() == 0:
+        pytest.fail("gpu tests need a GPU (the HIP path has no CPU fallback)")
+
+
+def dev(a, view):
+    return torch.from_numpy(np.ascontiguousarray(a).view(view)).to(DEV)
+
+
+def lay_pool(pkts, buf, shuffled=False, seed=1, spare=3):
+    """The datagrams in a pool of buf-byte buffers as recv_packet leaves them: (pool uint8, buf_idx
+    uint32, blk_first uint32, len16 uint16); buffers in order or a seeded permutation, `spare`
+    unused ones among them, the unused bytes random."""
+    len16 = np.array([len(p) for p in pkts], dtype=np.uint16)
+    blk_first, first, nf = rx_pool_layout(len16, buf)
+    nbuf = nf + spare
+    order = np.random.default_rng(seed).permutation(nbuf) if shuffled else np.arange(nbuf)
+    idx = order[:nf].astype(np.uint32)
+    pool = np.frombuffer(O.splitmix64_bytes(seed ^ 0x9001, nbuf * buf).tobytes(), dtype=np.uint8).copy()
+    rows = pool.reshape(nbuf, buf)
+    for i, p in enumerate(pkts):
+        for j, f in enumerate(netbuffers(p, buf)):
+            rows[idx[first[i] + j], :len(f)] = np.frombuffer(f, dtype=np.uint8)
+    return pool, idx, blk_first, len16
+
+
+def expand(idx, blk_first, len16, buf, n_frags=None):
+    """The CSR chains the compact form means (rns_checksum.h): (frag_off uint64, frag_len uint32,
+    first uint32).  A datagram whose range runs past n_frags gets no fragments (both forms call it
+    malformed)."""
+    n_frags = idx.size if n_frags is None else n_frags
+    nfr = -(-len16.astype(np.int64) // buf)
+    off, ln, first = [], [], [0]
+    for i in range(len16.size):
+        b = i // 64 * 64
+        f0 = int(blk_first[i // 64]) + int(nfr[b:i].sum())
+        if f0 + nfr[i] <= n_frags:
+            for j in range(int(nfr[i])):
+                off.append(int(idx[f0 + j]) * buf)
+                ln.append(min(buf, int(len16[i]) - j * buf))
+        first.append(len(off))
+    return np.array(off, dtype=np.uint64), np.array(ln, dtype=np.uint32), np.array(first, dtype=np.uint32)
+
+
+def u16(t):
+    return t.view(torch.int16).cpu().numpy().view(np.uint16)
+
+
+def run(pool, idx, blk_first, len16, buf, d_pool=None, pool_bytes=None, n_frags=None, chain=True):
+    """rx_verify_pool over host descriptors: (status uint8, l4 uint16).  The pool is only read, and
+    rx_verify_chain on the expanded chains over the same pool tensor gives the same two arrays."""
+    d_pool = torch.from_numpy(pool).to(DEV) if d_pool is None else d_pool
+    view = d_pool if pool_bytes is None else d_pool[:pool_bytes]
+    n = len16.size
+    d_idx = dev(idx.astype(np.uint32), np.int32)[:idx.size if n_frags is None else n_frags]
+    l4 = torch.full((n,), 0x5555, dtype=torch.uint16, device=DEV)
+    st, out = rx_verify_pool(view, d_idx, dev(blk_first.astype(np.uint32), np.int32), dev(len16, np.int16), L4, L6,
+                             buf_bytes=buf, l4_sum=l4)
+    torch.cuda.synchronize()
+    assert out is l4
+    got = st.cpu().numpy(), u16(l4)
+    if pool is not None:
+        assert np.array_equal(d_pool.cpu().numpy(), pool), "the pool changed"
+    if chain:
+        off, ln, first = expand(idx, blk_first, len16, buf, n_frags)
+        l4c = torch.full((n,), 0x3333, dtype=torch.uint16, device=DEV)
+        stc, _ = rx_verify_chain(view, dev(off, np.int64), dev(ln, np.int32), dev(first, np.int32), L4, L6, l4_sum=l4c)
+        torch.cuda.synchronize()
+        same(got, (stc.cpu().numpy(), u16(l4c)), len16, "rx_verify_chain")
+    return got
+
+
+def expect(pkts, buf, oracle):
+    w = [rx_verify_chain_ref(netbuffers(p, buf), L4, L6, ones_comp=oracle.compute_ones_comp) for p in pkts]
+    return np.array([x[0] for x in w], dtype=np.uint8), np.array([x[1] for x in w], dtype=np.uint16)
+
+
+def same(got, want, len16, ref="rx_verify_chain_ref"):
+    for g, w, what in zip(got, want, ("status", "l4")):
+        bad = np.flatnonzero(g != w)
+        assert bad.size == 0, (ref, what, [(int(i), hex(int(g[i])), hex(int(w[i])), int(len16[i])) for i in bad[:8]])
+
+
+# 1. every kind of datagram ------------------------------------------------------------------
+NS = (1, 63, 64, 65, 129, 700)
+
+
+@pytest.fixture(scope="module")
+def kinds(oracle):
+    pkts = make_datagrams(max(NS), 0x9001)
+    return pkts, {buf: expect(pkts, buf, oracle) for buf in BUFS}
+
+
+@pytest.mark.parametrize("shuffled", [False, True])
+@pytest.mark.parametrize("n", NS)
+@pytest.mark.parametrize("buf", BUFS)
+def test_parity(kinds, buf, n, shuffled):
+    pkts, want = kinds
+    assert n < 14 * 22 or len(set(want[buf][0][:n].tolist())) >= 7
+    pool, idx, blk, len16 = lay_pool(pkts[:n], buf, shuffled, seed=n)
+    same(run(pool, idx, blk, len16, buf), (want[buf][0][:n], want[buf][1][:n]), len16)
+
+
+# 2. lengths around the boundaries --------------------------------------------------------------
+def exact(L, fam, i):
+    """A TCP datagram of exactly L bytes (IPv4 IHL 5, IPv4 IHL 15, IPv6), or a longer one cut to L."""
+    hdr = (20, 60, 40)[fam]
+    body = O.splitmix64_bytes(0xE0 + i, max(L, 1)).tobytes()
+    build = (lambda seg: ipv4(6, seg), lambda seg: ipv4(6, seg, ihl=15), lambda seg: ipv6(6, seg))[fam]
+    ends = (R4, L4) if fam < 2 else (R6, L6)
+    if L >= hdr + 20:
+        p = build(tcp_seg(*ends, body[:L - hdr - 20]))
+    else:
+        p = build(tcp_seg(*ends, body[:64]))[:L]
+    assert len(p) == L
+    return p
+
+
+@pytest.mark.parametrize("buf", BUFS)
+def test_edge_lengths(oracle, buf):
+    pkts = []
+    for L in (0, 1, 19, 20, 39, 40, buf - 1, buf, buf + 1, 2 * buf, 2 * buf + 1):
+        for fam in range(3):
+            p = exact(L, fam, len(pkts))
+            pkts.append(p)
+            spots = {min(9, L - 1), L - 1} if L else set()     # the head buffer, the last buffer's last byte
+            if L > 2 * buf:
+                spots.add(buf + 7)                               # a middle buffer
+            for s in sorted(spots):
+                q = bytearray(p)
+                q[s] ^= 0x10
+                pkts.append(bytes(q))
+    want = expect(pkts, buf, oracle)
+    assert {MAL, O.RX_IP_OK, O.RX_IP_OK | O.RX_L4_OK | O.RX_ACCEPT} <= set(want[0].tolist())
+    for shuffled in (False, True):
+        pool, idx, blk, len16 = lay_pool(pkts, buf, shuffled, seed=buf)
+        same(run(pool, idx, blk, len16, buf), want, len16)
+
+
+# 3. the longest datagrams ----------------------------------------------------------------------
+def test_max_length(oracle, kinds):
+    """65535 bytes in 64-byte buffers: 1024 fragments each, a wave's fragment range over many passes."""
+    v4 = ipv4(6, tcp_seg(R4, L4, O.splitmix64_bytes(0x44, 65535 - 40).tobytes()))
+    v6 = ipv6(6, tcp_seg(R6, L6, O.splitmix64_bytes(0x66, 65535 - 60).tobytes()))
+    bad = bytearray(v6)
+    bad[65534] ^= 1
+    pkts = list(kinds[0][:150])
+    pkts[7], pkts[70], pkts[71] = v4, v6, bytes(bad)
+    assert len(v4) == len(v6) == 65535
+    want = expect(pkts, 64, oracle)
+    ok = O.RX_IP_OK | O.RX_L4_OK | O.RX_ACCEPT
+    assert want[0][7] == ok and want[0][70] == ok and want[0][71] == O.RX_IP_OK
+    for shuffled in (False, True):
+        pool, idx, blk, len16 = lay_pool(pkts, 64, shuffled, seed=5)
+        same(run(pool, idx, blk, len16, 64), want, len16)
+
+
+# 4. the workload batches -------------------------------------------------------------------------
+@pytest.mark.parametrize("shuffled", [False, True])
+@pytest.mark.parametrize("config,n", [("c3_1500B", 2 ** 16), ("c5_imix", 2 ** 17)])
+def test_workload_batches(config, n, shuffled):
+    rb = RxChainBatch(config, DEV, n=n, shuffled=shuffled)
+    st, l4 = rx_verify_pool(rb.arena, rb.d_buf_idx, rb.d_blk_first, rb.d_len16, LOCAL4, LOCAL6, l4_sum=rb.l4_sum)
+    torch.cuda.synchronize()
+    got = st.cpu().numpy(), u16(l4)
+    l4c = torch.empty_like(rb.l4_sum)
+    stc, _ = rx_verify_chain(rb.arena, rb.d_off, rb.d_len, rb.d_first, LOCAL4, LOCAL6, l4_sum=l4c)
+    torch.cuda.synchronize()
+    len16 = rb.d_len16.view(torch.int16).cpu().numpy().view(np.uint16)
+    same(got, (stc.cpu().numpy(), u16(l4c)), len16, "rx_verify_chain")
+    assert np.array_equal(got[0], rb.expected_status)
+
+
+# 5. rejections that touch one datagram only ------------------------------------------------------
+def test_rejections(oracle, kinds):
+    buf = 512
+    pkts = [p for p in kinds[0][:200] if len(p) >= 40][:130]
+    pkts[3] = exact(1300, 0, 3)                                  # three buffers
+    pkts[64] = exact(700, 2, 64)
+    want = expect(pkts, buf, oracle)
+    pool, idx, blk, len16 = lay_pool(pkts, buf, shuffled=True, seed=77, spare=0)
+    _, first, nf = rx_pool_layout(len16, buf)
+    same(run(pool, idx, blk, len16, buf), want, len16)
+
+    def only(i_bad, got):
+        assert (got[0][i_bad] == MAL).all() and (got[1][i_bad] == 0).all()
+        keep = np.ones(len(pkts), dtype=bool)
+        keep[i_bad] = False
+        same((got[0][keep], got[1][keep]), (want[0][keep], want[1][keep]), len16[keep])
+
+    for j in (0, 1, 2):                                          # an index past the pool: head, middle, last
+        bent = idx.copy()
+        bent[first[3] + j] = nf + 5
+        only([3], run(pool, bent, blk, len16, buf))
+    bent = idx.copy()
+    bent[first[3]] = 0xFFFFFFFF                                  # the offset needs more than 32 bits
+    only([3], run(pool, bent, blk, len16, buf))
+    # the pool ends exactly at, and one byte before, the end of the last fragment of datagram 3
+    last = nf - 1                                                # the highest buffer
+    owner = int(np.flatnonzero(idx == last)[0])
+    i_own = int(np.searchsorted(first, owner, side="right") - 1)
+    if owner == first[i_own + 1] - 1 and len16[i_own] % buf:     # it is a partly filled last fragment
+        end = last * buf + int(len16[i_own]) % buf
+    else:
+        end = (last + 1) * buf
+    same(run(pool, idx, blk, len16, buf, pool_bytes=end), want, len16)
+    only([i_own], run(pool, idx, blk, len16, buf, pool_bytes=end - 1))
+    # a block entry that pushes the block's last datagrams past n_frags
+    bent = blk.copy()
+    tail = int(first[130] - first[128])
+    bent[2] = nf - tail + 1
+    got = run(pool, idx, bent, len16, buf)
+    assert got[0][129] == MAL and got[1][129] == 0
+    same((got[0][:128], got[1][:128]), (want[0][:128], want[1][:128]), len16[:128])
+    bent[2] = 0xFFFFFFF0                                         # ... and one near 2^32
+    got = run(pool, idx, bent, len16, buf)
+    assert (got[0][128:] == MAL).all() and (got[1][128:] == 0).all()
+    same((got[0][:128], got[1][:128]), (want[0][:128], want[1][:128]), len16[:128])
+    # n_frags cut short: the last datagram loses its range
+    got = run(pool, idx, blk, len16, buf, n_frags=nf - 1)
+    only([129], got)
+    # two datagrams sharing their buffers: nothing is written, both get datagram 3's verdict
+    share = idx.copy()
+    share[first[64]:first[64] + 2] = idx[first[3]:first[3] + 2]
+    l2 = len16.copy()
+    l2[64] = 1000
+    got = run(pool, share, blk, l2, buf)
+    w64 = rx_verify_chain_ref(netbuffers(pkts[3][:1000], buf), L4, L6, ones_comp=oracle.compute_ones_comp)
+    assert (int(got[0][64]), int(got[1][64])) == w64 and got[0][3] == want[0][3] and got[1][3] == want[1][3]
+
+
+# 6. optional outputs ------------------------------------------------------------------------------
+def test_optional_outputs(kinds):
+    pkts, want = kinds
+    n, buf = 300, 512
+    pool, idx, blk, len16 = lay_pool(pkts[:n], buf, shuffled=True, seed=6)
+    d_pool = torch.from_numpy(pool).to(DEV)
+    args = (d_pool, dev(idx, np.int32), dev(blk, np.int32), dev(len16, np.int16), L4, L6)
+    st, none = rx_verify_pool(*args)                             # d_l4_sum NULL
+    torch.cuda.synchronize()
+    assert none is None and np.array_equal(st.cpu().numpy(), want[buf][0][:n])
+    status = torch.full((n,), 0xEE, dtype=torch.uint8, device=DEV)
+    out, _ = rx_verify_pool(*args, status=status)
+    torch.cuda.synchronize()
+    assert out is status and np.array_equal(status.cpu().numpy(), want[buf][0][:n])
+    with pytest.raises(ValueError):
+        rx_verify_pool(*args, status=torch.zeros(n + 1, dtype=torch.uint8, device=DEV))
+    with pytest.raises(ValueError):
+        rx_verify_pool(*args, buf_bytes=500)
+    with pytest.raises(ValueError):
+        rx_verify_pool(d_pool[8:], *args[1:])                    # not 16-byte aligned
+    with pytest.raises(ValueError):
+        rx_verify_pool(args[0], args[1], args[2][:4], *args[3:])  # too few block entries
+    with pytest.raises(TypeError):
+        rx_verify_pool(args[0], args[1].to(torch.int64), *args[2:])
+    with pytest.raises(ValueError, match="no CPU fallback"):
+        rx_verify_pool(args[0], args[1].cpu(), *args[2:])
+    e = rx_verify_pool(d_pool, dev(idx[:0], np.int32), dev(blk[:0], np.int32), dev(len16[:0], np.int16), L4, L6)
+    assert e[0].numel() == 0
+
+
+# 7. a pool just over 4 GiB ----------------------------------------------------------------------
+def test_pool_past_4gib(oracle, kinds):
+    """The 64-bit-address instantiation: buffers below, on both sides of and above the 4 GiB line —
+    passes inside one buffer window — and a wave whose buffers alternate between the pool's start
+    and its end (a pass spanning more than 4 GiB: 64-bit loads)."""
+    buf = 512
+    nbuf = (1 << 32) // buf + 4096
+    try:
+        big = torch.empty(nbuf * buf, dtype=torch.uint8, device=DEV)
+    except RuntimeError as e:  # out of memory
+        pytest.skip(f"no room for a pool past 4 GiB: {e}")
+    rows = big.view(nbuf, buf)
+    try:
+        pkts = kinds[0][:220]
+        want = (kinds[1][buf][0][:220], kinds[1][buf][1][:220])
+        len16 = np.array([len(p) for p in pkts], dtype=np.uint16)
+        blk, first, nf = rx_pool_layout(len16, buf)
+        line = (1 << 32) // buf
+        layouts = {
+            "straddling": line - nf // 2 + np.arange(nf),                       # consecutive indices across the line
+            "above": line + 100 + np.random.default_rng(3).permutation(nf),
+            "spread": np.where(np.arange(nf) % 2 == 0, 8 + np.arange(nf), nbuf - 1 - np.arange(nf)),
+        }
+        for name, where in layouts.items():
+            idx = where.astype(np.uint32)
+            assert name != "straddling" or ((idx < line).any() and (idx >= line).any())
+            host = np.zeros((nf, buf), dtype=np.uint8)
+            for i, p in enumerate(pkts):
+                for j, f in enumerate(netbuffers(p, buf)):
+                    host[first[i] + j, :len(f)] = np.frombuffer(f, dtype=np.uint8)
+            rows[torch.from_numpy(idx.astype(np.int64)).to(DEV)] = torch.from_numpy(host).to(DEV)
+            same(run(None, idx, blk, len16, buf, d_pool=big), want, len16)
+            torch.cuda.synchronize()
+            back = rows[torch.from_numpy(idx.astype(np.int64)).to(DEV)].cpu().numpy()
+            assert np.array_equal(back, host), "the pool changed"
+    finally:
+        del big, rows
+        torch.cuda.empty_cache()
+
+
+# 8. socket -> pool -> verdicts ----------------------------------------------------------------------
+def test_recv_batch_pool_to_verdict(oracle):
+    pkts = [p for p in make_datagrams(14 * 12, 0xE2F, max_body=1900) if 0 < len(p) <= 2048]
+    a, b = socket.socketpair(socket.AF_UNIX, socket.SOCK_DGRAM)
+    try:
+        a.setsockopt(socket.SOL_SOCKET, socket.SO_SNDBUF, 1 << 20)
+        a.setblocking(False)  # a full queue fails the test at once
+        for p in pkts:
+            a.send(p)
+        nbuf = 4 * len(pkts) + 4
+        pool = np.zeros(nbuf * 512, dtype=np.uint8)
+        free = np.random.default_rng(9).permutation(nbuf).astype(np.uint32)
+        n, len16, blk, nf = recv_batch_pool(b.fileno(), pool, free, timeout_ms=1000)
+    finally:
+        a.close()
+        b.close()
+    assert n == len(pkts) and [int(x) for x in len16] == [len(p) for p in pkts]
+    same(run(pool, free[:nf], blk, len16, 512), expect(pkts, 512, oracle), len16)
+
+
+def test_pipeline(oracle):
+    pkts = [p for p in make_datagrams(14 * 9, 0xE30, max_body=1900) if 0 < len(p) <= 2048]
+    half = len(pkts) // 2
+    first, second = pkts[:half], pkts[half:half + 10]
+    spare = 4                                                    # a datagram is offered mru / 512 = 4 buffers
+    pool_bufs = sum(len(netbuffers(p)) for p in first) + spare
+    a, b = socket.socketpair(socket.AF_UNIX, socket.SOCK_DGRAM)
+    pipe = RxPoolPipeline(L4, L6, pool_bufs=pool_bufs, max_pkts=256)
+    try:
+        a.setsockopt(socket.SOL_SOCKET, socket.SO_SNDBUF, 1 << 20)
+        a.setblocking(False)
+        assert pipe.receive(b.fileno(), timeout_ms=0)[0].size == 0 and pipe.h2d_bytes == 0
+
+        def batch(sent):
+            for p in sent:
+                a.send(p)
+            st, l4, chains = pipe.receive(b.fileno(), timeout_ms=1000)
+            assert len(chains) == len(sent)
+            same((st, l4), expect(sent, 512, oracle), np.array([len(p) for p in sent]))
+            used = np.concatenate([chains[i][0] for i in range(len(sent))])
+            assert [chains[i][1] for i in range(len(sent))] == [len(p) for p in sent]
+            assert [chains.bytes(i) for i in range(len(sent))] == sent
+            assert pipe.h2d_bytes == (int(used.max()) + 1 - int(used.min())) * 512
+            assert pipe.desc_bytes == 4 * used.size + 2 * len(sent) + 4 * ((len(sent) + 63) // 64)
+            return chains, used
+
+        c1, used1 = batch(first)
+        assert np.unique(used1).size == used1.size == pool_bufs - spare and pipe.free_bufs == spare
+        # every other datagram of the first batch is released, the rest stay held across the next call
+        keep = [i for i in range(half) if i % 2]
+        gone = np.concatenate([c1[i][0] for i in range(half) if i % 2 == 0])
+        held = np.concatenate([c1[i][0] for i in keep])
+        pipe.release(gone)
+        with pytest.raises(ValueError):
+            pipe.release(gone[:1])                               # not held any more
+        c2, used2 = batch(second)                                # needs more than the spare buffers
+        assert used2.size > spare and set(used2.tolist()) & set(gone.tolist())  # released buffers are reused,
+        assert not set(used2.tolist()) & set(held.tolist())     # held ones are not,
+        assert [c1.bytes(i) for i in keep] == [first[i] for i in keep]  # and their bytes are intact,
+        dpool = pipe.d_pool.cpu().numpy().reshape(-1, 512)
+        assert np.array_equal(dpool[held], pipe.host.array.reshape(-1, 512)[held])  # on the device too
+    finally:
+        a.close()
+        b.close()
+        pipe.close()

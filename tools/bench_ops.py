@@ -27,6 +27,10 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              order and shuffled; next to it csum_chain, rns_csum_chain_dev over the same chains of the
              same arena (the yardstick: an entry that reads the same bytes), timed in alternating
              rounds, both rows carrying every round's time
+* rx_verify_pool — rns_rx_verify_pool_dev: the same receive verify of the same pools over the compact
+             descriptors (a u32 buffer index per fragment, a u16 length per datagram, one u32 per 64
+             datagrams), next to rns_rx_verify_chain_dev over the CSR chains (the yardstick), in
+             alternating rounds; statuses and L4 values are compared before timing
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -144,6 +148,9 @@ def main():
         if "rx_verify_chain" in ops:
             for shuffled in (False, True):
                 r.update(bench_rx_chain(cfg, dev, args, shuffled))
+        if "rx_verify_pool" in ops:
+            for shuffled in (False, True):
+                r.update(bench_rx_pool(cfg, dev, args, shuffled))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -356,6 +363,47 @@ def bench_rx_chain(cfg, dev, args, shuffled):
     rxr["accepted"] = int((st == 0x43).sum())
     rxr["statuses_as_expected"] = as_expected
     rxr["ratio_to_csum_chain"] = round(rs_rx[len(rs_rx) // 2] / rs_cs[len(rs_cs) // 2], 4)
+    del rb
+    torch.cuda.empty_cache()
+    return res
+
+
+def bench_rx_pool(cfg, dev, args, shuffled):
+    """Receive verify over the compact pool descriptors and over the CSR chains of the same pool, in
+    alternating rounds."""
+    from rustnetworkstack_amd.batch import rx_verify_chain, rx_verify_pool
+    from rustnetworkstack_amd.workloads import LOCAL4, LOCAL6, RxChainBatch
+    rb = RxChainBatch(cfg, dev, shuffled=shuffled)
+    n, pay, nf = rb.n, rb.payload_bytes, rb.n_frags
+    st_c, l4_c = torch.empty_like(rb.status), torch.empty_like(rb.l4_sum)
+    pool = lambda: rx_verify_pool(rb.arena, rb.d_buf_idx, rb.d_blk_first, rb.d_len16, LOCAL4, LOCAL6,  # noqa: E731
+                                  buf_bytes=rb.layout.buf_bytes, status=rb.status, l4_sum=rb.l4_sum)
+    chain = lambda: rx_verify_chain(rb.arena, rb.d_off, rb.d_len, rb.d_first, LOCAL4, LOCAL6,  # noqa: E731
+                                    status=st_c, l4_sum=l4_c)
+    pool()
+    chain()
+    torch.cuda.synchronize()
+    st = rb.status.cpu().numpy()
+    as_expected = bool(np.array_equal(st, rb.expected_status))
+    equal = bool(torch.equal(rb.status, st_c)) and bool(torch.equal(rb.l4_sum.view(torch.int16), l4_c.view(torch.int16)))
+    rs_p, rs_c = timed_rounds([pool, chain], args.steps, args.rounds)
+
+    def row(rs, desc_bytes):
+        ms = rs[len(rs) // 2]
+        return {"us": round(ms * 1e3, 1), "GBps": round((pay + 3 * n) / ms / 1e6, 1), "packets": n, "fragments": nf,
+                "rounds_us": [round(x * 1e3, 1) for x in rs], "spread_us": round((rs[-1] - rs[0]) * 1e3, 1),
+                "descriptor_bytes_per_datagram": round(desc_bytes / n, 2)}
+
+    tag = "_shuffled" if shuffled else ""
+    res = {"rx_verify_pool" + tag: row(rs_p, 4 * nf + 2 * n + 4 * ((n + 63) // 64)),
+           "rx_verify_chain" + tag: row(rs_c, 12 * nf + 4 * (n + 1))}
+    pr = res["rx_verify_pool" + tag]
+    pr["accepted"] = int((st == 0x43).sum())
+    pr["statuses_as_expected"] = as_expected
+    pr["status_and_l4_equal_chain"] = equal
+    med_p, med_c = rs_p[len(rs_p) // 2], rs_c[len(rs_c) // 2]
+    pr["ratio_to_rx_verify_chain"] = round(med_p / med_c, 4)
+    pr["within_chain_median_plus_spread"] = bool(med_p <= med_c + max(rs_c[-1] - rs_c[0], rs_p[-1] - rs_p[0]))
     del rb
     torch.cuda.empty_cache()
     return res

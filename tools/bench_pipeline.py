@@ -5,7 +5,9 @@ Receive (default): a sender thread writes N valid IPv4/TCP datagrams (1500 B, or
 with --config c2_64B; sendmmsg); the receiver runs RxPipeline until all arrived — packed
 (rns_io_recv_batch_packed: recvmmsg into a packed pinned arena -> H2D of the used bytes ->
 rns_rx_verify_packed_dev -> verdicts D2H), or with --slots the round-5 form (2048-B slots ->
-H2D of whole slots -> rns_rx_verify_dev).
+H2D of whole slots -> rns_rx_verify_dev), or with --pool into 512-byte pool buffers as recv_packet
+does (RxPoolPipeline: rns_io_recv_batch_pool -> H2D of the buffers' covering span and the compact
+descriptors -> rns_rx_verify_pool_dev; every batch's buffers are released at once).
 Transmit (--tx): the same datagrams with their checksum fields zeroed are placed in
 TxPipeline's pinned slots and sent (H2D -> rns_tx_fill_dev -> header bytes D2H ->
 rns_io_send_batch); a drain thread reads them and the result is spot-checked.
@@ -35,7 +37,7 @@ import torch  # noqa: E402
 
 from rustnetworkstack_amd.batch import send_batch  # noqa: E402
 from rustnetworkstack_amd.batch import recv_batch  # noqa: E402
-from rustnetworkstack_amd.pipeline import RxPipeline, TxChainPipeline, TxPipeline  # noqa: E402
+from rustnetworkstack_amd.pipeline import RxPipeline, RxPoolPipeline, TxChainPipeline, TxPipeline  # noqa: E402
 from rustnetworkstack_amd.workloads import DeviceBatch, make_layout  # noqa: E402
 from bench_ops import L4, L6, write_ipv4_tcp_headers  # noqa: E402
 
@@ -51,6 +53,7 @@ def main():
     ap.add_argument("--compact", action="store_true",
                     help="with --tx --chain: TxChainPipeline(compact=True), the compact descriptors on the device path")
     ap.add_argument("--slots", action="store_true", help="receive into 2048-B slots (round-5 form)")
+    ap.add_argument("--pool", action="store_true", help="receive into 512-byte pool buffers (RxPoolPipeline; no --overlap)")
     ap.add_argument("--config", default="c3_1500B", help="datagram sizes: c3_1500B or c2_64B")
     args = ap.parse_args()
     if args.tx:
@@ -64,12 +67,13 @@ def main():
     a, r = socket.socketpair(socket.AF_UNIX, socket.SOCK_SEQPACKET)
     for s_, opt in ((a, socket.SO_SNDBUF), (r, socket.SO_RCVBUF)):
         s_.setsockopt(socket.SOL_SOCKET, opt, 64 << 20)
-    pipe = RxPipeline(L4, L6, device=0, max_pkts=args.batch, packed=not args.slots)
+    pipe = RxPoolPipeline(L4, L6, device=0, max_pkts=args.batch) if args.pool else \
+        RxPipeline(L4, L6, device=0, max_pkts=args.batch, packed=not args.slots)
     sender = threading.Thread(target=send_batch, args=(a.fileno(), arena, lay.off, lay.length))
     t0 = time.perf_counter()
     sender.start()
-    got = accepted = batches = 0
-    if args.overlap:
+    got = accepted = batches = pool_h2d = 0
+    if args.overlap and not args.pool:
         for st, ln, _ in pipe.stream(r.fileno(), timeout_ms=5000):
             got += st.shape[0]
             accepted += int((st == 0x43).sum())
@@ -77,7 +81,12 @@ def main():
             if got >= lay.n:
                 break
     while got < lay.n:
-        st, ln = pipe.receive(r.fileno(), timeout_ms=5000)
+        if args.pool:
+            st, _, chains = pipe.receive(r.fileno(), timeout_ms=5000)
+            pipe.release(chains.idx)
+            pool_h2d += pipe.h2d_bytes + pipe.desc_bytes
+        else:
+            st, ln = pipe.receive(r.fileno(), timeout_ms=5000)
         if st.shape[0] == 0:
             break
         got += st.shape[0]
@@ -88,10 +97,13 @@ def main():
     size = int(lay.length[0])
     res = {"packets": lay.n, "datagram_bytes": size, "received": got, "accepted": accepted, "batches": batches,
            "seconds": round(dt, 3), "packets_per_s": round(got / dt), "GBps": round(got * size / dt / 1e9, 3),
-           "h2d_bytes_per_datagram": round(pipe.h2d_bytes / max(pipe.datagrams, 1), 1),
-           "overlap": args.overlap, "packed": not args.slots,
+           "h2d_bytes_per_datagram": round(pool_h2d / max(got, 1) if args.pool else
+                                           pipe.h2d_bytes / max(pipe.datagrams, 1), 1),
+           "overlap": args.overlap and not args.pool, "packed": not (args.slots or args.pool), "pool": args.pool,
            "path": ("AF_UNIX SOCK_SEQPACKET socketpair (TUN-like; sendmmsg) -> " +
-                    ("rns_io_recv_batch (recvmmsg into 2048-B slots, pinned) -> H2D of whole slots -> rns_rx_verify_dev"
+                    ("rns_io_recv_batch_pool (recvmmsg into 512-byte pool buffers, pinned) -> H2D of the buffers' "
+                     "covering span + compact descriptors -> rns_rx_verify_pool_dev" if args.pool else
+                     "rns_io_recv_batch (recvmmsg into 2048-B slots, pinned) -> H2D of whole slots -> rns_rx_verify_dev"
                      if args.slots else
                      "rns_io_recv_batch_packed (recvmmsg, 16-byte packing, pinned) -> H2D of the used bytes -> "
                      "rns_rx_verify_packed_dev") + " -> status D2H; sender on another host thread")}
