@@ -431,6 +431,45 @@ int rns_tx_fill_chain_packed_dev(uint8_t *d_arena, uint64_t arena_bytes,
                                  uint32_t pay_align_log2,        /* payloads start at 2^this boundaries, 4..12 */
                                  uint32_t n, uint8_t *d_status, void *stream);
 
+/* The same finalize for datagrams held in POOL BUFFERS as the reference's transmit path leaves them
+ * — append_from_slice (buf.rs:385-420) fills whole buffers from offset 0 and a last one with the
+ * remainder, alloc_header (buf.rs:262-291) prepends a buffer whose data sits at its end — over the
+ * compact descriptors of rns_rx_verify_pool_dev.  d_pool (16-byte aligned) holds buffers of
+ * 2^buf_log2 bytes (8 <= buf_log2 <= 15, so every u8 head length fits a buffer; the reference's
+ * FRAGMENT_SIZE is 2^9), buffer k = d_pool[k << buf_log2 .. ).  Datagram i names
+ * nf_i = 1 + ceil(pay_len_i / 2^buf_log2) buffers, d_buf_idx[first_i .. first_i + nf_i), with first_i
+ * = d_blk_first[i / 64] + the sum of nf_k over the datagrams k of i's 64-datagram block before i
+ * (the blocks' entries are independent of each other).  The first is the head buffer: the head
+ * fragment is its LAST head_len_i bytes, offset (idx << buf_log2) + 2^buf_log2 - head_len_i.  The
+ * others are payload buffers read from their start, all full but the last, which holds the
+ * remainder.  Descriptors: 3 B per datagram + 4 B per buffer + 4 B per 64 datagrams — 19 B for a
+ * 1500-byte datagram in 512-byte buffers against the CSR form's 52 B.
+ * The form is defined by the CSR chain it expands to: the bytes stored and d_status[i] (optional)
+ * are exactly what rns_tx_fill_chain_dev gives for that chain on the same memory — the head's L4
+ * part folded as a fragment of its own (an odd length zero-padded), head_len 0 or a head that does
+ * not hold its IP header RNS_TX_MALFORMED, no L4 fill for a field that runs past the head.  A
+ * datagram with a buffer whose used bytes end past pool_bytes, or with first_i + nf_i > n_frags, is
+ * RNS_TX_MALFORMED and untouched, that datagram only.  Only head bytes are written (at most the
+ * two 2-byte fields): a head buffer must not be named anywhere else in the batch; payload buffers
+ * may be shared between datagrams.  Heads of any length and alignment take the same path: there
+ * is no exact per-datagram loop.
+ * n_pkts == 0 is RNS_OK; buf_log2 outside 8..15, a NULL d_pool / d_blk_first / d_head_len8 /
+ * d_pay_len16, a NULL d_buf_idx with n_frags > 0, n_pkts > RNS_CHAIN_MAX_PACKETS or a d_pool that is
+ * not 16-byte aligned is RNS_E_INVALID, all before the device is touched. */
+int rns_tx_fill_pool_dev(uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2,
+                         const uint32_t *d_buf_idx, uint32_t n_frags,
+                         const uint32_t *d_blk_first,   /* (n_pkts + 63) / 64 entries */
+                         const uint8_t  *d_head_len8,   /* head length per datagram, 0..255 */
+                         const uint16_t *d_pay_len16,   /* payload length per datagram, 0 = head only */
+                         uint32_t n_pkts, uint8_t *d_status /* optional */, void *stream);
+
+/* Host helper for the pool transmit form (CPU only), rns_rx_pool_layout with the + 1 for the head
+ * buffer: from the n payload lengths, blk_first ((n + 63) / 64 entries), optionally first[0..n]
+ * (the CSR index of the expanded chains) and *n_frags.  RNS_E_INVALID if the fragment total does
+ * not fit 32 bits or buf_log2 is outside 8..15. */
+int rns_tx_pool_layout(const uint16_t *pay_len16, uint64_t n, uint32_t buf_log2,
+                       uint32_t *blk_first, uint32_t *first /* optional, n + 1 */, uint64_t *n_frags);
+
 /* Host helper for the compact chain form (CPU only): given the n head and payload lengths, the
  * payload alignment (4..12) and the first head's and first payload's offsets, writes the
  * (n + 63) / 64 block offsets of each region, the offsets just past the last head and the last
@@ -530,6 +569,16 @@ int rns_io_send_batch(int fd, const uint8_t *h_arena, const uint64_t *h_off, con
 #define RNS_IO_MAX_FRAGS 8u
 int rns_io_send_batch_chain(int fd, const uint8_t *h_arena, const uint64_t *h_frag_off, const uint32_t *h_frag_len,
                             const uint32_t *h_first, uint32_t n_pkts);
+
+/* rns_io_send_batch_chain fed from the compact form of rns_tx_fill_pool_dev (buffers of 2^buf_log2
+ * bytes, 8..15): datagram i goes out as one message gathered from the last h_head_len8[i] bytes of
+ * its head buffer and its payload buffers, all full but the last — sendmmsg on a socket fd, one
+ * writev per datagram on a TUN fd.  A datagram with more than RNS_IO_MAX_FRAGS fragments (the head
+ * included) or with a head length of 0 is RNS_E_INVALID before anything is sent.  Returns the
+ * datagrams sent. */
+int rns_io_send_batch_pool(int fd, const uint8_t *h_pool, uint32_t buf_log2, const uint32_t *h_buf_idx,
+                           const uint32_t *h_blk_first, const uint8_t *h_head_len8,
+                           const uint16_t *h_pay_len16, uint32_t n_pkts);
 
 /* Batched receive straight into a PACKED arena (the descriptor form of
  * rns_rx_verify_packed_dev): every queued datagram (after waiting up to timeout_ms for the

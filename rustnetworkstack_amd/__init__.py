@@ -4,7 +4,8 @@
 
 * ``util``      — the reference's `netstack::util` checksum surface, same names and errors;
 * ``batch``     — device-resident / host-resident batch API (torch tensors, numpy arrays);
-* ``pool``      — receive verify of pool-buffer chains over compact descriptors (also ``batch.*``);
+* ``pool``      — receive verify and transmit finalize of datagrams in pool buffers over compact
+                  descriptors (also ``batch.*``);
 * ``workloads`` — the synthetic packet batches BASELINE.json's configs name.
 """
 from . import _lib, util  # noqa: F401

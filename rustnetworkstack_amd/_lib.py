@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = (
     "rns_tx_fill_chain_dev",
     "rns_tx_fill_chain_packed_dev",
     "rns_tx_chain_packed_layout",
+    "rns_tx_fill_pool_dev",
+    "rns_tx_pool_layout",
     "rns_host_ctx_create",
     "rns_host_ctx_destroy",
     "rns_csum_batch_host",
@@ -80,6 +82,7 @@ EXPORTED_SYMBOLS = (
     "rns_io_recv_batch_packed",
     "rns_io_recv_batch_chain",
     "rns_io_recv_batch_pool",
+    "rns_io_send_batch_pool",
     "rns_host_alloc",
     "rns_host_free",
     "rns_fill_splitmix64_dev",
@@ -154,6 +157,8 @@ _SIGNATURES = {
     "rns_tx_fill_chain_packed_dev": (_int, [_vp, _u64, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
     "rns_tx_chain_packed_layout": (_int, [_vp, _vp, _u64, _u32, _u64, _u64, _vp, _vp, _vp, _vp,
                                           ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "rns_tx_fill_pool_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "rns_tx_pool_layout": (_int, [_vp, _u64, _u32, _vp, _vp, ctypes.POINTER(_u64)]),
     "rns_host_ctx_create": (_int, [_int, _u64, _u32, ctypes.POINTER(_vp)]),
     "rns_host_ctx_destroy": (_int, [_vp]),
     "rns_csum_batch_host": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _u32]),
@@ -168,6 +173,7 @@ _SIGNATURES = {
     "rns_io_recv_batch_chain": (_int, [_int, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, _vp, ctypes.POINTER(_u32),
                                        _int]),
     "rns_io_recv_batch_pool": (_int, [_int, _vp, _u32, _vp, _u32, _u32, _u32, _vp, _vp, ctypes.POINTER(_u32), _int]),
+    "rns_io_send_batch_pool": (_int, [_int, _vp, _u32, _vp, _vp, _vp, _vp, _u32]),
     "rns_host_alloc": (_int, [_u64, ctypes.POINTER(_vp)]),
     "rns_host_free": (_int, [_vp]),
     "rns_fill_splitmix64_dev": (_int, [_vp, _u64, _u64, _vp]),

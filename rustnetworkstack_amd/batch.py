@@ -800,9 +800,10 @@ def csum_batch_multi_dev(shards, *, complement: bool = False) -> None:
     _lib.check(_lib.load().rns_csum_batch_multi_dev(arr, len(shards), flags), "rns_csum_batch_multi_dev")
 
 
-# The pool-buffer receive path (pool.py builds on the checks above) is part of this module's
-# interface: batch.rx_pool_layout, batch.rx_verify_pool, batch.recv_batch_pool.
-_POOL_API = ("recv_batch_pool", "rx_pool_layout", "rx_verify_pool")
+# The pool-buffer receive and transmit paths (pool.py builds on the checks above) are part of this
+# module's interface: batch.rx_pool_layout, batch.rx_verify_pool, batch.recv_batch_pool,
+# batch.tx_pool_layout, batch.tx_fill_pool, batch.send_batch_pool.
+_POOL_API = ("recv_batch_pool", "rx_pool_layout", "rx_verify_pool", "send_batch_pool", "tx_fill_pool", "tx_pool_layout")
 
 
 def __getattr__(name):

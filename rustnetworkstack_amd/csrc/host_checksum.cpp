@@ -199,6 +199,30 @@ int rns_rx_pool_layout(const uint16_t *len16, uint64_t n, uint32_t buf_log2, uin
     return RNS_OK;
 }
 
+int rns_tx_pool_layout(const uint16_t *pay_len16, uint64_t n, uint32_t buf_log2, uint32_t *blk_first, uint32_t *first,
+                       uint64_t *n_frags)
+{
+    if ((n && (!pay_len16 || !blk_first)) || !n_frags || buf_log2 < 8 || buf_log2 > 15)
+        return RNS_E_INVALID;
+    const uint64_t m = (1ull << buf_log2) - 1;
+    uint64_t at = 0;
+    for (uint64_t i = 0; i < n; ++i) {
+        if (at > 0xFFFFFFFFull)  // an index the kernel could not name
+            return RNS_E_INVALID;
+        if ((i & 63) == 0)
+            blk_first[i >> 6] = static_cast<uint32_t>(at);
+        if (first)
+            first[i] = static_cast<uint32_t>(at);
+        at += 1 + ((static_cast<uint64_t>(pay_len16[i]) + m) >> buf_log2);  // the head buffer + ceil(pay / buffer bytes)
+    }
+    if (at > 0xFFFFFFFFull)
+        return RNS_E_INVALID;
+    if (first)
+        first[n] = static_cast<uint32_t>(at);
+    *n_frags = at;
+    return RNS_OK;
+}
+
 int rns_abi_version(void) { return RNS_ABI_VERSION; }
 
 const char *rns_strerror(int status)

@@ -206,6 +206,50 @@ int recv_chain_loop(int fd, uint8_t *h_pool, uint32_t buf_bytes, uint32_t *h_fre
     return (n == 0 && status) ? status : static_cast<int>(n);
 }
 
+// The send loop rns_io_send_batch_chain and rns_io_send_batch_pool share: frags(i, v) writes datagram
+// i's fragments (1..kChainIov, checked by the caller) into v and returns their number.  Sockets:
+// sendmmsg, each message one datagram's fragments; a TUN fd: one writev per datagram, like tun_send.
+template <class Frags>
+int send_chain_loop(int fd, uint32_t n_pkts, Frags frags)
+{
+    uint32_t i = 0;
+    bool sock = true;
+    while (sock && i < n_pkts) {
+        const unsigned k = n_pkts - i < kMmsg ? n_pkts - i : kMmsg;
+        struct mmsghdr mh[kMmsg];
+        struct iovec iov[kMmsg * kChainIov];
+        std::memset(mh, 0, sizeof(mh));
+        for (unsigned j = 0; j < k; ++j) {
+            struct iovec *v = iov + j * kChainIov;
+            mh[j].msg_hdr.msg_iovlen = frags(i + j, v);
+            mh[j].msg_hdr.msg_iov = v;
+        }
+        int w;
+        do {
+            w = sendmmsg(fd, mh, k, 0);
+        } while (w < 0 && errno == EINTR);
+        if (w < 0) {
+            if (errno == ENOTSOCK && i == 0) {
+                sock = false;
+                break;
+            }
+            return i ? static_cast<int>(i) : RNS_E_IO;
+        }
+        i += static_cast<uint32_t>(w);
+    }
+    for (; i < n_pkts; ++i) {
+        struct iovec v[kChainIov];
+        const uint32_t nf = frags(i, v);
+        ssize_t w;
+        do {
+            w = writev(fd, v, static_cast<int>(nf));
+        } while (w < 0 && errno == EINTR);
+        if (w < 0)
+            return i ? static_cast<int>(i) : RNS_E_IO;
+    }
+    return static_cast<int>(n_pkts);
+}
+
 }  // namespace
 
 extern "C" {
@@ -471,51 +515,54 @@ int rns_io_send_batch_chain(int fd, const uint8_t *h_arena, const uint64_t *h_fr
         if (f1 <= f0 || f1 - f0 > kChainIov || !h_frag_off || !h_frag_len)
             return RNS_E_INVALID;
     }
-    uint32_t i = 0;
-    bool sock = true;
-    while (sock && i < n_pkts) {  // sockets: sendmmsg, each message one datagram's fragments
-        const unsigned k = n_pkts - i < kMmsg ? n_pkts - i : kMmsg;
-        struct mmsghdr mh[kMmsg];
-        struct iovec iov[kMmsg * kChainIov];
-        std::memset(mh, 0, sizeof(mh));
-        for (unsigned j = 0; j < k; ++j) {
-            const uint32_t f0 = h_first[i + j], nf = h_first[i + j + 1] - f0;
-            struct iovec *v = iov + j * kChainIov;
-            for (uint32_t f = 0; f < nf; ++f) {
-                v[f].iov_base = const_cast<uint8_t *>(h_arena + h_frag_off[f0 + f]);
-                v[f].iov_len = h_frag_len[f0 + f];
-            }
-            mh[j].msg_hdr.msg_iov = v;
-            mh[j].msg_hdr.msg_iovlen = nf;
-        }
-        int w;
-        do {
-            w = sendmmsg(fd, mh, k, 0);
-        } while (w < 0 && errno == EINTR);
-        if (w < 0) {
-            if (errno == ENOTSOCK && i == 0) {
-                sock = false;
-                break;
-            }
-            return i ? static_cast<int>(i) : RNS_E_IO;
-        }
-        i += static_cast<uint32_t>(w);
-    }
-    for (; i < n_pkts; ++i) {  // a TUN fd: one writev per datagram over its fragments, like tun_send
+    const auto frags = [&](uint32_t i, struct iovec *v) {
         const uint32_t f0 = h_first[i], nf = h_first[i + 1] - f0;
-        struct iovec v[kChainIov];
         for (uint32_t f = 0; f < nf; ++f) {
             v[f].iov_base = const_cast<uint8_t *>(h_arena + h_frag_off[f0 + f]);
             v[f].iov_len = h_frag_len[f0 + f];
         }
-        ssize_t w;
-        do {
-            w = writev(fd, v, static_cast<int>(nf));
-        } while (w < 0 && errno == EINTR);
-        if (w < 0)
-            return i ? static_cast<int>(i) : RNS_E_IO;
-    }
-    return static_cast<int>(n_pkts);
+        return nf;
+    };
+    return send_chain_loop(fd, n_pkts, frags);
+}
+
+int rns_io_send_batch_pool(int fd, const uint8_t *h_pool, uint32_t buf_log2, const uint32_t *h_buf_idx,
+                           const uint32_t *h_blk_first, const uint8_t *h_head_len8, const uint16_t *h_pay_len16,
+                           uint32_t n_pkts)
+{
+    if (fd < 0 || buf_log2 < 8 || buf_log2 > 15 ||
+        (n_pkts && (!h_pool || !h_buf_idx || !h_blk_first || !h_head_len8 || !h_pay_len16)))
+        return RNS_E_INVALID;
+    if (n_pkts > static_cast<uint32_t>(INT_MAX))
+        n_pkts = static_cast<uint32_t>(INT_MAX);
+    const uint32_t bbytes = 1u << buf_log2, bmask = bbytes - 1u;
+    // every datagram first: a head (an empty one would read as end-of-stream on a SOCK_SEQPACKET peer)
+    // and at most kChainIov fragments, else nothing is sent
+    for (uint32_t i = 0; i < n_pkts; ++i)
+        if (h_head_len8[i] == 0 || 1u + ((h_pay_len16[i] + bmask) >> buf_log2) > kChainIov)
+            return RNS_E_INVALID;
+    // first_i = h_blk_first[i / 64] + the buffers of the datagrams before i in its block; the loop asks
+    // for the datagrams in ascending order with at most one step back (sendmmsg's short count), so the
+    // running index restarts from the block's entry when i is not the next one
+    uint32_t next = 0, at = 0;
+    const auto frags = [&](uint32_t i, struct iovec *v) {
+        if (i != next || (i & 63u) == 0) {
+            at = h_blk_first[i >> 6];
+            for (uint32_t k = i & ~63u; k < i; ++k)
+                at += 1u + ((h_pay_len16[k] + bmask) >> buf_log2);
+        }
+        const uint32_t hl = h_head_len8[i], pay = h_pay_len16[i], npf = (pay + bmask) >> buf_log2;
+        v[0].iov_base = const_cast<uint8_t *>(h_pool + (static_cast<uint64_t>(h_buf_idx[at]) << buf_log2) + (bbytes - hl));
+        v[0].iov_len = hl;
+        for (uint32_t f = 1; f <= npf; ++f) {
+            v[f].iov_base = const_cast<uint8_t *>(h_pool + (static_cast<uint64_t>(h_buf_idx[at + f]) << buf_log2));
+            v[f].iov_len = f < npf ? bbytes : pay - ((pay - 1u) & ~bmask);
+        }
+        at += 1u + npf;
+        next = i + 1;
+        return 1u + npf;
+    };
+    return send_chain_loop(fd, n_pkts, frags);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // Fragment chains (rns_csum_chain_dev) and their head-fragment fill (rns_csum_chain_fill_dev):
-// the one-pass class kernel, K packets per lane; its receive forms over CSR chains and pool buffers.
+// the one-pass class kernel, K packets per lane; its receive forms over CSR chains and pool buffers and
+// the transmit finalize over pool buffers.
 #include "rns_launch.hpp"
 
 namespace rns {
@@ -67,6 +68,17 @@ int launch_rx_pool(const CsumArgs &a, uint32_t K, bool nt, hipStream_t st)
     const dim3 grid(static_cast<uint32_t>(waves)), block(kChainBlock);
     return with_kmax<1, 2, kChainMaxK>(K, [&](auto KM) {
         return with_flags([&](auto NT, auto BUF) { return launch(rx_pool_kernel<NT(), BUF(), KM()>, grid, block, 0, st, a); },
+                          nt, buf_ok(a));
+    });
+}
+
+// Transmit finalize over pool buffers (rns_tx_fill_pool_dev): one wave per K*64 datagrams, one batch each.
+int launch_tx_pool(const CsumArgs &a, uint32_t K, bool nt, hipStream_t st)
+{
+    const uint64_t waves = (static_cast<uint64_t>(a.n) + 64 * K - 1) / (64 * K);
+    const dim3 grid(static_cast<uint32_t>(waves)), block(kChainBlock);
+    return with_kmax<1, 2, kChainMaxK>(K, [&](auto KM) {
+        return with_flags([&](auto NT, auto BUF) { return launch(tx_pool_kernel<NT(), BUF(), KM()>, grid, block, 0, st, a); },
                           nt, buf_ok(a));
     });
 }

@@ -465,6 +465,30 @@ int rns_tx_fill_chain_packed_dev(uint8_t *d_arena, uint64_t arena_bytes, const u
                  });
 }
 
+int rns_tx_fill_pool_dev(uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2, const uint32_t *d_buf_idx,
+                         uint32_t n_frags, const uint32_t *d_blk_first, const uint8_t *d_head_len8,
+                         const uint16_t *d_pay_len16, uint32_t n_pkts, uint8_t *d_status, void *stream)
+{
+    return entry(n_pkts,
+                 buf_log2 >= kPoolTxMinLog2 && buf_log2 <= kPoolMaxLog2 && d_blk_first && d_head_len8 && d_pay_len16 &&
+                     (!n_frags || d_buf_idx) && n_pkts <= RNS_CHAIN_MAX_PACKETS &&
+                     (reinterpret_cast<uintptr_t>(d_pool) & 15) == 0,
+                 d_pool, pool_bytes, RNS_FLAG_COMPLEMENT, stream, [&](CsumArgs &a, hipStream_t st) {
+                     // the compact descriptors in CsumArgs: off32 = buffer indices, first = d_blk_first, head_len8,
+                     // len16 = payload lengths, align_mask = buffer bytes - 1 (rns_k_pool_tx.hpp)
+                     a.off32 = d_buf_idx;
+                     a.n_frags = n_frags;
+                     a.first = d_blk_first;
+                     a.head_len8 = d_head_len8;
+                     a.len16 = d_pay_len16;
+                     a.align_mask = (1u << buf_log2) - 1u;
+                     set_tx_status(a, d_status);
+                     const double mean = chain_mean(a);
+                     a.chain_k = chain_pick_k(mean);
+                     return launch_tx_pool(a, a.chain_k, chain_nt_from_arena(pool_bytes, n_frags, mean), st);
+                 });
+}
+
 int rns_tx_fill_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_off, const uint32_t *d_len,
                     uint32_t n, uint8_t *d_status, void *stream)
 {

@@ -56,7 +56,9 @@ struct CsumArgs {
     const uint8_t *head_len8;      // compact chain finalize: u8 head lengths (payloads: len16 / blk_off / align_mask)
     const uint64_t *head_blk_off;  // compact chain finalize: offset of the head of datagram 64*b
     // pool-buffer receive verify (rns_k_pool_rx.hpp) adds no field: off32 = the fragments' buffer indices,
-    // first = the first fragment of datagram 64*b, len16 = datagram lengths, align_mask = buffer bytes - 1
+    // first = the first fragment of datagram 64*b, len16 = datagram lengths, align_mask = buffer bytes - 1;
+    // nor does the pool-buffer transmit finalize (rns_k_pool_tx.hpp): the same, with len16 = payload lengths
+    // and head_len8 = the head lengths
 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));

@@ -129,6 +129,7 @@ extern template int launch_txrows<false, true, false>(const CsumArgs &, hipStrea
 extern template int launch_txrows<false, true, true>(const CsumArgs &, hipStream_t);
 int launch_rx_chain(const CsumArgs &a, uint32_t K, bool nt, hipStream_t st);  // receive verify over chains
 int launch_rx_pool(const CsumArgs &a, uint32_t K, bool nt, hipStream_t st);   // ... over pool buffers (compact descriptors)
+int launch_tx_pool(const CsumArgs &a, uint32_t K, bool nt, hipStream_t st);   // transmit finalize over pool buffers
 // k_stash.hip: the class kernel's stash modes on one-wave workgroups
 int launch_fill(const CsumArgs &a, dim3 grid, hipStream_t st);
 int launch_rx(const CsumArgs &a, dim3 grid, hipStream_t st);

@@ -13,7 +13,10 @@ gathered from its two fragments (rns_io_send_batch_chain, like send_packet's wri
 RxPoolPipeline receives as the reference does — into a pool of fixed-size buffers that stay held
 until the stack releases them (rns_io_recv_batch_pool) — and verifies the chains where they lie
 (rns_rx_verify_pool_dev): a batch costs one copy of the buffers it used and 14 B of descriptors per
-MTU datagram.
+MTU datagram.  TxPoolPipeline is its transmit twin: datagrams built in the pool as tcp_output
+builds them (a head buffer with the headers at its end, payload buffers filled from their start)
+are finalized where they lie (rns_tx_fill_pool_dev), only the heads' tails come back, and each
+leaves gathered from its buffers (rns_io_send_batch_pool).
 
 The reference handles one packet per loop iteration on its receive thread
 (packet_receive_thread lib.rs:26-31 -> recv_packet netif.rs:65-83 -> ip_input
@@ -36,7 +39,7 @@ import torch
 
 from .batch import (PinnedBuffer, recv_batch, recv_batch_packed, rx_verify, rx_verify_packed, send_batch,
                     send_batch_chain, tx_fill, tx_fill_chain, tx_fill_chain_packed)
-from .pool import recv_batch_pool, rx_verify_pool
+from .pool import _buf_log2, recv_batch_pool, rx_verify_pool, send_batch_pool, tx_fill_pool, tx_pool_layout
 
 MRU = 2048  # netif.rs:66
 
@@ -651,4 +654,123 @@ class RxPoolPipeline:
 
     def close(self):
         for b in (self.host, self._h_idx, self._h_len, self._h_blk, self._h_status, self._h_l4):
+            b.free()
+
+
+class TxPoolPipeline:
+    """Batched transmit out of a buffer pool: pinned pool of ``pool_bufs`` buffers of ``buf_bytes``
+    (the reference's NetBuffer pool: alloc_header's head buffer with its data at the end, buf.rs:262-291,
+    then append_from_slice's payload buffers, buf.rs:385-420) -> the same offsets of a device mirror ->
+    rns_tx_fill_pool_dev -> the heads' tails back -> datagram fd.  ``alloc`` hands out free buffers
+    and marks them held; they stay held, as a TCP retransmit queue holds them, until ``release``
+    returns them.  ``h2d_bytes``: the pool bytes the last ``send`` copied (the covering span of the
+    buffers it used), ``d2h_bytes``: the head bytes it brought back, ``desc_bytes``: its descriptor
+    bytes (3 B per datagram + 4 B per buffer + 4 B per 64 datagrams)."""
+
+    def __init__(self, device: int = 0, pool_bufs: int | None = None, max_pkts: int = 8192, buf_bytes: int = 512):
+        self.buf_bytes, self.max_pkts = int(buf_bytes), int(max_pkts)
+        _buf_log2(self.buf_bytes, 256)
+        self.pool_bufs = int(pool_bufs) if pool_bufs is not None else self.max_pkts * (1 + -(-MRU // self.buf_bytes))
+        self.tail = min(self.buf_bytes, 256)  # the bytes of a head buffer a head (<= 255) can lie in
+        self.dev = torch.device(f"cuda:{device}")
+        nblk = (self.max_pkts + 63) // 64
+        self.host = PinnedBuffer(self.pool_bufs * self.buf_bytes)
+        self._h_idx, self._h_hl = PinnedBuffer(4 * self.pool_bufs), PinnedBuffer(self.max_pkts)
+        self._h_pl, self._h_blk = PinnedBuffer(2 * self.max_pkts), PinnedBuffer(4 * nblk)
+        self._h_status, self._h_heads = PinnedBuffer(self.max_pkts), PinnedBuffer(self.max_pkts * self.tail)
+        self.d_pool = torch.empty(self.pool_bufs * self.buf_bytes, dtype=torch.uint8, device=self.dev)
+        self._d_idx = torch.empty(self.pool_bufs, dtype=torch.int32, device=self.dev)
+        self._d_hl = torch.empty(self.max_pkts, dtype=torch.uint8, device=self.dev)
+        self._d_pl = torch.empty(self.max_pkts, dtype=torch.int16, device=self.dev)
+        self._d_blk = torch.empty(nblk, dtype=torch.int32, device=self.dev)
+        self._d_status = torch.empty(self.max_pkts, dtype=torch.uint8, device=self.dev)
+        self._d_heads = torch.empty(self.max_pkts, self.tail, dtype=torch.uint8, device=self.dev)
+        self._done = torch.cuda.Event()
+        self._free = np.arange(self.pool_bufs, dtype=np.uint32)
+        self._held = np.zeros(self.pool_bufs, dtype=bool)
+        self.h2d_bytes = self.d2h_bytes = self.desc_bytes = 0
+
+    @property
+    def free_bufs(self) -> int:
+        return int(self._free.shape[0])
+
+    def _lengths(self, head_len, pay_len) -> tuple[np.ndarray, np.ndarray]:
+        hl, pl = np.asarray(head_len), np.asarray(pay_len)
+        if hl.ndim != 1 or hl.shape != pl.shape or hl.shape[0] > self.max_pkts:
+            raise ValueError(f"head_len and pay_len: one entry per datagram each, at most {self.max_pkts}")
+        if hl.size and not (1 <= int(hl.min()) and int(hl.max()) <= 255 and 0 <= int(pl.min()) and int(pl.max()) <= 0xFFFF):
+            raise ValueError("head lengths are 1..255 and payload lengths 0..65535")
+        return hl.astype(np.uint8), pl.astype(np.uint16)
+
+    def alloc(self, head_len, pay_len) -> np.ndarray:
+        """The buffer indices (uint32, in the form's order: each datagram's head buffer, then its
+        payload buffers) of a batch with these lengths, taken from the free list and marked held."""
+        _, pl = self._lengths(head_len, pay_len)
+        nf = int((1 + -(-pl.astype(np.int64) // self.buf_bytes)).sum())
+        if nf > self._free.shape[0]:
+            raise ValueError(f"the batch needs {nf} buffers, {self._free.shape[0]} are free")
+        idx, self._free = self._free[:nf].copy(), self._free[nf:].copy()
+        self._held[idx] = True
+        return idx
+
+    def send(self, fd: int, buf_idx, head_len, pay_len) -> np.ndarray:
+        """Finalize and send one batch whose heads (at each head buffer's end) and payloads the caller
+        wrote into ``host``; returns the uint8 status (RNS_TX_*) per datagram."""
+        hl, pl = self._lengths(head_len, pay_len)
+        idx = np.ascontiguousarray(buf_idx, dtype=np.uint32).ravel()
+        n = int(hl.shape[0])
+        self.h2d_bytes = self.d2h_bytes = self.desc_bytes = 0
+        if n == 0:
+            return np.empty(0, dtype=np.uint8)
+        blk, first, nf = tx_pool_layout(pl, self.buf_bytes)
+        if idx.shape[0] != nf or int(idx.max()) >= self.pool_bufs or not self._held[idx].all():
+            raise ValueError("buf_idx must name the batch's held buffers, one per fragment")
+        heads = idx[first[:-1]].astype(np.int64)
+        if np.unique(heads).size != n:
+            raise ValueError("a head buffer is named twice")
+        nb, B, tail = blk.shape[0], self.buf_bytes, self.tail
+        h_idx, h_blk = self._h_idx.array.view(np.int32)[:nf], self._h_blk.array.view(np.int32)[:nb]
+        h_hl, h_pl = self._h_hl.array[:n], self._h_pl.array.view(np.int16)[:n]
+        h_idx[:], h_blk[:], h_hl[:], h_pl[:] = idx.view(np.int32), blk.view(np.int32), hl, pl.view(np.int16)
+        lo, hi = int(idx.min()) * B, (int(idx.max()) + 1) * B
+        h_heads = self._h_heads.array[:n * tail].reshape(n, tail)
+        with torch.cuda.device(self.dev):
+            # pinned host memory (rns_host_alloc): every copy is a DMA transfer
+            self.d_pool[lo:hi].copy_(torch.from_numpy(self.host.array[lo:hi]), non_blocking=True)
+            self._d_idx[:nf].copy_(torch.from_numpy(h_idx), non_blocking=True)
+            self._d_blk[:nb].copy_(torch.from_numpy(h_blk), non_blocking=True)
+            self._d_hl[:n].copy_(torch.from_numpy(h_hl), non_blocking=True)
+            self._d_pl[:n].copy_(torch.from_numpy(h_pl), non_blocking=True)
+            self.h2d_bytes, self.desc_bytes = hi - lo, 3 * n + 4 * nf + 4 * nb
+            tx_fill_pool(self.d_pool, self._d_idx[:nf], self._d_blk[:nb], self._d_hl[:n], self._d_pl[:n],
+                         buf_bytes=B, status=self._d_status[:n])
+            # only the heads come back: the last `tail` bytes of every head buffer gathered on the device
+            # (the head buffers' places in buf_idx follow from the payload lengths already there)
+            nfr = 1 + ((self._d_pl[:n].to(torch.int64) & 0xFFFF) + (B - 1)) // B
+            d_heads = self._d_idx[:nf][torch.cumsum(nfr, 0) - nfr].to(torch.int64)
+            torch.index_select(self.d_pool.view(self.pool_bufs, B)[:, B - tail:], 0, d_heads, out=self._d_heads[:n])
+            torch.from_numpy(h_heads).copy_(self._d_heads[:n], non_blocking=True)
+            torch.from_numpy(self._h_status.array[:n]).copy_(self._d_status[:n], non_blocking=True)
+            self.d2h_bytes = n * tail
+            self._done.record()
+            self._done.synchronize()
+        self.host.array.reshape(self.pool_bufs, B)[heads, B - tail:] = h_heads
+        sent = send_batch_pool(fd, self.host.array, idx, blk, hl, pl, B)
+        if sent != n:
+            raise RuntimeError(f"sent {sent} of {n} datagrams")
+        return self._h_status.array[:n].copy()
+
+    def release(self, indices) -> None:
+        """Return held buffers to the free list (each index once, and only while it is held); the list
+        is kept in index order, as RxPoolPipeline keeps it."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).ravel()
+        if idx.size == 0:
+            return
+        if int(idx.max()) >= self.pool_bufs or not self._held[idx].all() or np.unique(idx).size != idx.size:
+            raise ValueError("release takes indices of held buffers, each once")
+        self._held[idx] = False
+        self._free = np.sort(np.concatenate([self._free, idx]))
+
+    def close(self):
+        for b in (self.host, self._h_idx, self._h_hl, self._h_pl, self._h_blk, self._h_status, self._h_heads):
             b.free()

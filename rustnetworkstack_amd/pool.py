@@ -1,10 +1,16 @@
-"""Receive verify of datagrams held in fixed-size pool buffers, over compact descriptors.
+"""Receive verify and transmit finalize of datagrams held in fixed-size pool buffers, over
+compact descriptors.
 
 recv_packet (netif.rs:65-83) leaves a datagram as a chain of full pool buffers and one partly
 filled one, so the chain is implied by the datagram's length and its buffers' indices:
 ``recv_batch_pool`` receives into that form, ``rx_verify_pool`` verifies it on the device
 (rns_rx_verify_pool_dev) and ``rx_pool_layout`` computes the index for given lengths.  The
-functions are re-exported by ``batch``, whose argument checks they use.
+transmit side is its twin: append_from_slice (buf.rs:385-420) fills whole buffers and a last one
+with the remainder, alloc_header (buf.rs:262-291) prepends a buffer whose data sits at its end, so
+a datagram is implied by its head length, its payload length and its buffers' indices.
+``tx_pool_layout`` computes the index, ``tx_fill_pool`` finalizes on the device
+(rns_tx_fill_pool_dev) and ``send_batch_pool`` sends from that form.  The functions are re-exported
+by ``batch``, whose argument checks they use.
 """
 from __future__ import annotations
 
@@ -14,14 +20,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import (_I32, _U16, _call, _descriptors, _local_addrs, _per_packet, _recv_chain_args, _status)
+from .batch import (_I32, _U8, _U16, _call, _descriptors, _local_addrs, _per_packet, _recv_chain_args, _status)
 
 
-def _buf_log2(buf_bytes: int) -> int:
-    """log2 of a pool's buffer size: a power of two in 64..32768 (rns_rx_verify_pool_dev)."""
+def _buf_log2(buf_bytes: int, lowest: int = 64) -> int:
+    """log2 of a pool's buffer size: a power of two in 64..32768 (rns_rx_verify_pool_dev), in
+    256..32768 for the transmit form (rns_tx_fill_pool_dev: every u8 head length fits a buffer)."""
     buf_bytes = int(buf_bytes)
-    if buf_bytes & (buf_bytes - 1) or not 64 <= buf_bytes <= 32768:
-        raise ValueError("buf_bytes must be a power of two in 64..32768")
+    if buf_bytes & (buf_bytes - 1) or not lowest <= buf_bytes <= 32768:
+        raise ValueError(f"buf_bytes must be a power of two in {lowest}..32768")
     return buf_bytes.bit_length() - 1
 
 
@@ -92,3 +99,80 @@ def recv_batch_pool(fd: int, pool: np.ndarray, free: np.ndarray, buf_bytes: int 
     if r < 0:
         raise _lib.ChecksumError(r, "rns_io_recv_batch_pool")
     return r, len16[:r], blk_first[:(r + 63) // 64], int(nf.value)
+
+
+def tx_pool_layout(pay_len, buf_bytes: int = 512):
+    """The pool transmit form's index of datagrams with the given payload lengths
+    (rns_tx_pool_layout): datagram i takes ``1 + ceil(pay_len[i] / buf_bytes)`` buffer indices from
+    ``first[i]`` on, the head buffer first.  Returns (blk_first uint32 [ceil(n/64)], first uint32
+    [n+1], n_frags)."""
+    pl = np.asarray(pay_len)
+    if pl.ndim != 1:
+        raise ValueError("pay_len must be 1-D")
+    if pl.size and (int(pl.max()) > 0xFFFF or int(pl.min()) < 0):
+        raise ValueError("the pool form holds u16 payload lengths (<= 65535)")
+    log2 = _buf_log2(buf_bytes, 256)
+    p16 = np.ascontiguousarray(pl, dtype=np.uint16)
+    n = int(p16.size)
+    nb = (n + 63) // 64
+    blk, first = np.zeros(max(nb, 1), dtype=np.uint32), np.zeros(n + 1, dtype=np.uint32)
+    nf = ctypes.c_uint64(0)
+    st = _lib.load().rns_tx_pool_layout(p16.ctypes.data, n, log2, blk.ctypes.data, first.ctypes.data, ctypes.byref(nf))
+    _lib.check(st, "rns_tx_pool_layout")
+    return blk[:nb], first, int(nf.value)
+
+
+def tx_fill_pool(pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: torch.Tensor, head_len8: torch.Tensor,
+                 pay_len16: torch.Tensor, *, buf_bytes: int = 512, status: torch.Tensor | None = None) -> torch.Tensor:
+    """Transmit finalize of datagrams held in fixed-size pool buffers (rns_tx_fill_pool_dev): buffer
+    k = ``pool[k * buf_bytes:]``, datagram i = the LAST ``head_len8[i]`` bytes of its head buffer
+    followed by ``pay_len16[i]`` payload bytes in buffers read from their start, all full but the
+    last; its ``1 + ceil(pay_len16[i] / buf_bytes)`` indices are ``buf_idx[first_i:]`` with
+    ``first_i`` = ``blk_first[i // 64]`` + the buffers of the datagrams before i in its block of 64
+    (see ``tx_pool_layout``).  Exactly the bytes and the uint8 status per datagram of
+    ``tx_fill_chain`` on the chains this expands to.  A head buffer must not be named twice."""
+    dev = _descriptors(pool, ("buf_idx", buf_idx, _I32), ("blk_first", blk_first, _I32),
+                       ("head_len8", head_len8, _U8), ("pay_len16", pay_len16, _U16))
+    log2 = _buf_log2(buf_bytes, 256)
+    n, nf = pay_len16.numel(), buf_idx.numel()
+    if head_len8.numel() != n:
+        raise ValueError("head_len8 and pay_len16 must have one entry per datagram each")
+    if blk_first.numel() < (n + 63) // 64:
+        raise ValueError("blk_first needs one entry per 64 datagrams")
+    if n > _lib.RNS_CHAIN_MAX_PACKETS or nf >= 2 ** 32:
+        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} datagrams and 2^32-1 buffers per pool call")
+    if pool.data_ptr() & 15:
+        raise ValueError("the pool must start 16-byte aligned")
+    status = _status(status, n, dev)
+    _call("rns_tx_fill_pool_dev", dev, pool.data_ptr(), pool.numel(), log2, buf_idx.data_ptr(), nf,
+          blk_first.data_ptr(), head_len8.data_ptr(), pay_len16.data_ptr(), n, status.data_ptr())
+    return status
+
+
+def send_batch_pool(fd: int, pool: np.ndarray, buf_idx: np.ndarray, blk_first: np.ndarray, head_len8: np.ndarray,
+                    pay_len16: np.ndarray, buf_bytes: int = 512) -> int:
+    """Send datagrams held in the pool transmit form (rns_io_send_batch_pool): each goes out as one
+    datagram gathered from its head bytes and its payload buffers, as ``send_batch_chain`` sends
+    the chains the form expands to.  Returns the number of datagrams sent."""
+    log2 = _buf_log2(buf_bytes, 256)
+    if pool.dtype != np.uint8 or not pool.flags["C_CONTIGUOUS"]:
+        raise ValueError("pool must be a contiguous uint8 array")
+    buf_idx = np.ascontiguousarray(buf_idx, dtype=np.uint32)
+    blk_first = np.ascontiguousarray(blk_first, dtype=np.uint32)
+    head_len8 = np.ascontiguousarray(head_len8, dtype=np.uint8)
+    pay_len16 = np.ascontiguousarray(pay_len16, dtype=np.uint16)
+    n = int(pay_len16.shape[0])
+    if head_len8.shape[0] != n or blk_first.shape[0] < (n + 63) // 64:
+        raise ValueError("head_len8 and pay_len16 need one entry per datagram, blk_first one per 64")
+    nfr = 1 + (pay_len16.astype(np.int64) + int(buf_bytes) - 1) // int(buf_bytes)
+    for b in range((n + 63) // 64):  # every block's buffers lie inside buf_idx, and inside the pool
+        end = int(blk_first[b]) + int(nfr[64 * b:64 * b + 64].sum())
+        if end > buf_idx.shape[0]:
+            raise ValueError("blk_first points past buf_idx")
+    if buf_idx.shape[0] and int(buf_idx.max()) >= pool.shape[0] // int(buf_bytes):
+        raise ValueError("buf_idx names a buffer outside the pool")
+    r = _lib.load().rns_io_send_batch_pool(int(fd), pool.ctypes.data, log2, buf_idx.ctypes.data, blk_first.ctypes.data,
+                                           head_len8.ctypes.data, pay_len16.ctypes.data, n)
+    if r < 0:
+        raise _lib.ChecksumError(r, "rns_io_send_batch_pool")
+    return r

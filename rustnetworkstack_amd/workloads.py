@@ -545,3 +545,79 @@ class RxChainBatch:
     @property
     def payload_bytes(self) -> int:
         return self.layout.flat.payload_bytes
+
+
+# ---------------------------------------------------------------------------
+# Transmit pool batches (rns_tx_fill_pool_dev): datagrams as tcp_output leaves them in the
+# reference's fragment pool — append_from_slice (buf.rs:385-420) fills whole buffers and a last
+# one with the remainder, alloc_header (buf.rs:262-291) prepends a buffer whose data sits at its
+# end.  The pool hands buffers out in order after start-up and in any order later: `shuffled`.
+# ---------------------------------------------------------------------------
+class TxPoolBatch:
+    """A transmit batch in pool buffers in HBM: the IPv4/TCP datagrams of TxChainBatch (a 40-byte
+    head — an IPv4 header from LOCAL4 to REMOTE4, then the TCP header alloc_header left: splitmix64
+    bytes — plus the payload) laid into ``buf_bytes``-byte buffers, the head in the last 40 bytes of
+    its own buffer, the payload in whole buffers and a last partly filled one.  Carries the compact
+    descriptors (``d_buf_idx``, ``d_blk_first``, ``d_head_len8``, ``d_pay_len16``) and the CSR chains
+    they expand to (``d_off``, ``d_len``, ``d_first``) over the same ``arena``."""
+
+    HEAD = 40  # IPv4 header + TCP header
+
+    def __init__(self, config: str, device, n: int | None = None, buf_bytes: int = 512, shuffled: bool = False,
+                 data_seed: int = DATA_SEED):
+        import torch
+
+        from .batch import fill_splitmix64, tx_pool_layout
+        flat = make_layout(config, n=n, data_seed=data_seed)
+        self.config, self.buf_bytes, self.shuffled = config, int(buf_bytes), bool(shuffled)
+        self.device = torch.device(device)
+        L = flat.length.astype(np.int64)
+        cnt = flat.n
+        if cnt and int(L.min()) < MIN_DATAGRAM:
+            raise ValueError(f"finalize batches need datagrams of at least {MIN_DATAGRAM} B")
+        B = self.buf_bytes
+        pay = L - self.HEAD
+        blk, first32, nf = tx_pool_layout(pay, B)
+        first = first32.astype(np.int64)
+        npf = first[1:] - first[:-1] - 1
+        if shuffled:
+            buf = np.argsort(splitmix64(data_seed ^ SHUFFLE_STREAM, nf), kind="stable").astype(np.int64)
+        else:
+            buf = np.arange(nf, dtype=np.int64)
+        # the expanded chains: the head fragment at its buffer's end, the payload fragments from their buffers' starts
+        frag_off = buf * B
+        frag_len = np.full(nf, B, dtype=np.int64)
+        heads = first[:-1]
+        frag_off[heads] += B - self.HEAD
+        frag_len[heads] = self.HEAD
+        has = npf > 0
+        frag_len[first[1:][has] - 1] = (pay - (npf - 1) * B)[has]
+        self.length, self.first, self.buf = L, first32, buf
+        self.frag_off, self.frag_len = frag_off.astype(np.uint64), frag_len.astype(np.uint32)
+        self.hoff = frag_off[heads]
+        self.payload_bytes = int(L.sum())
+        self.arena = torch.empty(nf * B + 16, dtype=torch.uint8, device=self.device)
+        fill_splitmix64(self.arena, flat.data_seed)
+        hdr = torch.from_numpy(ipv4_tcp_headers(L, LOCAL4, REMOTE4)).to(self.device)
+        d_hoff = torch.from_numpy(self.hoff).to(self.device)
+        step = 1 << 20  # datagrams per scatter (bounds the index tensor)
+        for i in range(0, cnt, step):
+            idx = d_hoff[i:i + step].view(-1, 1) + torch.arange(20, device=self.device)
+            self.arena[idx.flatten()] = hdr[i:i + step].flatten()
+        self.pool = self.arena[:nf * B]
+        self.d_buf_idx = torch.from_numpy(buf.astype(np.uint32).view(np.int32)).to(self.device)
+        self.d_blk_first = torch.from_numpy(blk.view(np.int32)).to(self.device)
+        self.d_head_len8 = torch.full((cnt,), self.HEAD, dtype=torch.uint8, device=self.device)
+        self.d_pay_len16 = torch.from_numpy(pay.astype(np.uint16).view(np.int16)).to(self.device)
+        self.d_off = torch.from_numpy(self.frag_off.view(np.int64)).to(self.device)
+        self.d_len = torch.from_numpy(self.frag_len.view(np.int32)).to(self.device)
+        self.d_first = torch.from_numpy(first32.view(np.int32)).to(self.device)
+        self.status = torch.empty(cnt, dtype=torch.uint8, device=self.device)
+
+    @property
+    def n(self) -> int:
+        return int(self.length.shape[0])
+
+    @property
+    def n_frags(self) -> int:
+        return int(self.frag_off.shape[0])

@@ -31,6 +31,12 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              descriptors (a u32 buffer index per fragment, a u16 length per datagram, one u32 per 64
              datagrams), next to rns_rx_verify_chain_dev over the CSR chains (the yardstick), in
              alternating rounds; statuses and L4 values are compared before timing
+* tx_pool — rns_tx_fill_pool_dev: transmit finalize of datagrams in 512-byte pool buffers as the
+             reference's transmit path leaves them (workloads.TxPoolBatch: a 40-byte head at the end of
+             its own buffer, the payload in whole buffers and a last partly filled one), the buffers in
+             order and shuffled, over the compact descriptors; next to it rns_tx_fill_chain_dev over the
+             CSR chains of the same pool tensor (the yardstick), in alternating rounds; bytes and
+             statuses are compared before timing
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -151,6 +157,9 @@ def main():
         if "rx_verify_pool" in ops:
             for shuffled in (False, True):
                 r.update(bench_rx_pool(cfg, dev, args, shuffled))
+        if "tx_pool" in ops:
+            for shuffled in (False, True):
+                r.update(bench_tx_pool(cfg, dev, args, shuffled))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -405,6 +414,55 @@ def bench_rx_pool(cfg, dev, args, shuffled):
     pr["ratio_to_rx_verify_chain"] = round(med_p / med_c, 4)
     pr["within_chain_median_plus_spread"] = bool(med_p <= med_c + max(rs_c[-1] - rs_c[0], rs_p[-1] - rs_p[0]))
     del rb
+    torch.cuda.empty_cache()
+    return res
+
+
+def bench_tx_pool(cfg, dev, args, shuffled):
+    """Transmit finalize over the compact pool descriptors and over the CSR chains of the same pool, in
+    alternating rounds (finalizing again stores the same bytes, so both run on one tensor)."""
+    from rustnetworkstack_amd.batch import tx_fill_chain, tx_fill_pool
+    from rustnetworkstack_amd.workloads import TxPoolBatch
+    tb = TxPoolBatch(cfg, dev, shuffled=shuffled)
+    n, pay, nf = tb.n, tb.payload_bytes, tb.n_frags
+    st_c = torch.empty_like(tb.status)
+    pool = lambda: tx_fill_pool(tb.arena, tb.d_buf_idx, tb.d_blk_first, tb.d_head_len8, tb.d_pay_len16,  # noqa: E731
+                                buf_bytes=tb.buf_bytes, status=tb.status)
+    chain = lambda: tx_fill_chain(tb.arena, tb.d_off, tb.d_len, tb.d_first, status=st_c)  # noqa: E731
+    # the two entries' bytes, each from the unfinalized pool (the heads are all either writes)
+    heads = torch.from_numpy(tb.hoff).to(dev).view(-1, 1) + torch.arange(tb.HEAD, device=dev)
+    raw = tb.arena[heads.flatten()].clone()
+    pool()
+    torch.cuda.synchronize()
+    by_pool = tb.arena[heads.flatten()].clone()
+    tb.arena[heads.flatten()] = raw
+    chain()
+    torch.cuda.synchronize()
+    equal = bool(torch.equal(tb.arena[heads.flatten()], by_pool)) and bool(torch.equal(tb.status, st_c))
+    changed = not bool(torch.equal(by_pool, raw))
+    del heads, raw, by_pool
+    filled = int((tb.status == 3).sum().item())
+    rs_p, rs_c = timed_rounds([pool, chain], args.steps, args.rounds)
+
+    def row(rs, desc_bytes):
+        ms = rs[len(rs) // 2]
+        return {"us": round(ms * 1e3, 1), "GBps": round((pay + 5 * n) / ms / 1e6, 1), "packets": n, "fragments": nf,
+                "rounds_us": [round(x * 1e3, 1) for x in rs], "spread_us": round((rs[-1] - rs[0]) * 1e3, 1),
+                "descriptor_bytes_per_datagram": round(desc_bytes / n, 2)}
+
+    tag = "_shuffled" if shuffled else ""
+    res = {"tx_pool" + tag: row(rs_p, 3 * n + 4 * nf + 4 * ((n + 63) // 64)),
+           "tx_pool_chain" + tag: row(rs_c, 12 * nf + 4 * (n + 1))}
+    pr = res["tx_pool" + tag]
+    pr["filled"] = filled
+    pr["heads_changed"] = changed
+    pr["bytes_and_status_equal_chain"] = equal
+    med_p, med_c = rs_p[len(rs_p) // 2], rs_c[len(rs_c) // 2]
+    spread = max(rs_c[-1] - rs_c[0], rs_p[-1] - rs_p[0])
+    pr["ratio_to_tx_fill_chain"] = round(med_p / med_c, 4)
+    pr["faster_than_chain_by_more_than_spread"] = bool(med_p < med_c - spread)
+    pr["within_chain_median_plus_spread"] = bool(med_p <= med_c + spread)
+    del tb
     torch.cuda.empty_cache()
     return res
 
