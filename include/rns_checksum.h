@@ -470,6 +470,74 @@ int rns_tx_fill_pool_dev(uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2
 int rns_tx_pool_layout(const uint16_t *pay_len16, uint64_t n, uint32_t buf_log2,
                        uint32_t *blk_first, uint32_t *first /* optional, n + 1 */, uint64_t *n_frags);
 
+/* TCP segmentation offload: tcp_write's segment loop (tcp.rs:256-285) on the device.  The reference
+ * cuts one send into send_mss pieces and sends each through send_packet -> tcp_output -> ip_output
+ * with the same ports, ack, window, flags and addresses; retransmit (tcp.rs:329-348) is the same with
+ * one piece.  So a "flow" — one tcp_write call — is a template head (IP + TCP header, finished but
+ * for the fields below), its data where it lies in the arena (any byte alignment), its mss and the
+ * place its heads go: flow f has nseg_f = ceil(pay_len_f / mss_f) segments, segment j carries
+ * data[j * mss .. min((j + 1) * mss, pay_len)) and its head, hl = d_head_len8[f] bytes, is written at
+ * d_head_off[f] + j * hl.  The head is the template (d_tmpl + f * tmpl_stride) copied verbatim except
+ *   IPv4 (ip.rs:140-160): [2..4] = hl + seglen, [4..6] = the template's id + j (mod 2^16),
+ *                         [10..12] = the header checksum;
+ *   IPv6 (ip.rs:164-177): [4..6] = the TCP header length + seglen;
+ *   TCP at the IP header's end (tcp.rs:938-976): [4..8] = the template's seq + j * mss (mod 2^32),
+ *                         [16..18] = the checksum (pseudo-header from the template's addresses, the
+ *                         length TCP header + seglen as u16, protocol 6).
+ * Flags, ack, window, options, TTL and everything else are the template's in EVERY segment: the
+ * reference sends ACK|PSH on each piece, so no flag is cleared on the segments before the last as a
+ * NIC's TSO would.  Whatever the template's two checksum fields hold is ignored.
+ * The form is defined by what it expands to: after the call the head range and
+ * d_status[d_seg_first[f] + j] (optional) hold the head built as above with both checksum fields
+ * zero, and then exactly what rns_tx_fill_chain_dev stores and reports for the chain
+ * [(head_off_f + j * hl, hl), (pay_off_f + j * mss, seglen)].  The TCP header has even length, so
+ * every fragment the reference would fold over the same bytes but the last has even length too
+ * (the head's L4 part, then 512-byte payload fragments), and folding per fragment then equals
+ * folding the whole: the value is compute_buffer_ones_comp over the reference's own fragments.
+ * d_seg_first is the CSR index of segments over flows (n_flows + 1 entries), d_blk_flow[b] the flow
+ * that holds segment 64 * b ((n_seg + 63) / 64 entries): rns_tx_segment_layout computes both.
+ * A flow is rejected — every one of its segments RNS_TX_MALFORMED, no byte of its head range
+ * written, that flow only — unless hl <= tmpl_stride; the template is IPv4 with t[0] == 0x45 and
+ * t[9] == 6 (IP header 20 bytes) or IPv6 with t[0] >> 4 == 6 and t[6] == 6 (40 bytes); the TCP data
+ * offset at t[iphdr + 12] >> 4 is >= 5 and iphdr + 4 * doff == hl; mss >= 1 and hl + mss <= 65535;
+ * d_seg_first[f + 1] - d_seg_first[f] == nseg_f and d_seg_first[f + 1] <= n_seg; the data range and
+ * the head range lie inside the arena.  A segment that no well-formed flow covers is
+ * RNS_TX_MALFORMED.  Whatever the descriptors hold, nothing outside the arena and the descriptor
+ * arrays is read or written.  Only head ranges are written: they must not overlap each other, any
+ * data or the templates.  Descriptors: 27 B + the template per flow and 4 B per 64 segments, nothing
+ * per datagram.
+ * n_flows == 0 or n_seg == 0 is RNS_OK; a NULL d_arena / d_tmpl / d_head_len8 / d_pay_off /
+ * d_pay_len / d_mss / d_head_off / d_seg_first / d_blk_flow, tmpl_stride == 0 or n_seg >
+ * RNS_CHAIN_MAX_PACKETS is RNS_E_INVALID, all before the device is touched. */
+int rns_tx_segment_dev(uint8_t *d_arena, uint64_t arena_bytes,
+                       const uint8_t  *d_tmpl, uint32_t tmpl_stride, /* template f at d_tmpl + f * tmpl_stride */
+                       const uint8_t  *d_head_len8,  /* n_flows: template / head length */
+                       const uint64_t *d_pay_off,    /* n_flows: the send's data in the arena */
+                       const uint32_t *d_pay_len,    /* n_flows: data bytes; 0 = no segments */
+                       const uint16_t *d_mss,        /* n_flows */
+                       const uint64_t *d_head_off,   /* n_flows: where the flow's heads go, back to back */
+                       const uint32_t *d_seg_first,  /* n_flows + 1: CSR of segments over flows */
+                       const uint32_t *d_blk_flow,   /* (n_seg + 63) / 64: the flow that holds segment 64 * b */
+                       uint32_t n_flows, uint32_t n_seg, uint8_t *d_status /* optional, n_seg */, void *stream);
+
+/* Host helper for the segmentation form (CPU only): from the n_flows data lengths, mss and head
+ * lengths and the first head's offset, seg_first (n_flows + 1), head_off (n_flows: the flows' heads
+ * back to back in flow order), *n_seg, *head_end (just past the last head) and, when blk_flow is
+ * non-NULL, its (n_seg + 63) / 64 entries — call it once with blk_flow NULL for *n_seg, then again
+ * with the array.  mss == 0 with pay_len > 0, or a segment total past RNS_CHAIN_MAX_PACKETS, is
+ * RNS_E_INVALID. */
+int rns_tx_segment_layout(const uint32_t *pay_len, const uint16_t *mss, const uint8_t *head_len8, uint32_t n_flows,
+                          uint64_t head_first_off, uint32_t *seg_first, uint64_t *head_off,
+                          uint32_t *blk_flow /* optional */, uint64_t *n_seg, uint64_t *head_end);
+
+/* The CSR chains the segmentation form expands to (CPU only; two fragments per segment: its head,
+ * its data slice), for rns_io_send_batch_chain and rns_tx_fill_chain_dev: frag_off / frag_len get
+ * 2 * n_seg entries, first n_seg + 1.  RNS_E_INVALID if the flows do not have n_seg segments in all
+ * or an mss is 0 with data to send. */
+int rns_tx_segment_chains(const uint64_t *pay_off, const uint32_t *pay_len, const uint16_t *mss,
+                          const uint8_t *head_len8, const uint64_t *head_off, uint32_t n_flows, uint64_t n_seg,
+                          uint64_t *frag_off, uint32_t *frag_len, uint32_t *first);
+
 /* Host helper for the compact chain form (CPU only): given the n head and payload lengths, the
  * payload alignment (4..12) and the first head's and first payload's offsets, writes the
  * (n + 63) / 64 block offsets of each region, the offsets just past the last head and the last

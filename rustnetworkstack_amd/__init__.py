@@ -6,16 +6,18 @@
 * ``batch``     — device-resident / host-resident batch API (torch tensors, numpy arrays);
 * ``pool``      — receive verify and transmit finalize of datagrams in pool buffers over compact
                   descriptors (also ``batch.*``);
+* ``segment``   — TCP segmentation offload: one template head per send, the segments' heads built
+                  and finalized on the device (also ``batch.*``);
 * ``workloads`` — the synthetic packet batches BASELINE.json's configs name.
 """
 from . import _lib, util  # noqa: F401
 from ._lib import ChecksumError, ChecksumLibraryMissing  # noqa: F401
 
-__all__ = ["util", "batch", "pool", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
+__all__ = ["util", "batch", "pool", "segment", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
 
 
 def __getattr__(name):
-    if name in ("batch", "pool", "workloads"):
+    if name in ("batch", "pool", "segment", "workloads"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

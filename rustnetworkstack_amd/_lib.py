@@ -69,6 +69,9 @@ EXPORTED_SYMBOLS = (
     "rns_tx_chain_packed_layout",
     "rns_tx_fill_pool_dev",
     "rns_tx_pool_layout",
+    "rns_tx_segment_dev",
+    "rns_tx_segment_layout",
+    "rns_tx_segment_chains",
     "rns_host_ctx_create",
     "rns_host_ctx_destroy",
     "rns_csum_batch_host",
@@ -159,6 +162,10 @@ _SIGNATURES = {
                                           ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "rns_tx_fill_pool_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _vp, _vp]),
     "rns_tx_pool_layout": (_int, [_vp, _u64, _u32, _vp, _vp, ctypes.POINTER(_u64)]),
+    "rns_tx_segment_dev": (_int, [_vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp]),
+    "rns_tx_segment_layout": (_int, [_vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp, ctypes.POINTER(_u64),
+                                     ctypes.POINTER(_u64)]),
+    "rns_tx_segment_chains": (_int, [_vp, _vp, _vp, _vp, _vp, _u32, _u64, _vp, _vp, _vp]),
     "rns_host_ctx_create": (_int, [_int, _u64, _u32, ctypes.POINTER(_vp)]),
     "rns_host_ctx_destroy": (_int, [_vp]),
     "rns_csum_batch_host": (_int, [_vp, _vp, _u64, _vp, _vp, _vp, _vp, _u32, _u32]),

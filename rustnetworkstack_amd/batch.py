@@ -804,10 +804,15 @@ def csum_batch_multi_dev(shards, *, complement: bool = False) -> None:
 # module's interface: batch.rx_pool_layout, batch.rx_verify_pool, batch.recv_batch_pool,
 # batch.tx_pool_layout, batch.tx_fill_pool, batch.send_batch_pool.
 _POOL_API = ("recv_batch_pool", "rx_pool_layout", "rx_verify_pool", "send_batch_pool", "tx_fill_pool", "tx_pool_layout")
+# and so is TCP segmentation offload (segment.py): batch.tx_segment, batch.tx_segment_layout, batch.tx_segment_chains.
+_SEGMENT_API = ("tx_segment", "tx_segment_chains", "tx_segment_layout")
 
 
 def __getattr__(name):
     if name in _POOL_API:
         from . import pool
         return getattr(pool, name)
+    if name in _SEGMENT_API:
+        from . import segment
+        return getattr(segment, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

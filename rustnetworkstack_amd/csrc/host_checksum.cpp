@@ -13,6 +13,7 @@
 //     sum_words = 256 * sum(even bytes) + sum(odd bytes)
 // then reduced mod 2^32 and folded the same way, so the result equals the
 // reference's for every length, including the wrap beyond 131072 bytes.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 
@@ -220,6 +221,61 @@ int rns_tx_pool_layout(const uint16_t *pay_len16, uint64_t n, uint32_t buf_log2,
     if (first)
         first[n] = static_cast<uint32_t>(at);
     *n_frags = at;
+    return RNS_OK;
+}
+
+int rns_tx_segment_layout(const uint32_t *pay_len, const uint16_t *mss, const uint8_t *head_len8, uint32_t n_flows,
+                          uint64_t head_first_off, uint32_t *seg_first, uint64_t *head_off, uint32_t *blk_flow,
+                          uint64_t *n_seg, uint64_t *head_end)
+{
+    if ((n_flows && (!pay_len || !mss || !head_len8 || !head_off)) || !seg_first || !n_seg || !head_end)
+        return RNS_E_INVALID;
+    uint64_t at = 0, h = head_first_off;
+    for (uint32_t f = 0; f < n_flows; ++f) {
+        if (pay_len[f] && !mss[f])
+            return RNS_E_INVALID;
+        const uint64_t ns = pay_len[f] ? (static_cast<uint64_t>(pay_len[f]) + mss[f] - 1) / mss[f] : 0;  // tcp.rs:262-270
+        if (at + ns > RNS_CHAIN_MAX_PACKETS)
+            return RNS_E_INVALID;
+        seg_first[f] = static_cast<uint32_t>(at);
+        head_off[f] = h;
+        if (blk_flow)
+            for (uint64_t b = (at + 63) >> 6; (b << 6) < at + ns; ++b)  // the 64-segment blocks that start in this flow
+                blk_flow[b] = f;
+        at += ns;
+        h += ns * head_len8[f];  // the flow's heads back to back
+    }
+    seg_first[n_flows] = static_cast<uint32_t>(at);
+    *n_seg = at;
+    *head_end = h;
+    return RNS_OK;
+}
+
+int rns_tx_segment_chains(const uint64_t *pay_off, const uint32_t *pay_len, const uint16_t *mss, const uint8_t *head_len8,
+                          const uint64_t *head_off, uint32_t n_flows, uint64_t n_seg, uint64_t *frag_off,
+                          uint32_t *frag_len, uint32_t *first)
+{
+    if ((n_flows && (!pay_off || !pay_len || !mss || !head_len8 || !head_off)) || !first ||
+        (n_seg && (!frag_off || !frag_len)) || 2 * n_seg > 0xFFFFFFFFull)  // the chains' fragment index is u32
+        return RNS_E_INVALID;
+    uint64_t s = 0;
+    for (uint32_t f = 0; f < n_flows; ++f) {
+        if (pay_len[f] && !mss[f])
+            return RNS_E_INVALID;
+        for (uint64_t done = 0; done < pay_len[f]; done += mss[f], ++s) {  // tcp.rs:262-270: one piece per segment
+            if (s >= n_seg)
+                return RNS_E_INVALID;
+            const uint64_t j = done / mss[f];
+            first[s] = static_cast<uint32_t>(2 * s);
+            frag_off[2 * s] = head_off[f] + j * head_len8[f];
+            frag_len[2 * s] = head_len8[f];
+            frag_off[2 * s + 1] = pay_off[f] + done;
+            frag_len[2 * s + 1] = static_cast<uint32_t>(std::min<uint64_t>(mss[f], pay_len[f] - done));
+        }
+    }
+    if (s != n_seg)
+        return RNS_E_INVALID;
+    first[n_seg] = static_cast<uint32_t>(2 * n_seg);
     return RNS_OK;
 }
 

@@ -489,6 +489,33 @@ int rns_tx_fill_pool_dev(uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2
                  });
 }
 
+int rns_tx_segment_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint8_t *d_tmpl, uint32_t tmpl_stride,
+                       const uint8_t *d_head_len8, const uint64_t *d_pay_off, const uint32_t *d_pay_len,
+                       const uint16_t *d_mss, const uint64_t *d_head_off, const uint32_t *d_seg_first,
+                       const uint32_t *d_blk_flow, uint32_t n_flows, uint32_t n_seg, uint8_t *d_status, void *stream)
+{
+    return entry(n_flows ? n_seg : 0u,
+                 d_tmpl && tmpl_stride && d_head_len8 && d_pay_off && d_pay_len && d_mss && d_head_off && d_seg_first &&
+                     d_blk_flow && n_seg <= RNS_CHAIN_MAX_PACKETS,
+                 d_arena, arena_bytes, RNS_FLAG_COMPLEMENT, stream, [&](CsumArgs &a, hipStream_t st) {
+                     // the flows' descriptors in CsumArgs: first = d_seg_first, len = the data lengths, len16 = the
+                     // mss, head_len8, and the fields of its own (rns_k_segment.hpp)
+                     a.tmpl = d_tmpl;
+                     a.tmpl_stride = tmpl_stride;
+                     a.n_flows = n_flows;
+                     a.head_len8 = d_head_len8;
+                     a.seg_pay_off = d_pay_off;
+                     a.len = d_pay_len;
+                     a.len16 = d_mss;
+                     a.seg_head_off = d_head_off;
+                     a.first = d_seg_first;
+                     a.blk_flow = d_blk_flow;
+                     set_tx_status(a, d_status);
+                     // nontemporal loads for MTU-sized segments, as the chain forms choose them
+                     return launch_tx_segment(a, arena_bytes / n_seg >= RNS_CHAIN_NT_FROM, st);
+                 });
+}
+
 int rns_tx_fill_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_off, const uint32_t *d_len,
                     uint32_t n, uint8_t *d_status, void *stream)
 {

@@ -59,6 +59,14 @@ struct CsumArgs {
     // first = the first fragment of datagram 64*b, len16 = datagram lengths, align_mask = buffer bytes - 1;
     // nor does the pool-buffer transmit finalize (rns_k_pool_tx.hpp): the same, with len16 = payload lengths
     // and head_len8 = the head lengths
+    // TCP segmentation (rns_k_segment.hpp): n = segments, first = d_seg_first, len = the flows' data lengths,
+    // len16 = their mss, head_len8 = their head lengths, and
+    const uint8_t *tmpl;           // template head of flow f at tmpl + f * tmpl_stride
+    uint32_t tmpl_stride;
+    uint32_t n_flows;
+    const uint64_t *seg_pay_off;   // per flow: its data in the arena
+    const uint64_t *seg_head_off;  // per flow: where its heads go, back to back
+    const uint32_t *blk_flow;      // the flow that holds segment 64*b
 };
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));

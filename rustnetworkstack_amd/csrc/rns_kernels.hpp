@@ -38,3 +38,4 @@
 #include "rns_k_rows_tx.hpp"
 #include "rns_k_txrows.hpp"
 #include "rns_k_pool_tx.hpp"
+#include "rns_k_segment.hpp"

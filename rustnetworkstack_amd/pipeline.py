@@ -16,7 +16,9 @@ until the stack releases them (rns_io_recv_batch_pool) — and verifies the chai
 MTU datagram.  TxPoolPipeline is its transmit twin: datagrams built in the pool as tcp_output
 builds them (a head buffer with the headers at its end, payload buffers filled from their start)
 are finalized where they lie (rns_tx_fill_pool_dev), only the heads' tails come back, and each
-leaves gathered from its buffers (rns_io_send_batch_pool).
+leaves gathered from its buffers (rns_io_send_batch_pool).  TxSegmentPipeline moves tcp_write's
+segment loop to the device: per send one template head, the data where it lies and the mss go up,
+rns_tx_segment_dev builds and finalizes every segment's head, and only the header region comes back.
 
 The reference handles one packet per loop iteration on its receive thread
 (packet_receive_thread lib.rs:26-31 -> recv_packet netif.rs:65-83 -> ip_input
@@ -40,6 +42,7 @@ import torch
 from .batch import (PinnedBuffer, recv_batch, recv_batch_packed, rx_verify, rx_verify_packed, send_batch,
                     send_batch_chain, tx_fill, tx_fill_chain, tx_fill_chain_packed)
 from .pool import _buf_log2, recv_batch_pool, rx_verify_pool, send_batch_pool, tx_fill_pool, tx_pool_layout
+from .segment import tx_segment, tx_segment_chains, tx_segment_layout
 
 MRU = 2048  # netif.rs:66
 
@@ -773,4 +776,111 @@ class TxPoolPipeline:
 
     def close(self):
         for b in (self.host, self._h_idx, self._h_hl, self._h_pl, self._h_blk, self._h_status, self._h_heads):
+            b.free()
+
+
+class TxSegmentPipeline:
+    """Bulk TCP sends with the segment loop on the device (tcp_write, tcp.rs:256-285): the caller
+    writes each send's data into the pinned payload region ``host.array[:pay_bytes]`` (any byte
+    alignment) and passes one template head, the data's offset and length and the mss per send.
+    Data, templates and per-send descriptors go up; rns_tx_segment_dev builds and finalizes every
+    segment's head in the header region behind the payload region; only that region comes back, and
+    the [head, data slice] chains go out on the datagram fd (rns_io_send_batch_chain).  ``send`` is
+    synchronous.  ``h2d_bytes``: the payload span, templates and descriptors the last ``send``
+    copied up, ``desc_bytes``: the descriptors' share of that (27 B per send + 4 B per 64 segments),
+    ``d2h_bytes``: the head bytes it brought back."""
+
+    def __init__(self, device: int = 0, pay_bytes: int = 16 << 20, max_flows: int = 1024, max_segs: int = 16384,
+                 tmpl_stride: int = 100):
+        self.pay_bytes = (int(pay_bytes) + 15) // 16 * 16
+        self.max_flows, self.max_segs, self.stride = int(max_flows), int(max_segs), int(tmpl_stride)
+        if not 40 <= self.stride <= 255:
+            raise ValueError("tmpl_stride must be in 40..255")
+        self.hdr_bytes = self.max_segs * self.stride
+        self.dev = torch.device(f"cuda:{device}")
+        self.host = PinnedBuffer(self.pay_bytes + self.hdr_bytes)
+        # per-send descriptors, one pinned block: templates, then the u64 / u32 / u16 / u8 arrays
+        nf, nb = self.max_flows, (self.max_segs + 63) // 64
+        self._lay = []
+        at = 0
+        for name, dt, cnt in (("tmpl", np.uint8, nf * self.stride), ("po", np.int64, nf), ("ho", np.int64, nf),
+                              ("pl", np.int32, nf), ("sf", np.int32, nf + 1), ("bf", np.int32, nb),
+                              ("mss", np.int16, nf), ("hl", np.uint8, nf)):
+            at = (at + 15) // 16 * 16
+            self._lay.append((name, np.dtype(dt), at, cnt))
+            at += np.dtype(dt).itemsize * cnt
+        self._h_desc, self._h_status = PinnedBuffer(at), PinnedBuffer(self.max_segs)
+        self.d_arena = torch.empty(self.pay_bytes + self.hdr_bytes, dtype=torch.uint8, device=self.dev)
+        self._d_desc = torch.empty(at, dtype=torch.uint8, device=self.dev)
+        self._d_status = torch.empty(self.max_segs, dtype=torch.uint8, device=self.dev)
+        self._done = torch.cuda.Event()
+        self.h2d_bytes = self.d2h_bytes = self.desc_bytes = 0
+
+    def send(self, fd: int, templates, pay_off, pay_len, mss) -> np.ndarray:
+        """Segment, finalize and send the given sends; returns the uint8 status (RNS_TX_*) per
+        segment, in send order.  Nothing is sent unless every segment is well formed."""
+        tm = [bytes(t) for t in templates]
+        nfl = len(tm)
+        po, pl = np.asarray(pay_off, dtype=np.uint64), np.asarray(pay_len, dtype=np.uint32)
+        ms = np.asarray(mss, dtype=np.uint16)
+        self.h2d_bytes = self.d2h_bytes = self.desc_bytes = 0
+        if nfl == 0:
+            return np.empty(0, dtype=np.uint8)
+        if nfl > self.max_flows or po.shape != (nfl,) or pl.shape != (nfl,) or ms.shape != (nfl,):
+            raise ValueError(f"one template, offset, length and mss per send, at most {self.max_flows} sends")
+        if max(len(t) for t in tm) > self.stride or min(len(t) for t in tm) < 40:
+            raise ValueError(f"template heads are 40..{self.stride} bytes")
+        if int((po + pl).max()) > self.pay_bytes:
+            raise ValueError("a send's data lies outside the payload region")
+        hl = np.array([len(t) for t in tm], dtype=np.uint8)
+        seg_first, head_off, blk_flow, n_seg, head_end = tx_segment_layout(pl, ms, hl, self.pay_bytes)
+        if n_seg > self.max_segs or head_end > self.pay_bytes + self.hdr_bytes:
+            raise ValueError(f"the sends make {n_seg} segments; the pipeline holds {self.max_segs}")
+        if n_seg == 0:
+            return np.empty(0, dtype=np.uint8)
+        nb = blk_flow.shape[0]
+        vals = {"po": po.view(np.int64), "ho": head_off.view(np.int64), "pl": pl.view(np.int32),
+                "sf": seg_first.view(np.int32), "bf": blk_flow.view(np.int32), "mss": ms.view(np.int16), "hl": hl}
+        h, d, used = {}, {}, 0
+        for name, dt, at, cnt in self._lay:
+            h[name] = self._h_desc.array[at:at + dt.itemsize * cnt].view(dt)
+            d[name] = self._d_desc[at:at + dt.itemsize * cnt].view(getattr(torch, dt.name))
+            k = nfl * self.stride if name == "tmpl" else vals[name].shape[0]
+            if name == "tmpl":
+                rows = h[name][:k].reshape(nfl, self.stride)
+                for i, t in enumerate(tm):
+                    rows[i, :len(t)] = np.frombuffer(t, dtype=np.uint8)
+            else:
+                h[name][:k] = vals[name]
+            used = max(used, at + dt.itemsize * k)
+        nz = pl > 0
+        lo = int(po[nz].min()) & ~15
+        hi = int((po + pl)[nz].max())
+        with torch.cuda.device(self.dev):
+            # pinned host memory (rns_host_alloc): every copy is a DMA transfer
+            self.d_arena[lo:hi].copy_(torch.from_numpy(self.host.array[lo:hi]), non_blocking=True)
+            self._d_desc[:used].copy_(torch.from_numpy(self._h_desc.array[:used]), non_blocking=True)
+            self.desc_bytes = 27 * nfl + 4 * nb
+            self.h2d_bytes = hi - lo + nfl * self.stride + self.desc_bytes
+            tx_segment(self.d_arena, d["tmpl"][:nfl * self.stride].view(nfl, self.stride), d["hl"][:nfl], d["po"][:nfl],
+                       d["pl"][:nfl], d["mss"][:nfl], d["ho"][:nfl], d["sf"][:nfl + 1], d["bf"][:nb], n_seg,
+                       status=self._d_status[:n_seg])
+            # only the header region comes back
+            torch.from_numpy(self.host.array[self.pay_bytes:head_end]).copy_(self.d_arena[self.pay_bytes:head_end],
+                                                                             non_blocking=True)
+            torch.from_numpy(self._h_status.array[:n_seg]).copy_(self._d_status[:n_seg], non_blocking=True)
+            self.d2h_bytes = head_end - self.pay_bytes
+            self._done.record()
+            self._done.synchronize()
+        status = self._h_status.array[:n_seg].copy()
+        if (status & 0x80).any():
+            return status
+        frag_off, frag_len, first = tx_segment_chains(po, pl, ms, hl, head_off)
+        sent = send_batch_chain(fd, self.host.array, frag_off, frag_len, first)
+        if sent != n_seg:
+            raise RuntimeError(f"sent {sent} of {n_seg} datagrams")
+        return status
+
+    def close(self):
+        for b in (self.host, self._h_desc, self._h_status):
             b.free()

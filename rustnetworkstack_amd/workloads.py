@@ -621,3 +621,83 @@ class TxPoolBatch:
     @property
     def n_frags(self) -> int:
         return int(self.frag_off.shape[0])
+
+
+# ---------------------------------------------------------------------------
+# TCP segmentation batches (rns_tx_segment_dev): bulk sends as tcp_write (tcp.rs:256-285) makes
+# them — one template head per send, the send's data contiguous in a payload region, the heads of
+# its segments back to back in a header region — and, for comparison, the same datagrams as the
+# compact chain form holds them (prebuilt heads, payloads repacked to 16-byte starts).
+# ---------------------------------------------------------------------------
+class TxSegmentBatch:
+    """Synthetic sends in HBM.  ``shape``:
+
+    * ``bulk44`` — sends of 44 segments of mss 1460 (a 64 KiB tcp_write), IPv4 40-byte heads;
+      ``n_seg`` (default 2^20) is rounded down to whole sends;
+    * ``imix1``  — ``n_seg`` (default 2^23) one-segment sends whose data lengths are the IMIX
+      datagram lengths (mss 1500): a wave's 64 segments are 64 flows, the flow search's worst case.
+
+    ``arena`` holds the header region (from offset 0) and the data; ``d_*`` are the descriptors of
+    ``batch.tx_segment``.  ``c_arena`` and ``c_*`` are the same datagrams for
+    ``batch.tx_fill_chain_packed``: heads prebuilt by the host in a header region, payloads at
+    16-byte starts (other random bytes: the two arenas are timed, not compared)."""
+
+    HEAD = 40  # IPv4 header + TCP header
+
+    def __init__(self, shape: str, device, n_seg: int | None = None, data_seed: int = DATA_SEED, compact: bool = True):
+        import torch
+
+        from .batch import fill_splitmix64, tx_chain_packed_layout, tx_segment_layout
+        self.shape, self.device = shape, torch.device(device)
+        if shape == "bulk44":
+            nfl = (n_seg if n_seg is not None else 1 << 20) // 44
+            pay_len = np.full(nfl, 44 * 1460, dtype=np.uint32)
+            mss = np.full(nfl, 1460, dtype=np.uint16)
+        elif shape == "imix1":
+            nfl = n_seg if n_seg is not None else 1 << 23
+            pay_len = imix_lengths(nfl, data_seed).astype(np.uint32)
+            mss = np.full(nfl, 1500, dtype=np.uint16)
+        else:
+            raise ValueError("shape is bulk44 or imix1")
+        H = self.HEAD
+        hl = np.full(nfl, H, dtype=np.uint8)
+        seg_first, head_off, blk_flow, n, head_end = tx_segment_layout(pay_len, mss, hl, 0)
+        self.n_flows, self.n = nfl, n
+        data0 = (head_end + 4095) & ~4095
+        pay_off = np.zeros(nfl, dtype=np.uint64)
+        if nfl > 1:
+            np.cumsum(pay_len[:-1].astype(np.uint64), out=pay_off[1:])  # the sends' data back to back: any alignment
+        pay_off += np.uint64(data0)
+        total = int(pay_len.astype(np.int64).sum())
+        self.payload_bytes = total + H * n
+        self.arena = torch.empty(data0 + total + 64, dtype=torch.uint8, device=self.device)
+        fill_splitmix64(self.arena, data_seed)
+        # template heads: an IPv4 header from LOCAL4 to REMOTE4, a TCP header with data offset 5 and ACK|PSH
+        tm = (splitmix64(data_seed ^ 0x7E3B1A7E, nfl * H // 8).view(np.uint8).reshape(nfl, H)).copy()
+        tm[:, :20] = ipv4_tcp_headers(np.full(nfl, H, dtype=np.int64), LOCAL4, REMOTE4)
+        tm[:, 32], tm[:, 33] = 0x50, 0x18
+        dv = lambda a, view: torch.from_numpy(np.ascontiguousarray(a).view(view)).to(self.device)  # noqa: E731
+        self.d_tmpl = dv(tm, np.uint8)
+        self.d_head_len8, self.d_pay_off, self.d_pay_len = dv(hl, np.uint8), dv(pay_off, np.int64), dv(pay_len, np.int32)
+        self.d_mss, self.d_head_off = dv(mss, np.int16), dv(head_off, np.int64)
+        self.d_seg_first, self.d_blk_flow = dv(seg_first, np.int32), dv(blk_flow, np.int32)
+        self.status = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self.head_bytes = int(head_end)
+        # bytes the host hands over per datagram: descriptors, and everything that crosses to the device
+        self.desc_bytes = 27 * nfl + 4 * blk_flow.shape[0]
+        self.h2d_bytes = self.desc_bytes + H * nfl + total
+        if not compact:
+            return
+        owner = np.repeat(np.arange(nfl), seg_first[1:].astype(np.int64) - seg_first[:-1].astype(np.int64))
+        j = np.arange(n, dtype=np.int64) - seg_first[:-1].astype(np.int64)[owner]
+        seglen = np.minimum(mss.astype(np.int64)[owner], pay_len.astype(np.int64)[owner] - j * mss.astype(np.int64)[owner])
+        hblk, pblk, _, _, hend, pend = tx_chain_packed_layout(np.full(n, H), seglen, 4, 0, (H * n + 4095) & ~4095)
+        self.c_arena = torch.empty(pend + 64, dtype=torch.uint8, device=self.device)
+        fill_splitmix64(self.c_arena, data_seed ^ 0xC0)
+        self.c_arena[:H * n].view(n, H)[:, :20] = torch.from_numpy(ipv4_tcp_headers(seglen + H, LOCAL4, REMOTE4)).to(self.device)
+        self.c_head_blk_off, self.c_pay_blk_off = dv(hblk, np.int64), dv(pblk, np.int64)
+        self.c_head_len8 = torch.full((n,), H, dtype=torch.uint8, device=self.device)
+        self.c_pay_len16 = dv(seglen.astype(np.uint16), np.int16)
+        self.c_status = torch.empty(n, dtype=torch.uint8, device=self.device)
+        self.c_desc_bytes = 3 * n + 16 * hblk.shape[0]
+        self.c_h2d_bytes = self.c_desc_bytes + H * n + int(((seglen + 15) & ~15).sum())

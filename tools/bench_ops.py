@@ -37,6 +37,12 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              order and shuffled, over the compact descriptors; next to it rns_tx_fill_chain_dev over the
              CSR chains of the same pool tensor (the yardstick), in alternating rounds; bytes and
              statuses are compared before timing
+* tx_segment — rns_tx_segment_dev: TCP segmentation offload over workloads.TxSegmentBatch's shapes
+             (bulk44: 2^20 segments of mss 1460 as sends of 44 segments, IPv4 40-byte heads; imix1: 2^23
+             one-segment sends with IMIX data lengths, the flow search's worst case); next to it
+             rns_tx_fill_chain_packed_dev finalizing the same datagrams from prebuilt heads (payloads
+             repacked to 16-byte starts), in alternating rounds; both rows carry the descriptor and
+             host-to-device bytes per datagram.  Timed once per run, whatever --configs names
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -123,6 +129,8 @@ def main():
                          "the buffers in order (a packet's fragments adjacent); netbuf_shuffled: the same "
                          "buffers in a random order (no two fragments adjacent)")
     ap.add_argument("--tx-frags", default="0,512", help="chain_fill: payload fragment sizes (0 = one fragment)")
+    ap.add_argument("--segment-shapes", default="bulk44,imix1", help="tx_segment: workloads.TxSegmentBatch shapes")
+    ap.add_argument("--segment-n", type=int, default=0, help="tx_segment: segments per shape (0 = the shape's default)")
     ap.add_argument("--tx-modes", default="plain,runs,txpacked", help="chain_fill: hint flags to time")
     args = ap.parse_args()
     ops = set(args.ops.split(","))
@@ -160,6 +168,9 @@ def main():
         if "tx_pool" in ops:
             for shuffled in (False, True):
                 r.update(bench_tx_pool(cfg, dev, args, shuffled))
+        if "tx_segment" in ops and cfg == args.configs.split(",")[0]:  # its shapes are its own, not the configs'
+            for shape in args.segment_shapes.split(","):
+                r.update(bench_tx_segment(shape, dev, args))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -462,6 +473,43 @@ def bench_tx_pool(cfg, dev, args, shuffled):
     pr["ratio_to_tx_fill_chain"] = round(med_p / med_c, 4)
     pr["faster_than_chain_by_more_than_spread"] = bool(med_p < med_c - spread)
     pr["within_chain_median_plus_spread"] = bool(med_p <= med_c + spread)
+    del tb
+    torch.cuda.empty_cache()
+    return res
+
+
+def bench_tx_segment(shape, dev, args):
+    """TCP segmentation offload against the compact chain finalize of the same datagrams from prebuilt
+    heads (the best path without it), in alternating rounds; both rewrite the same bytes every time."""
+    from rustnetworkstack_amd.batch import tx_fill_chain_packed, tx_segment
+    from rustnetworkstack_amd.workloads import TxSegmentBatch
+    tb = TxSegmentBatch(shape, dev, n_seg=args.segment_n or None)
+    n, pay = tb.n, tb.payload_bytes
+    seg = lambda: tx_segment(tb.arena, tb.d_tmpl, tb.d_head_len8, tb.d_pay_off, tb.d_pay_len, tb.d_mss,  # noqa: E731
+                             tb.d_head_off, tb.d_seg_first, tb.d_blk_flow, n, status=tb.status)
+    cpt = lambda: tx_fill_chain_packed(tb.c_arena, tb.c_head_blk_off, tb.c_head_len8, tb.c_pay_blk_off,  # noqa: E731
+                                       tb.c_pay_len16, pay_align_log2=4, status=tb.c_status)
+    seg()
+    cpt()
+    torch.cuda.synchronize()
+    filled, c_filled = int((tb.status == 3).sum().item()), int((tb.c_status == 3).sum().item())
+    rs_s, rs_c = timed_rounds([seg, cpt], args.steps, args.rounds)
+
+    def row(rs, desc_bytes, h2d_bytes):
+        ms = rs[len(rs) // 2]
+        return {"us": round(ms * 1e3, 1), "GBps": round(pay / ms / 1e6, 1), "datagrams": n, "flows": tb.n_flows,
+                "rounds_us": [round(x * 1e3, 1) for x in rs], "spread_us": round((rs[-1] - rs[0]) * 1e3, 1),
+                "descriptor_bytes_per_datagram": round(desc_bytes / n, 3),
+                "h2d_bytes_per_datagram": round(h2d_bytes / n, 1)}
+
+    res = {f"tx_segment_{shape}": row(rs_s, tb.desc_bytes, tb.h2d_bytes),
+           f"tx_segment_{shape}_compact_finalize": row(rs_c, tb.c_desc_bytes, tb.c_h2d_bytes)}
+    pr = res[f"tx_segment_{shape}"]
+    pr["filled"], res[f"tx_segment_{shape}_compact_finalize"]["filled"] = filled, c_filled
+    med_s, med_c = rs_s[len(rs_s) // 2], rs_c[len(rs_c) // 2]
+    spread = max(rs_c[-1] - rs_c[0], rs_s[-1] - rs_s[0])
+    pr["ratio_to_compact_finalize"] = round(med_s / med_c, 4)
+    pr["within_compact_median_plus_spread"] = bool(med_s <= med_c + spread)
     del tb
     torch.cuda.empty_cache()
     return res
