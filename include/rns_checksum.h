@@ -354,6 +354,98 @@ int rns_rx_verify_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t 
 int rns_rx_pool_layout(const uint16_t *len16, uint64_t n, uint32_t buf_log2,
                        uint32_t *blk_first, uint32_t *first /* optional, n + 1 */, uint64_t *n_frags);
 
+/* TCP receive placement over pool buffers: what tcp_input does after validate_checksum, and
+ * tcp_read's copy, on the device — the receive twin of rns_tx_segment_dev.  For the pool form
+ * above (same pool, same descriptors) every accepted TCP segment is decoded (tcp.rs:549-574), its
+ * flow looked up by PORT_MAP's key (tcp.rs:577-578) in a table the host built, and its payload
+ * copied to its place in that flow's contiguous receive window: window start + (seq - next expected
+ * seq).  The place comes from the sequence number, so segments may arrive in any order within a
+ * batch and no datagram depends on another.  After the call the host holds 24 bytes per datagram
+ * (d_meta) to drive the control plane, and the bytes tcp_read would deliver (tcp.rs:230-246,
+ * buf.rs:424-441) lie contiguous in d_stream.
+ * The form is defined by what it expands to:
+ *   Status: d_status[i] and d_l4_sum[i] are exactly what rns_rx_verify_pool_dev gives for the same
+ *     pool and descriptors.
+ *   Decode: with T = d_len16[i], ip_hdr as the verify parses it (IHL * 4, or 40) and L = T - ip_hdr,
+ *     datagram i is decoded (RNS_PLACE_TCP) iff its status has RNS_RX_ACCEPT, its protocol is 6,
+ *     L >= 20 and 20 <= tcp_hdr = 4 * (byte 12 >> 4) <= L.  Then sport, dport, seq, ack and window
+ *     are the header's big-endian fields, flags = byte 13 and pay_len = L - tcp_hdr.  Everything
+ *     else has place 0, flow RNS_RX_NO_FLOW and every other field 0.  (The reference panics on
+ *     header[0..20] / header[20..header_length] / trim_head for the short cases: parity is unpinned
+ *     there.)  Options are not parsed: parse_options loops forever on a zero option length, and a
+ *     SYN's options are the host's business.
+ *   Lookup: the key is the source address (family from the IP version), sport and dport;
+ *     RNS_PLACE_FLOW is set and flow is the key's index iff the key is in the table.  The listen
+ *     socket fallback and the RST reply (tcp.rs:579-615) stay on the host, which sees RNS_PLACE_TCP
+ *     without RNS_PLACE_FLOW.  With n_flows == 0 every datagram is unmatched and d_tbl is not read.
+ *   Placement: with f = flow and d = (seq - d_next_seq[f]) mod 2^32, the payload is placed
+ *     (RNS_PLACE_DONE) iff the segment is decoded with a flow, pay_len > 0, neither SYN nor RST is
+ *     set, d < d_win_len[f], pay_len <= d_win_len[f] - d and d_win_off[f] + d_win_len[f] <=
+ *     stream_bytes (computed without overflow).  Then d_stream[d_win_off[f] + d + k] = byte
+ *     ip_hdr + tcp_hdr + k of the datagram for k in [0, pay_len): with o = ip_hdr + tcp_hdr + k, the
+ *     byte at offset o & (B - 1) of buffer d_buf_idx[first_i + (o >> buf_log2)], B = 2^buf_log2.  A
+ *     segment with a flow and payload, no SYN / RST, that fails the window test gets
+ *     RNS_PLACE_OUTSIDE (stale, straddling next_seq, past the window's end, or a window past
+ *     stream_bytes) and nothing is written for it.  No byte of d_stream outside the placed ranges
+ *     is written and nothing is ever written to the pool.  Windows of different flows must not
+ *     overlap.  Two placed segments of one batch may overlap within a window: each such byte then
+ *     holds one of the two values, which TCP makes equal.  The per-flow arrays are read-only;
+ *     advancing next_seq and sliding the window is the host's job.
+ * Whatever the descriptors, the table and the per-flow arrays hold, nothing outside the pool,
+ * tbl_bytes and the arrays is read and nothing outside d_stream[0 .. stream_bytes) is written.
+ * Descriptors: the pool form's, plus 16 B per flow and the table (32 B per slot); 24 B of d_meta
+ * come back per datagram.
+ * n_pkts == 0 is RNS_OK; buf_log2 outside 7..15 (60 + 60 header bytes must lie in the first buffer:
+ * the verify's 6 is too small), a NULL d_pool / d_blk_first / d_len16 / d_status / d_meta /
+ * d_next_seq / d_win_off / d_win_len / d_stream / local address, a NULL d_tbl with n_flows > 0, a
+ * NULL d_buf_idx with n_frags > 0, a d_pool that is not 16-byte aligned, a d_meta or d_tbl that is
+ * not 4-byte aligned, tbl_bytes below what rns_rx_flow_table_build asks for n_flows, or n_pkts >
+ * RNS_CHAIN_MAX_PACKETS is RNS_E_INVALID, all before the device is touched. */
+#define RNS_RX_NO_FLOW 0xffffffffu
+typedef struct rns_rx_flow_key {      /* PORT_MAP's key, tcp.rs:578: the REMOTE address and port, the local port */
+    uint8_t ip[16];                   /* family 4: ip[0..4], ip[4..16] zero; family 6: all 16 */
+    uint16_t sport, dport;            /* host byte order: the segment's source port, its destination port */
+    uint8_t family, pad[3];           /* 4 or 6; pad zero */
+} rns_rx_flow_key;                    /* 24 bytes */
+typedef struct rns_rx_tcp_meta {      /* 24 bytes; fields in host byte order */
+    uint32_t flow;                    /* index into the per-flow arrays, RNS_RX_NO_FLOW if none */
+    uint32_t seq, ack;
+    uint16_t sport, dport, window, pay_len;
+    uint8_t flags, ip_hdr, tcp_hdr, place;
+} rns_rx_tcp_meta;
+#define RNS_PLACE_TCP     0x01u  /* decoded: the other fields are valid */
+#define RNS_PLACE_FLOW    0x02u  /* its key is in the table */
+#define RNS_PLACE_DONE    0x04u  /* its payload was copied into its flow's window */
+#define RNS_PLACE_OUTSIDE 0x08u  /* it has a flow and payload, but the window does not take it */
+int rns_rx_tcp_place_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2,
+                              const uint32_t *d_buf_idx, uint32_t n_frags,
+                              const uint32_t *d_blk_first,   /* (n_pkts + 63) / 64 entries */
+                              const uint16_t *d_len16, uint32_t n_pkts,
+                              const uint8_t *local_ipv4, const uint8_t *local_ipv6,
+                              const uint8_t *d_tbl, uint64_t tbl_bytes,   /* rns_rx_flow_table_build's, on the device */
+                              const uint32_t *d_next_seq,    /* n_flows: the next expected sequence number */
+                              const uint64_t *d_win_off,     /* n_flows: the window's start in d_stream */
+                              const uint32_t *d_win_len,     /* n_flows: its bytes */
+                              uint32_t n_flows,
+                              uint8_t *d_stream, uint64_t stream_bytes,
+                              uint8_t *d_status, uint16_t *d_l4_sum /* optional */, rns_rx_tcp_meta *d_meta,
+                              void *stream);
+
+/* Host helper for the placement's flow table (CPU only): *need_bytes = the table's size for n_flows
+ * keys, and, when tbl is non-NULL, the table itself, key f mapped to flow index f.  Only this
+ * function writes a table and only the kernel reads it; copy the bytes to the device as they are.
+ * Layout: 32-byte slots, their count the smallest power of two >= 2 * n_flows and >= 64, an empty
+ * slot all zero, a taken one six little-endian dwords of key (ip[0..16) as bytes, sport | dport <<
+ * 16, family), the flow index and 1.  A key's probe starts at slot h & (slots - 1), h = 0x9e3779b9
+ * then per key dword w: h = (h ^ w) * 0x85ebca6b mod 2^32, h ^= h >> 15, and goes on linearly
+ * (wrapping) to the first empty slot.  Whatever bytes a table holds, the kernel's probe ends within
+ * the slot count and a stored flow >= n_flows is no match.  RNS_E_INVALID for a duplicate key, a
+ * family other than 4 or 6, non-zero padding or non-zero ip[4..16] with family 4, a NULL need_bytes,
+ * a NULL keys with n_flows > 0, or tbl_bytes below the need (the table's contents are then
+ * unspecified; nothing past tbl_bytes is ever written). */
+int rns_rx_flow_table_build(const rns_rx_flow_key *keys, uint32_t n_flows,
+                            uint8_t *tbl /* NULL: size only */, uint64_t tbl_bytes, uint64_t *need_bytes);
+
 /* Transmit finalize (SURVEY a6, §8f row 2 for whole datagrams): for each finished
  * outgoing IP datagram d_arena[d_off[i] .. + d_len[i]), the checksums the stack's
  * transmit path stores — tcp_output (tcp.rs:957-973: pseudo-header from the header's

@@ -8,16 +8,19 @@
                   descriptors (also ``batch.*``);
 * ``segment``   — TCP segmentation offload: one template head per send, the segments' heads built
                   and finalized on the device (also ``batch.*``);
+* ``place``     — TCP receive placement: accepted segments decoded, matched to their flow and their
+                  payload copied into the flow's contiguous receive window on the device (also
+                  ``batch.*``);
 * ``workloads`` — the synthetic packet batches BASELINE.json's configs name.
 """
 from . import _lib, util  # noqa: F401
 from ._lib import ChecksumError, ChecksumLibraryMissing  # noqa: F401
 
-__all__ = ["util", "batch", "pool", "segment", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
+__all__ = ["util", "batch", "pool", "segment", "place", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
 
 
 def __getattr__(name):
-    if name in ("batch", "pool", "segment", "workloads"):
+    if name in ("batch", "pool", "segment", "place", "workloads"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -35,6 +35,11 @@ RNS_RX_FRAGMENT = 0x08
 RNS_RX_UNKNOWN_PROTO = 0x10
 RNS_RX_ACCEPT = 0x40
 RNS_RX_MALFORMED = 0x80
+RNS_RX_NO_FLOW = 0xFFFFFFFF  # rns_rx_tcp_meta.flow: the segment's key is not in the table
+RNS_PLACE_TCP = 0x01
+RNS_PLACE_FLOW = 0x02
+RNS_PLACE_DONE = 0x04
+RNS_PLACE_OUTSIDE = 0x08
 RNS_TX_IP_FILLED = 0x01
 RNS_TX_L4_FILLED = 0x02
 RNS_TX_MALFORMED = 0x80
@@ -62,6 +67,8 @@ EXPORTED_SYMBOLS = (
     "rns_rx_verify_chain_dev",
     "rns_rx_verify_pool_dev",
     "rns_rx_pool_layout",
+    "rns_rx_tcp_place_pool_dev",
+    "rns_rx_flow_table_build",
     "rns_tx_fill_dev",
     "rns_tx_fill_packed_dev",
     "rns_tx_fill_chain_dev",
@@ -154,6 +161,9 @@ _SIGNATURES = {
     "rns_rx_verify_chain_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "rns_rx_verify_pool_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "rns_rx_pool_layout": (_int, [_vp, _u64, _u32, _vp, _vp, ctypes.POINTER(_u64)]),
+    "rns_rx_tcp_place_pool_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp,
+                                         _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
+    "rns_rx_flow_table_build": (_int, [_vp, _u32, _vp, _u64, ctypes.POINTER(_u64)]),
     "rns_tx_fill_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _vp]),
     "rns_tx_fill_packed_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _u32, _vp, _u32, _vp]),
     "rns_tx_fill_chain_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),

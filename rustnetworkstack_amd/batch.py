@@ -806,6 +806,8 @@ def csum_batch_multi_dev(shards, *, complement: bool = False) -> None:
 _POOL_API = ("recv_batch_pool", "rx_pool_layout", "rx_verify_pool", "send_batch_pool", "tx_fill_pool", "tx_pool_layout")
 # and so is TCP segmentation offload (segment.py): batch.tx_segment, batch.tx_segment_layout, batch.tx_segment_chains.
 _SEGMENT_API = ("tx_segment", "tx_segment_chains", "tx_segment_layout")
+# and TCP receive placement (place.py): batch.rx_tcp_place_pool, batch.rx_flow_table, batch.Reassembler, batch.META_DTYPE.
+_PLACE_API = ("META_DTYPE", "Reassembler", "meta_records", "rx_flow_table", "rx_tcp_place_pool")
 
 
 def __getattr__(name):
@@ -815,4 +817,7 @@ def __getattr__(name):
     if name in _SEGMENT_API:
         from . import segment
         return getattr(segment, name)
+    if name in _PLACE_API:
+        from . import place
+        return getattr(place, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

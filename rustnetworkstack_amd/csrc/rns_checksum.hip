@@ -426,6 +426,48 @@ int rns_rx_verify_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t 
                  });
 }
 
+int rns_rx_tcp_place_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2, const uint32_t *d_buf_idx,
+                              uint32_t n_frags, const uint32_t *d_blk_first, const uint16_t *d_len16, uint32_t n_pkts,
+                              const uint8_t *local_ipv4, const uint8_t *local_ipv6, const uint8_t *d_tbl,
+                              uint64_t tbl_bytes, const uint32_t *d_next_seq, const uint64_t *d_win_off,
+                              const uint32_t *d_win_len, uint32_t n_flows, uint8_t *d_stream, uint64_t stream_bytes,
+                              uint8_t *d_status, uint16_t *d_l4_sum, rns_rx_tcp_meta *d_meta, void *stream)
+{
+    static_assert(sizeof(rns_rx_tcp_meta) == 24 && sizeof(rns_rx_flow_key) == kFlowSlotBytes - 8, "rns_k_pool_place.hpp");
+    if (n_pkts == 0)
+        return RNS_OK;
+    const uint64_t slots = flow_slots(n_flows);
+    if (buf_log2 < kPlaceMinLog2 || !d_meta || (reinterpret_cast<uintptr_t>(d_meta) & 3) || !d_next_seq || !d_win_off ||
+        !d_win_len || !d_stream ||
+        (n_flows && (!d_tbl || (reinterpret_cast<uintptr_t>(d_tbl) & 3) || tbl_bytes < slots * kFlowSlotBytes)))
+        return RNS_E_INVALID;
+    // the verify as it is: its rejections, its kernel, its status and L4 sum
+    if (int st = rns_rx_verify_pool_dev(d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
+                                        local_ipv4, local_ipv6, d_status, d_l4_sum, stream))
+        return st;
+    PlaceArgs p{};
+    p.pool = d_pool;
+    p.pool_bytes = pool_bytes;
+    p.buf_idx = d_buf_idx;
+    p.blk_first = d_blk_first;
+    p.len16 = d_len16;
+    p.status = d_status;
+    p.tbl = reinterpret_cast<const uint32_t *>(d_tbl);
+    p.next_seq = d_next_seq;
+    p.win_off = d_win_off;
+    p.win_len = d_win_len;
+    p.stream = d_stream;
+    p.stream_bytes = stream_bytes;
+    p.meta = reinterpret_cast<uint32_t *>(d_meta);
+    p.n = n_pkts;
+    p.n_frags = n_frags;
+    p.n_flows = n_flows;
+    p.slots = static_cast<uint32_t>(slots);
+    p.blog = buf_log2;
+    return launch_rx_place(p, chain_nt_from_arena(pool_bytes, n_frags, static_cast<double>(n_frags) / n_pkts),
+                           static_cast<hipStream_t>(stream));
+}
+
 int rns_tx_fill_packed_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_blk_off, const uint16_t *d_len16,
                            uint32_t align_log2, uint32_t n, uint8_t *d_status, uint32_t len_hint, void *stream)
 {

@@ -39,3 +39,4 @@
 #include "rns_k_txrows.hpp"
 #include "rns_k_pool_tx.hpp"
 #include "rns_k_segment.hpp"
+#include "rns_k_pool_place.hpp"

@@ -43,6 +43,14 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              rns_tx_fill_chain_packed_dev finalizing the same datagrams from prebuilt heads (payloads
              repacked to 16-byte starts), in alternating rounds; both rows carry the descriptor and
              host-to-device bytes per datagram.  Timed once per run, whatever --configs names
+* rx_place — rns_rx_tcp_place_pool_dev: TCP receive placement over RxPlaceBatch's shapes (bulk: 2^20
+             datagrams of 1500 B, 1024 flows x 1024 in-order segments of 1460 B; imix: 2^23 IMIX datagrams
+             whose 40-byte ones are pure ACKs, decoded and not placed), in 512-byte buffers in order and
+             shuffled; next to it rns_rx_verify_pool_dev on the same pool (the difference is what decode,
+             lookup and copy cost) and that verify plus a plain device-to-device copy of the payload bytes
+             (the floor of a two-pass design on payloads that were already contiguous), in alternating
+             rounds; every row carries descriptor bytes and read / written bytes per datagram.  Timed once
+             per run, whatever --configs names
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -131,6 +139,9 @@ def main():
     ap.add_argument("--tx-frags", default="0,512", help="chain_fill: payload fragment sizes (0 = one fragment)")
     ap.add_argument("--segment-shapes", default="bulk44,imix1", help="tx_segment: workloads.TxSegmentBatch shapes")
     ap.add_argument("--segment-n", type=int, default=0, help="tx_segment: segments per shape (0 = the shape's default)")
+    ap.add_argument("--place-shapes", default="bulk,imix", help="rx_place: bulk (1500-byte datagrams) and / or imix")
+    ap.add_argument("--place-n", type=int, default=0, help="rx_place: datagrams per shape (0 = 2^20 bulk, 2^23 imix)")
+    ap.add_argument("--place-flows", type=int, default=1024, help="rx_place: flows (a divisor of the datagram count)")
     ap.add_argument("--tx-modes", default="plain,runs,txpacked", help="chain_fill: hint flags to time")
     args = ap.parse_args()
     ops = set(args.ops.split(","))
@@ -171,6 +182,10 @@ def main():
         if "tx_segment" in ops and cfg == args.configs.split(",")[0]:  # its shapes are its own, not the configs'
             for shape in args.segment_shapes.split(","):
                 r.update(bench_tx_segment(shape, dev, args))
+        if "rx_place" in ops and cfg == args.configs.split(",")[0]:  # its shapes are its own, too
+            for shape in args.place_shapes.split(","):
+                for shuffled in (False, True):
+                    r.update(bench_rx_place(shape, dev, args, shuffled))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -511,6 +526,148 @@ def bench_tx_segment(shape, dev, args):
     pr["ratio_to_compact_finalize"] = round(med_s / med_c, 4)
     pr["within_compact_median_plus_spread"] = bool(med_s <= med_c + spread)
     del tb
+    torch.cuda.empty_cache()
+    return res
+
+
+class RxPlaceBatch:
+    """Received TCP segments of `n_flows` flows in 512-byte pool buffers, for rns_rx_tcp_place_pool_dev:
+    datagram i belongs to flow i % n_flows and carries that flow's next in-order payload bytes.  bulk:
+    every datagram 1500 B (1460 B of payload); imix: workloads.imix_lengths, whose 40-byte datagrams are
+    pure ACKs.  IPv4, 20-byte headers; the checksums are filled by rns_tx_fill_dev."""
+
+    BUF, HEAD = 512, 40
+
+    def __init__(self, shape, dev, n, n_flows, shuffled):
+        from rustnetworkstack_amd.batch import fill_splitmix64, rx_flow_table
+        from rustnetworkstack_amd.workloads import DATA_SEED, LOCAL4, SHUFFLE_STREAM, imix_lengths, splitmix64
+        B, H = self.BUF, self.HEAD
+        assert n % n_flows == 0 and n_flows <= 65536
+        length = np.full(n, 1500, dtype=np.int64) if shape == "bulk" else imix_lengths(n, DATA_SEED).astype(np.int64)
+        pay = length - H
+        nfr = (length + B - 1) // B
+        first = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(nfr, out=first[1:])
+        nf = int(first[-1])
+        flow = np.arange(n) % n_flows
+        per_flow = pay.reshape(-1, n_flows)                       # row j: the flows' j-th segments
+        before = np.cumsum(per_flow, axis=0) - per_flow           # payload bytes of the flow before each
+        win_len = per_flow.sum(axis=0)
+        win_off = np.concatenate([[0], np.cumsum(win_len)[:-1]])
+        next_seq = (0xFFFF0000 + 977 * np.arange(n_flows)) & 0xFFFFFFFF
+        seq = (next_seq[flow] + before.reshape(-1)) & 0xFFFFFFFF
+        h = np.zeros((n, H), dtype=np.uint8)
+        h[:, 0], h[:, 6], h[:, 8], h[:, 9] = 0x45, 0x40, 64, 6
+        h[:, 2], h[:, 3] = (length >> 8) & 0xFF, length & 0xFF
+        h[:, 12], h[:, 13], h[:, 14], h[:, 15] = 10, 1, flow >> 8, flow & 0xFF
+        h[:, 16:20] = np.frombuffer(LOCAL4, dtype=np.uint8)
+        sport = 40000 + (flow % 20000)
+        h[:, 20], h[:, 21], h[:, 22], h[:, 23] = sport >> 8, sport & 0xFF, 0, 80
+        for k in range(4):
+            h[:, 24 + k] = (seq >> (24 - 8 * k)) & 0xFF
+        h[:, 32], h[:, 33], h[:, 34] = 0x50, 0x18, 0x20                # data offset 5, ACK | PSH, window 0x2000
+        self.n, self.n_flows, self.n_frags, self.pay_total = n, n_flows, nf, int(pay.sum())
+        self.total_bytes = int(length.sum())
+        arena = torch.empty(nf * B + 16, dtype=torch.uint8, device=dev)
+        fill_splitmix64(arena[:nf * B], DATA_SEED)
+        d_off = torch.from_numpy(first[:-1] * B).to(dev)
+        d_h = torch.from_numpy(h).to(dev)
+        step = 1 << 20
+        for i in range(0, n, step):
+            idx = d_off[i:i + step].view(-1, 1) + torch.arange(H, device=dev)
+            arena[idx.flatten()] = d_h[i:i + step].flatten()
+        del d_h
+        st = tx_fill(arena, d_off, torch.from_numpy(length.astype(np.int32)).to(dev))
+        assert int((st != 3).sum().item()) == 0, "transmit finalize did not fill every synthetic datagram"
+        self.flat, self.flat_off, self.pay, self.flow = arena, first[:-1] * B, pay, flow
+        self.dst = win_off[flow] + before.reshape(-1)                # where each payload must land
+        if shuffled:
+            buf = np.argsort(splitmix64(DATA_SEED ^ SHUFFLE_STREAM, nf), kind="stable").astype(np.int64)
+            pool = torch.empty_like(arena)
+            d_buf = torch.from_numpy(buf).to(dev)
+            rows, prow = arena[:nf * B].view(nf, B), pool[:nf * B].view(nf, B)
+            for i in range(0, nf, step):
+                prow[d_buf[i:i + step]] = rows[i:i + step]
+            self.pool = pool
+        else:
+            buf, self.pool = np.arange(nf, dtype=np.int64), arena
+        t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)  # noqa: E731
+        self.d_buf_idx = t(buf, np.uint32).view(torch.int32)
+        self.d_len16 = t(length, np.uint16)
+        self.d_blk_first = t(first[:-1:64], np.uint32).view(torch.int32)
+        keys = [(bytes([10, 1, f >> 8, f & 0xFF]), 40000 + f % 20000, 80) for f in range(n_flows)]
+        table = rx_flow_table(keys)
+        self.table_bytes = int(table.size)
+        self.d_table = torch.from_numpy(table).to(dev)
+        self.d_next_seq = t(next_seq, np.uint32).view(torch.int32)
+        self.d_win_off = t(win_off, np.int64)
+        self.d_win_len = t(win_len, np.uint32).view(torch.int32)
+        self.stream = torch.zeros(self.pay_total + 16, dtype=torch.uint8, device=dev)
+        self.status = torch.empty(n, dtype=torch.uint8, device=dev)
+        self.l4_sum = torch.empty(n, dtype=torch.uint16, device=dev)
+        self.meta = torch.empty((n, 24), dtype=torch.uint8, device=dev)
+
+
+def bench_rx_place(shape, dev, args, shuffled):
+    """TCP receive placement next to (a) the pool receive verify of the same pool and (b) that verify
+    plus a plain device-to-device copy of the payload bytes (the floor of a two-pass design on
+    payloads that were already contiguous), in alternating rounds."""
+    from rustnetworkstack_amd.batch import rx_tcp_place_pool, rx_verify_pool
+    from rustnetworkstack_amd.workloads import LOCAL4, LOCAL6
+    n = args.place_n or (1 << 20 if shape == "bulk" else 1 << 23)
+    rb = RxPlaceBatch(shape, dev, n, args.place_flows, shuffled)
+    st_v, l4_v = torch.empty_like(rb.status), torch.empty_like(rb.l4_sum)
+    src = torch.empty(rb.pay_total, dtype=torch.uint8, device=dev)
+    place = lambda: rx_tcp_place_pool(rb.pool, rb.d_buf_idx, rb.d_blk_first, rb.d_len16, LOCAL4, LOCAL6,  # noqa: E731
+                                      rb.d_table, rb.d_next_seq, rb.d_win_off, rb.d_win_len, rb.stream,
+                                      status=rb.status, l4_sum=rb.l4_sum, meta=rb.meta)
+    verify = lambda: rx_verify_pool(rb.pool, rb.d_buf_idx, rb.d_blk_first, rb.d_len16, LOCAL4, LOCAL6,  # noqa: E731
+                                    status=st_v, l4_sum=l4_v)
+
+    def verify_copy():
+        verify()
+        rb.stream[:rb.pay_total].copy_(src)
+
+    place()
+    verify()
+    torch.cuda.synchronize()
+    m = rb.meta[:, 23]                                               # the place byte of every record
+    placed = int((m == 7).sum().item())
+    acks = int((m == 3).sum().item())
+    equal = bool(torch.equal(rb.status, st_v)) and bool(torch.equal(rb.l4_sum.view(torch.int16), l4_v.view(torch.int16)))
+    # the placed bytes, on a sample of datagrams (all of their bytes)
+    pick = np.random.default_rng(1).choice(rb.n, min(rb.n, 4096), replace=False)
+    pick = pick[rb.pay[pick] > 0]
+    ok = True
+    for i in pick[:512]:
+        a, d, ln = int(rb.flat_off[i]) + rb.HEAD, int(rb.dst[i]), int(rb.pay[i])
+        ok = ok and bool(torch.equal(rb.flat[a:a + ln], rb.stream[d:d + ln]))
+    rs_p, rs_v, rs_c = timed_rounds([place, verify, verify_copy], args.steps, args.rounds)
+    nf, nfl = rb.n_frags, rb.n_flows
+    desc_v = 4 * nf + 2 * n + 4 * ((n + 63) // 64)
+
+    def row(rs, desc_bytes, read_bytes, written_bytes):
+        ms = rs[len(rs) // 2]
+        return {"us": round(ms * 1e3, 1), "datagrams": n, "fragments": nf, "flows": nfl,
+                "rounds_us": [round(x * 1e3, 1) for x in rs], "spread_us": round((rs[-1] - rs[0]) * 1e3, 1),
+                "descriptor_bytes": desc_bytes, "descriptor_bytes_per_datagram": round(desc_bytes / n, 2),
+                "read_bytes_per_datagram": round(read_bytes / n, 1),
+                "written_bytes_per_datagram": round(written_bytes / n, 1)}
+
+    tag = f"rx_place_{shape}" + ("_shuffled" if shuffled else "")
+    tcp = placed + acks
+    res = {tag: row(rs_p, desc_v + 16 * nfl + rb.table_bytes,
+                    rb.total_bytes + n + tcp * rb.HEAD + rb.pay_total, 27 * n + rb.pay_total),
+           tag + "_verify_only": row(rs_v, desc_v, rb.total_bytes, 3 * n),
+           tag + "_verify_plus_copy": row(rs_c, desc_v, rb.total_bytes + rb.pay_total, 3 * n + rb.pay_total)}
+    pr = res[tag]
+    pr["placed"], pr["pure_acks"], pr["payload_bytes"] = placed, acks, rb.pay_total
+    pr["status_and_l4_equal_verify"] = equal
+    pr["sampled_payloads_in_place"] = ok
+    med = [r[len(r) // 2] for r in (rs_p, rs_v, rs_c)]
+    pr["decode_lookup_copy_us"] = round((med[0] - med[1]) * 1e3, 1)
+    pr["ratio_to_verify_plus_copy"] = round(med[0] / med[2], 4)
+    del rb, src
     torch.cuda.empty_cache()
     return res
 
