@@ -18,7 +18,7 @@ LIB      := $(PKG)/librns_checksum.so
 # tests/test_c_caller_rx_place.py (TCP receive placement).
 CABI_TESTS := tests/c/test_batch_abi tests/c/test_tx_chain_packed_abi tests/c/test_rx_chain_abi \
               tests/c/test_rx_pool_abi tests/c/test_tx_pool_abi tests/c/test_tx_segment_abi \
-              tests/c/test_rx_place_abi
+              tests/c/test_rx_place_abi tests/c/test_rx_flow_abi
 
 all: $(LIB) oracle $(CABI_TESTS)
 

@@ -446,6 +446,152 @@ int rns_rx_tcp_place_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
 int rns_rx_flow_table_build(const rns_rx_flow_key *keys, uint32_t n_flows,
                             uint8_t *tbl /* NULL: size only */, uint64_t tbl_bytes, uint64_t *need_bytes);
 
+/* TCP flow update: the rest of tcp_input for an Established socket (tcp.rs:642-740) on the device,
+ * over the placement's d_meta as it is — the advance of receive_next_seq and the reassembler's
+ * next_sequence, the delayed-ACK count and its immediate ACKs, the ACK-field check that trims the
+ * retransmit queue, the send-window update.  This is header prediction: for every flow f < n_flows
+ * its segments of the batch are walked in batch order, the first one that is not the fast path's
+ * stops the flow, and the host takes over from there with the state of the consumed prefix.
+ *   Which datagrams: flow f's list is the datagrams i with d_meta[i].place & RNS_PLACE_FLOW and
+ *     d_meta[i].flow == f < n_flows, in ascending i (the order tcp_input would have met them in).
+ *     Every other datagram gets an all-zero d_seg record.
+ *   Stops, tested before each segment in this order (a flow without segments never stops); the
+ *   segment that stops the flow and all its later ones get zero d_seg records, d_res[f].stop is its
+ *   datagram index and d_res[f].why the reason:
+ *     RNS_STOP_MANY     the list has more than RNS_FLOW_MAX_SEGS entries (nothing is consumed, stop =
+ *                       the flow's first datagram).  The reference advertises at most 65535 bytes and
+ *                       no window scale, so a flow has fewer than 64 KiB in flight; the cap lets a
+ *                       flow's list fit on chip.
+ *     RNS_STOP_STATE    state != RNS_TCP_ESTABLISHED at the start of the batch, or n_pend > pend_cap
+ *                       on input (nothing is consumed).
+ *     RNS_STOP_FLAGS    SYN, RST or FIN is set: the RST hack (tcp.rs:635) and the state machine
+ *                       (tcp.rs:742-835) are the host's.
+ *     RNS_STOP_OPTIONS  tcp_hdr != 20: parse_options is the host's, as in the placement (it loops for
+ *                       ever on a zero option length: parity is unpinned there).  With 20 bytes
+ *                       tcp.rs:622-625 is a no-op.
+ *     RNS_STOP_OUTSIDE  place & RNS_PLACE_OUTSIDE: the bytes are not in the window.
+ *     RNS_STOP_PEND     pay_len > 0, seq != rcv_nxt and n_pend == pend_cap: no room to remember it.
+ *   Step of a consumed segment (act has RNS_SEG_CONSUMED), exactly tcp.rs:642-740 with state ==
+ *   Established, seq_gt / seq_lt / seq_le as util.rs:155-166:
+ *     Data (tcp.rs:642-687), when pay_len > 0 (the placement has then set RNS_PLACE_DONE):
+ *       rcv_max = wrapping_max(rcv_max, seq + pay_len) (util.rs:172);
+ *       got = TCPReassembler::add_packet over (seq, pay_len) (tcp.rs:488-516) with the Vec's own
+ *         semantics: seq != rcv_nxt appends (seq, pay_len) at the end of the pending list and got =
+ *         0; else got = pay_len, rcv_nxt += pay_len and the list is rescanned from i = 0: an entry
+ *         with seq_gt(the ARRIVING seq, entry.seq) is removed, an entry with entry.seq == rcv_nxt is
+ *         removed, rcv_nxt += its length, got += its length and the scan restarts at 0; a removal
+ *         moves the tail down one place;
+ *       rq_len += got, readable += got; delayed_acks += 1 (mod 2^16); if it is then >= 5
+ *       (MAX_DELAYED_ACKS): delayed_acks = 0, ack_timer = 0, act |= RNS_SEG_ACK with ack_num =
+ *       rcv_nxt and window = (0xffff - (rq_len & 0xffff)) & 0xffff (send_packet, tcp.rs:403-417; the
+ *       FIN + 1 never applies in Established), n_acks += 1; otherwise, if ack_timer == 0: ack_timer =
+ *       1 and act |= RNS_SEG_TIMER.  (With rq_len > 0xffff the reference computes MAX_RECEIVE_WINDOW
+ *       - len as u16, which panics in a debug build and wraps in a release one: parity is unpinned
+ *       there, and so it is for the panicking decodes inherited from the placement.)
+ *     ACK field (tcp.rs:698-740), when flags & 0x10: if seq_lt(snd_una, ack) && seq_le(ack, snd_nxt):
+ *       acked += ack - snd_una, snd_una = ack.  Then, with the new snd_una, if seq_le(snd_una, ack)
+ *       && seq_le(ack, snd_nxt) && (seq_lt(snd_wl1, seq) || (snd_wl1 == seq && seq_le(snd_wl2,
+ *       ack))): snd_wnd = window, snd_wl1 = seq, snd_wl2 = ack, events |= RNS_EV_WND.
+ *   Timers are the host's: it derives them from consumed > 0 (the response timer's cancel),
+ *   ack_timer (arm or cancel the delayed-ACK timer) and acked (cancel the retransmit timer when the
+ *   queue empties).
+ * d_flow_out[f], d_res[f] and every datagram's d_seg record are written on every call; d_pend_out
+ * holds flow f's list in entries [f * pend_cap, f * pend_cap + n_pend), the entries past n_pend are
+ * unspecified.  A flow stopped at its first segment has d_flow_out[f] == d_flow_in[f] bytewise.  The
+ * in and out arrays must not overlap, and d_meta must not change during the call.  Whatever meta,
+ * state and pending lists hold (n_pend > pend_cap, flow >= n_flows, any place bits), nothing outside
+ * the argument arrays is read or written.  The call allocates nothing: d_work is the caller's,
+ * work_bytes at least what rns_rx_tcp_flow_update_work gives for (n_pkts, n_flows); its contents
+ * before and after the call mean nothing.
+ * n_pkts == 0 still writes every flow's out record (a copy) and a zero result; n_flows == 0 writes
+ * zero d_seg records.  A NULL d_meta / d_seg with n_pkts > 0, a NULL d_flow_in / d_flow_out / d_res
+ * with n_flows > 0, a NULL d_pend_in / d_pend_out with n_flows > 0 and pend_cap > 0, a NULL d_work
+ * with n_pkts + n_flows > 0, any of these arrays not 4-byte aligned (d_work: 8-byte), work_bytes below the need,
+ * n_pkts > RNS_CHAIN_MAX_PACKETS or n_flows >= 2^31 is RNS_E_INVALID, all before the device is
+ * touched. */
+#define RNS_TCP_ESTABLISHED 1u
+#define RNS_FLOW_MAX_SEGS   1024u
+typedef struct rns_tcp_flow {   /* 40 bytes, host byte order */
+    uint32_t rcv_nxt;           /* reassembler.next_sequence (tcp.rs:110) */
+    uint32_t rcv_max;           /* receive_next_seq */
+    uint32_t snd_una, snd_nxt, snd_wnd, snd_wl1, snd_wl2; /* send_unacked, send_next_seq, send_window, send_last_win_seq / _ack */
+    uint32_t rq_len;            /* receive_queue.len() */
+    uint32_t n_pend;            /* out_of_order.len(), <= pend_cap */
+    uint16_t delayed_acks;      /* num_delayed_acks */
+    uint8_t  state;             /* RNS_TCP_ESTABLISHED; anything else is not the fast path's */
+    uint8_t  ack_timer;         /* 1: delayed_ack_timer_id != -1 */
+} rns_tcp_flow;
+/* d_pend: pend_cap (seq, len) u32 pairs per flow, the reassembler's out_of_order Vec IN ITS ORDER;
+ * pend_cap == 0 allows NULL d_pend_*. */
+typedef struct rns_rx_tcp_seg { uint32_t ack_num; uint16_t window; uint8_t act, pad; } rns_rx_tcp_seg; /* 8 bytes */
+#define RNS_SEG_CONSUMED 1u   /* the fast path processed it */
+#define RNS_SEG_ACK      2u   /* an immediate ACK was sent after it: ack_num / window are that ACK's */
+#define RNS_SEG_TIMER    4u   /* it started the delayed-ACK timer */
+typedef struct rns_tcp_flow_res {   /* 24 bytes */
+    uint32_t n_segs;      /* the flow's datagrams in the batch */
+    uint32_t consumed;    /* how many of them, from the front, were processed */
+    uint32_t stop;        /* datagram index of the first one not processed, 0xffffffff if none */
+    uint32_t readable;    /* bytes appended to receive_queue (sum of add_packet's returned lengths) */
+    uint32_t acked;       /* bytes trimmed from the retransmit queue */
+    uint16_t n_acks;      /* immediate ACKs sent */
+    uint8_t events;       /* RNS_EV_WND */
+    uint8_t why;          /* RNS_STOP_* */
+} rns_tcp_flow_res;
+#define RNS_EV_WND       1u   /* the send window was updated */
+#define RNS_STOP_NONE    0u
+#define RNS_STOP_MANY    1u
+#define RNS_STOP_STATE   2u
+#define RNS_STOP_FLAGS   3u
+#define RNS_STOP_OPTIONS 4u
+#define RNS_STOP_OUTSIDE 5u
+#define RNS_STOP_PEND    6u
+int rns_rx_tcp_flow_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,
+                               const rns_tcp_flow *d_flow_in, const uint32_t *d_pend_in, uint32_t pend_cap,
+                               rns_tcp_flow *d_flow_out, uint32_t *d_pend_out,
+                               rns_rx_tcp_seg *d_seg,       /* n_pkts */
+                               rns_tcp_flow_res *d_res,     /* n_flows */
+                               void *d_work, uint64_t work_bytes, void *stream);
+
+/* The workspace of rns_rx_tcp_flow_update_dev (CPU only): *bytes for n_pkts datagrams and n_flows
+ * flows, monotone in both; it also covers rns_tx_ack_build_dev for the same n_pkts.  A NULL bytes,
+ * n_pkts > RNS_CHAIN_MAX_PACKETS or n_flows >= 2^31 is RNS_E_INVALID. */
+int rns_rx_tcp_flow_update_work(uint32_t n_pkts, uint32_t n_flows, uint64_t *bytes);
+
+/* ACK build: the pure ACKs the update decided on, as send_packet(NetBuffer::new(), FLAG_ACK) ->
+ * tcp_output (tcp.rs:938-976) -> ip_output (ip.rs:140-177) builds them, finalized, in batch order.
+ * ACK k belongs to the k-th datagram i in ascending i with d_seg[i].act & RNS_SEG_ACK and
+ * f = d_meta[i].flow < n_flows (an ACK flag on a datagram whose flow >= n_flows is ignored).  Its
+ * head, hl = d_head_len8[f] bytes at d_out + 64 * k, is its flow's template (d_tmpl + f *
+ * tmpl_stride, as in rns_tx_segment_dev) verbatim except
+ *   TCP at the IP header's end: [4..8] = d_flow[f].snd_nxt, [8..12] = d_seg[i].ack_num, [12] = 0x50,
+ *                         [13] = 0x10, [14..16] = d_seg[i].window, [16..18] = the checksum;
+ *   IPv4 (hl == 40):      [2..4] = 40, [4..6] = ip_id_base + (the IPv4 ACKs among ACKs 0..k-1) mod
+ *                         2^16 — NEXT_PACKET_ID.fetch_add runs in ip_output_v4 only and the reference
+ *                         answers in batch order, so these are its ids —, [10..12] = the header
+ *                         checksum;
+ *   IPv6 (hl == 60):      [4..6] = 20.
+ * The result is what rns_tx_fill_dev stores for that head as a datagram without payload.  Bytes
+ * [hl, 64) of a slot are not written.  d_ack_src[k] = i and d_ack_len8[k] = hl, so the slots go out
+ * through rns_io_send_batch(off = 64 * k, len = d_ack_len8[k]).  A malformed template — hl neither
+ * 40 nor 60, hl > tmpl_stride, hl == 40 without t[0] == 0x45 and t[9] == 6, hl == 60 without
+ * t[0] >> 4 == 6 and t[6] == 6, or a TCP data offset t[iphdr + 12] >> 4 other than 5 — keeps its
+ * slot and (an ACK is an IPv4 one, and takes an id, iff hl == 40) its id, gets d_ack_len8[k] = 0 and
+ * no byte of its slot is written.  ACKs at and past ack_cap are counted but not written, neither slot
+ * nor d_ack_src nor d_ack_len8.  d_n_acks[0] = the ACKs, d_n_acks[1] = the IPv4 ones, always
+ * written.  ack_cap == 0 allows NULL d_out / d_ack_src / d_ack_len8: the call counts only.  d_work
+ * as above (the update's workspace serves, once the update is done).
+ * A NULL d_n_acks; with n_pkts > 0 a NULL d_meta / d_seg / d_work, work_bytes below the need or,
+ * with n_flows > 0, a NULL d_flow / d_tmpl / d_head_len8 or tmpl_stride == 0; with ack_cap > 0 a
+ * NULL d_out / d_ack_src / d_ack_len8; a d_meta / d_seg / d_flow / d_out / d_ack_src / d_n_acks that
+ * is not 4-byte aligned or a d_work that is not 8-byte aligned; or n_pkts > RNS_CHAIN_MAX_PACKETS is RNS_E_INVALID, all before
+ * the device is touched. */
+int rns_tx_ack_build_dev(const rns_rx_tcp_meta *d_meta, const rns_rx_tcp_seg *d_seg, uint32_t n_pkts,
+                         const rns_tcp_flow *d_flow, uint32_t n_flows,
+                         const uint8_t *d_tmpl, uint32_t tmpl_stride, const uint8_t *d_head_len8,
+                         uint16_t ip_id_base, void *d_work, uint64_t work_bytes,
+                         uint8_t *d_out, uint32_t ack_cap, uint32_t *d_ack_src, uint8_t *d_ack_len8,
+                         uint32_t *d_n_acks /* 2 */, void *stream);
+
 /* Transmit finalize (SURVEY a6, §8f row 2 for whole datagrams): for each finished
  * outgoing IP datagram d_arena[d_off[i] .. + d_len[i]), the checksums the stack's
  * transmit path stores — tcp_output (tcp.rs:957-973: pseudo-header from the header's

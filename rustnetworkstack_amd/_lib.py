@@ -40,6 +40,13 @@ RNS_PLACE_TCP = 0x01
 RNS_PLACE_FLOW = 0x02
 RNS_PLACE_DONE = 0x04
 RNS_PLACE_OUTSIDE = 0x08
+RNS_TCP_ESTABLISHED = 1  # rns_tcp_flow.state: the only one the flow update's fast path takes
+RNS_FLOW_MAX_SEGS = 1024  # a flow's datagrams per flow-update call
+RNS_SEG_CONSUMED = 0x01
+RNS_SEG_ACK = 0x02
+RNS_SEG_TIMER = 0x04
+RNS_EV_WND = 0x01
+RNS_STOP_NONE, RNS_STOP_MANY, RNS_STOP_STATE, RNS_STOP_FLAGS, RNS_STOP_OPTIONS, RNS_STOP_OUTSIDE, RNS_STOP_PEND = range(7)
 RNS_TX_IP_FILLED = 0x01
 RNS_TX_L4_FILLED = 0x02
 RNS_TX_MALFORMED = 0x80
@@ -69,6 +76,9 @@ EXPORTED_SYMBOLS = (
     "rns_rx_pool_layout",
     "rns_rx_tcp_place_pool_dev",
     "rns_rx_flow_table_build",
+    "rns_rx_tcp_flow_update_dev",
+    "rns_rx_tcp_flow_update_work",
+    "rns_tx_ack_build_dev",
     "rns_tx_fill_dev",
     "rns_tx_fill_packed_dev",
     "rns_tx_fill_chain_dev",
@@ -164,6 +174,10 @@ _SIGNATURES = {
     "rns_rx_tcp_place_pool_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp,
                                          _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
     "rns_rx_flow_table_build": (_int, [_vp, _u32, _vp, _u64, ctypes.POINTER(_u64)]),
+    "rns_rx_tcp_flow_update_dev": (_int, [_vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "rns_rx_tcp_flow_update_work": (_int, [_u32, _u32, ctypes.POINTER(_u64)]),
+    "rns_tx_ack_build_dev": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u16, _vp, _u64, _vp, _u32, _vp, _vp, _vp,
+                                    _vp]),
     "rns_tx_fill_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _vp]),
     "rns_tx_fill_packed_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _u32, _vp, _u32, _vp]),
     "rns_tx_fill_chain_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),

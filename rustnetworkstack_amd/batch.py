@@ -808,6 +808,9 @@ _POOL_API = ("recv_batch_pool", "rx_pool_layout", "rx_verify_pool", "send_batch_
 _SEGMENT_API = ("tx_segment", "tx_segment_chains", "tx_segment_layout")
 # and TCP receive placement (place.py): batch.rx_tcp_place_pool, batch.rx_flow_table, batch.Reassembler, batch.META_DTYPE.
 _PLACE_API = ("META_DTYPE", "Reassembler", "meta_records", "rx_flow_table", "rx_tcp_place_pool")
+# and the TCP flow update and ACK build (flow.py): batch.rx_tcp_flow_update, batch.tx_ack_build, batch.flow_update_host.
+_FLOW_API = ("FLOW_DTYPE", "RES_DTYPE", "SEG_DTYPE", "flow_update_host", "flow_update_work", "rx_tcp_flow_update",
+             "tx_ack_build")
 
 
 def __getattr__(name):
@@ -820,4 +823,7 @@ def __getattr__(name):
     if name in _PLACE_API:
         from . import place
         return getattr(place, name)
+    if name in _FLOW_API:
+        from . import flow
+        return getattr(flow, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

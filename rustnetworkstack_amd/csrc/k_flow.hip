@@ -1,0 +1,69 @@
+// TCP flow update and ACK build (rns_rx_tcp_flow_update_dev, rns_tx_ack_build_dev): the launch
+// sequences — every grid-wide dependency is a launch boundary on the one stream — and the
+// workspace's host-side sizing.
+#define RNS_FLOW_KERNELS
+#include <algorithm>
+
+#include "rns_launch.hpp"
+
+namespace rns {
+
+namespace {
+
+#define RNS_LAUNCH(kernel, grid, block, st, ...)                                      \
+    do {                                                                              \
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);      \
+        if (int e = hip_status(hipGetLastError()))                                    \
+            return e;                                                                 \
+    } while (0)
+
+uint32_t blocks_of(uint64_t n) { return static_cast<uint32_t>(scan_blocks(n)); }
+
+}  // namespace
+
+int launch_flow_update(const FlowArgs &a, hipStream_t st)
+{
+    if (a.n_flows == 0) {  // every datagram's record is zero
+        RNS_LAUNCH(flow_count_kernel, blocks_of(a.n_pkts), kScanBlock, st, a);
+        return RNS_OK;
+    }
+    if (int e = hip_status(hipMemsetAsync(a.cnt, 0, 4ull * a.n_flows, st)))
+        return e;
+    if (a.n_pkts) {
+        const uint32_t nb = blocks_of(a.n_flows);
+        RNS_LAUNCH(flow_count_kernel, blocks_of(a.n_pkts), kScanBlock, st, a);
+        RNS_LAUNCH((scan2_reduce_kernel<FlowCountValue, FlowArgs>), nb, kScanBlock, st, a, static_cast<uint64_t>(a.n_flows),
+                   a.part);
+        RNS_LAUNCH(scan2_parts_kernel, 1, kScanBlock, st, a.part, nb, static_cast<uint32_t *>(nullptr));
+        RNS_LAUNCH(flow_cursor_kernel, nb, kScanBlock, st, a);
+        RNS_LAUNCH(flow_scatter_kernel, blocks_of(a.n_pkts), kScanBlock, st, a);
+    }
+    RNS_LAUNCH(flow_walk_lane_kernel, blocks_of(a.n_flows), kScanBlock, st, a);
+    if (a.n_pkts >= 2)  // a flow with two datagrams exists only then, and at most n_pkts / 2 of them
+        RNS_LAUNCH(flow_walk_wave_kernel, std::min({a.n_flows, a.n_pkts / 2, kFlowWaveGrid}), 64, st, a);
+    return RNS_OK;
+}
+
+int launch_ack_build(const AckArgs &a, hipStream_t st)
+{
+    if (a.n_pkts == 0)
+        return hip_status(hipMemsetAsync(a.n_acks, 0, 8, st));
+    const uint32_t nb = blocks_of(a.n_pkts);
+    RNS_LAUNCH((scan2_reduce_kernel<AckValue, AckArgs>), nb, kScanBlock, st, a, static_cast<uint64_t>(a.n_pkts), a.part);
+    RNS_LAUNCH(scan2_parts_kernel, 1, kScanBlock, st, a.part, nb, a.n_acks);
+    if (a.ack_cap)
+        RNS_LAUNCH(ack_build_kernel, nb, kScanBlock, st, a);
+    return RNS_OK;
+}
+
+}  // namespace rns
+
+using namespace rns;
+
+extern "C" int rns_rx_tcp_flow_update_work(uint32_t n_pkts, uint32_t n_flows, uint64_t *bytes)
+{
+    if (!bytes || n_pkts > RNS_CHAIN_MAX_PACKETS || n_flows > kFlowMaxFlows)
+        return RNS_E_INVALID;
+    *bytes = flow_work_bytes(n_pkts, n_flows);
+    return RNS_OK;
+}

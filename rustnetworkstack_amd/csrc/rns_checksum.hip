@@ -468,6 +468,79 @@ int rns_rx_tcp_place_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
                            static_cast<hipStream_t>(stream));
 }
 
+int rns_rx_tcp_flow_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,
+                               const rns_tcp_flow *d_flow_in, const uint32_t *d_pend_in, uint32_t pend_cap,
+                               rns_tcp_flow *d_flow_out, uint32_t *d_pend_out, rns_rx_tcp_seg *d_seg,
+                               rns_tcp_flow_res *d_res, void *d_work, uint64_t work_bytes, void *stream)
+{
+    static_assert(sizeof(rns_tcp_flow) == 4 * kFlowDw && sizeof(rns_rx_tcp_seg) == 8 &&
+                      sizeof(rns_tcp_flow_res) == 4 * kFlowResDw,
+                  "rns_k_flow.hpp");
+    if (n_pkts == 0 && n_flows == 0)
+        return RNS_OK;
+    const auto mis = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    const bool pend = n_flows && pend_cap;
+    if (n_pkts > RNS_CHAIN_MAX_PACKETS || n_flows > kFlowMaxFlows || (n_pkts && (!d_meta || !d_seg)) ||
+        (n_flows && (!d_flow_in || !d_flow_out || !d_res)) || (pend && (!d_pend_in || !d_pend_out)) || !d_work ||
+        mis(d_meta, 3) || mis(d_seg, 3) || mis(d_flow_in, 3) || mis(d_flow_out, 3) || mis(d_res, 3) ||
+        (pend && (mis(d_pend_in, 3) || mis(d_pend_out, 3))) || mis(d_work, 7) ||
+        work_bytes < flow_work_bytes(n_pkts, n_flows))
+        return RNS_E_INVALID;
+    if (int st = check_device())
+        return st;
+    FlowArgs a{};
+    a.meta = reinterpret_cast<const uint32_t *>(d_meta);
+    a.flow_in = reinterpret_cast<const uint32_t *>(d_flow_in);
+    a.pend_in = d_pend_in;
+    a.flow_out = reinterpret_cast<uint32_t *>(d_flow_out);
+    a.pend_out = d_pend_out;
+    a.seg = reinterpret_cast<uint32_t *>(d_seg);
+    a.res = reinterpret_cast<uint32_t *>(d_res);
+    a.part = static_cast<uint2 *>(d_work);
+    a.cnt = static_cast<uint32_t *>(d_work) + 2 * (scan_blocks(n_flows) + 1);
+    a.cursor = a.cnt + n_flows;
+    a.longs = a.cursor + n_flows;
+    a.list = a.longs + n_flows;
+    a.n_pkts = n_pkts;
+    a.n_flows = n_flows;
+    a.pend_cap = pend_cap;
+    return launch_flow_update(a, static_cast<hipStream_t>(stream));
+}
+
+int rns_tx_ack_build_dev(const rns_rx_tcp_meta *d_meta, const rns_rx_tcp_seg *d_seg, uint32_t n_pkts,
+                         const rns_tcp_flow *d_flow, uint32_t n_flows, const uint8_t *d_tmpl, uint32_t tmpl_stride,
+                         const uint8_t *d_head_len8, uint16_t ip_id_base, void *d_work, uint64_t work_bytes,
+                         uint8_t *d_out, uint32_t ack_cap, uint32_t *d_ack_src, uint8_t *d_ack_len8, uint32_t *d_n_acks,
+                         void *stream)
+{
+    const auto mis = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    if (!d_n_acks || n_pkts > RNS_CHAIN_MAX_PACKETS ||
+        (n_pkts && (!d_meta || !d_seg || !d_work || work_bytes < ack_work_bytes(n_pkts))) ||
+        (n_pkts && n_flows && (!d_flow || !d_tmpl || !d_head_len8 || !tmpl_stride)) ||
+        (ack_cap && (!d_out || !d_ack_src || !d_ack_len8)) || mis(d_meta, 3) || mis(d_seg, 3) || mis(d_flow, 3) ||
+        mis(d_out, 3) || mis(d_ack_src, 3) || mis(d_n_acks, 3) || mis(d_work, 7))
+        return RNS_E_INVALID;
+    if (int st = check_device())
+        return st;
+    AckArgs a{};
+    a.meta = reinterpret_cast<const uint32_t *>(d_meta);
+    a.seg = reinterpret_cast<const uint32_t *>(d_seg);
+    a.flow = reinterpret_cast<const uint32_t *>(d_flow);
+    a.tmpl = d_tmpl;
+    a.head_len8 = d_head_len8;
+    a.out = d_out;
+    a.ack_src = d_ack_src;
+    a.ack_len8 = d_ack_len8;
+    a.n_acks = d_n_acks;
+    a.part = static_cast<uint2 *>(d_work);
+    a.n_pkts = n_pkts;
+    a.n_flows = n_flows;
+    a.tmpl_stride = tmpl_stride;
+    a.ip_id_base = ip_id_base;
+    a.ack_cap = ack_cap;
+    return launch_ack_build(a, static_cast<hipStream_t>(stream));
+}
+
 int rns_tx_fill_packed_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_blk_off, const uint16_t *d_len16,
                            uint32_t align_log2, uint32_t n, uint8_t *d_status, uint32_t len_hint, void *stream)
 {

@@ -40,3 +40,4 @@
 #include "rns_k_pool_tx.hpp"
 #include "rns_k_segment.hpp"
 #include "rns_k_pool_place.hpp"
+#include "rns_k_flow.hpp"

@@ -51,6 +51,14 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              (the floor of a two-pass design on payloads that were already contiguous), in alternating
              rounds; every row carries descriptor bytes and read / written bytes per datagram.  Timed once
              per run, whatever --configs names
+* rx_flow  — rns_rx_tcp_flow_update_dev + rns_tx_ack_build_dev behind the placement, over RxPlaceBatch's
+             shapes in order (the records do not depend on the buffers' order), the flows' state set so
+             that every segment is consumed; a flow takes at most RNS_FLOW_MAX_SEGS segments per call, so
+             a batch with more per flow (imix: 8192) goes through in slices of flows x 1024 datagrams
+             with the state carried.  Timed in alternating rounds: the placement alone, the update
+             alone, the build alone and all three; and, for the other extreme, 2^20 flows with one
+             synthetic segment each.  The rows carry the added passes as a ratio to the placement and
+             their record traffic against the floor of 24 B read + 8 B written per datagram
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -186,6 +194,10 @@ def main():
             for shape in args.place_shapes.split(","):
                 for shuffled in (False, True):
                     r.update(bench_rx_place(shape, dev, args, shuffled))
+        if "rx_flow" in ops and cfg == args.configs.split(",")[0]:
+            for shape in args.place_shapes.split(","):
+                r.update(bench_rx_flow(shape, dev, args))
+            r.update(bench_rx_flow_wide(dev, args))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -670,6 +682,140 @@ def bench_rx_place(shape, dev, args, shuffled):
     del rb, src
     torch.cuda.empty_cache()
     return res
+
+
+def _flow_templates(nfl, dev):
+    """One IPv4 template head per flow (local -> 10.1.x.y, the ports of RxPlaceBatch's flows), 64 bytes apart."""
+    from rustnetworkstack_amd.workloads import LOCAL4
+    f = np.arange(nfl)
+    t = np.zeros((nfl, 64), dtype=np.uint8)
+    t[:, 0], t[:, 8], t[:, 9] = 0x45, 64, 6
+    t[:, 12:16] = np.frombuffer(LOCAL4, dtype=np.uint8)
+    t[:, 16], t[:, 17], t[:, 18], t[:, 19] = 10, 1, (f >> 8) & 0xFF, f & 0xFF
+    sport = 40000 + (f % 20000)
+    t[:, 20], t[:, 21], t[:, 22], t[:, 23] = 0, 80, sport >> 8, sport & 0xFF
+    t[:, 32] = 0x50
+    return torch.from_numpy(t).to(dev), torch.full((nfl,), 40, dtype=torch.uint8, device=dev)
+
+
+def _flow_rows(n, nfl, rs, names):
+    med = {k: r[len(r) // 2] for k, r in zip(names, rs)}
+    out = {k + "_us": round(v * 1e3, 1) for k, v in med.items()}
+    out.update({k + "_rounds_us": [round(x * 1e3, 1) for x in r] for k, r in zip(names, rs)})
+    out["datagrams"], out["flows"] = n, nfl
+    return out, med
+
+
+def bench_rx_flow(shape, dev, args):
+    """The flow update and the ACK build behind the placement (see the module docstring)."""
+    from rustnetworkstack_amd import _lib
+    from rustnetworkstack_amd.flow import FLOW_DTYPE, RES_DTYPE, flow_update_work, rx_tcp_flow_update, tx_ack_build
+    from rustnetworkstack_amd.batch import rx_tcp_place_pool
+    from rustnetworkstack_amd.workloads import LOCAL4, LOCAL6
+    n = args.place_n or (1 << 20 if shape == "bulk" else 1 << 23)
+    nfl = args.place_flows
+    rb = RxPlaceBatch(shape, dev, n, nfl, False)
+    place = lambda: rx_tcp_place_pool(rb.pool, rb.d_buf_idx, rb.d_blk_first, rb.d_len16, LOCAL4, LOCAL6,  # noqa: E731
+                                      rb.d_table, rb.d_next_seq, rb.d_win_off, rb.d_win_len, rb.stream,
+                                      status=rb.status, l4_sum=rb.l4_sum, meta=rb.meta)
+    place()
+    chunk = min(n, nfl * _lib.RNS_FLOW_MAX_SEGS)                     # datagram i is flow i % nfl's: 1024 per flow and slice
+    slices = [(a, min(n, a + chunk)) for a in range(0, n, chunk)]
+    fl0 = np.zeros(nfl, dtype=FLOW_DTYPE)
+    fl0["rcv_nxt"] = fl0["rcv_max"] = rb.d_next_seq.cpu().numpy().view(np.uint32)
+    fl0["snd_wl1"], fl0["state"] = (fl0["rcv_nxt"] - 1) & 0xFFFFFFFF, _lib.RNS_TCP_ESTABLISHED
+    d_fl = [torch.from_numpy(fl0.view(np.uint8)).to(dev)] + [torch.empty(nfl * 40, dtype=torch.uint8, device=dev)
+                                                            for _ in range(2)]
+    cap = 4
+    d_pd = [torch.zeros(nfl * cap * 2, dtype=torch.int32, device=dev) for _ in range(3)]
+    seg = torch.empty((n, 8), dtype=torch.uint8, device=dev)
+    res = torch.empty((len(slices), nfl, 24), dtype=torch.uint8, device=dev)
+    work = torch.empty(flow_update_work(chunk, nfl), dtype=torch.uint8, device=dev)
+    tmpl, hl8 = _flow_templates(nfl, dev)
+    ack_cap = chunk // 5 + nfl
+    out = torch.empty((ack_cap, 64), dtype=torch.uint8, device=dev)
+    src, ln8 = torch.empty(ack_cap, dtype=torch.int32, device=dev), torch.empty(ack_cap, dtype=torch.uint8, device=dev)
+    n_acks = torch.empty((len(slices), 2), dtype=torch.int32, device=dev)
+    meta = rb.meta.reshape(-1)
+
+    def io(k):                                                       # slice k reads state k's, writes state k + 1's
+        return (0 if k == 0 else 1 + (k - 1) % 2), 1 + k % 2
+
+    def update():
+        for k, (a, b) in enumerate(slices):
+            i, o = io(k)
+            rx_tcp_flow_update(meta[24 * a:24 * b], d_fl[i], d_pd[i], pend_cap=cap, flows_out=d_fl[o], pend_out=d_pd[o],
+                               seg=seg[a:b].reshape(-1), res=res[k].reshape(-1), work=work)
+
+    def build():
+        for k, (a, b) in enumerate(slices):
+            tx_ack_build(meta[24 * a:24 * b], seg[a:b].reshape(-1), d_fl[io(k)[1]], tmpl, hl8, 1, ack_cap=ack_cap, out=out,
+                         ack_src=src, ack_len8=ln8, n_acks=n_acks[k], work=work)
+
+    def both():
+        for k, (a, b) in enumerate(slices):
+            i, o = io(k)
+            rx_tcp_flow_update(meta[24 * a:24 * b], d_fl[i], d_pd[i], pend_cap=cap, flows_out=d_fl[o], pend_out=d_pd[o],
+                               seg=seg[a:b].reshape(-1), res=res[k].reshape(-1), work=work)
+            tx_ack_build(meta[24 * a:24 * b], seg[a:b].reshape(-1), d_fl[o], tmpl, hl8, 1, ack_cap=ack_cap, out=out,
+                         ack_src=src, ack_len8=ln8, n_acks=n_acks[k], work=work)
+
+    def all3():
+        place()
+        both()
+
+    both()
+    torch.cuda.synchronize()
+    r = res.cpu().numpy().reshape(-1).view(RES_DTYPE)
+    acks = n_acks.cpu().numpy()
+    names = ("place", "update", "build", "all")
+    row, med = _flow_rows(n, nfl, timed_rounds([place, update, build, all3], args.steps, args.rounds), names)
+    added = med["all"] - med["place"]
+    row.update({"slices": len(slices), "consumed": int(r["consumed"].sum()), "stopped_flows": int((r["why"] != 0).sum()),
+                "readable_bytes": int(r["readable"].astype(np.int64).sum()), "payload_bytes": rb.pay_total,
+                "acks": int(acks[:, 0].sum()), "acks_written_last_slice": int(min(ack_cap, acks[-1, 0])),
+                "added_us": round(added * 1e3, 1), "added_ratio_to_place": round(added / med["place"], 4),
+                "record_floor_bytes": 32 * n, "added_GBps_of_floor": round(32 * n / added / 1e6, 1),
+                "update_GBps_of_floor": round(32 * n / med["update"] / 1e6, 1)})
+    del rb
+    torch.cuda.empty_cache()
+    return {f"rx_flow_{shape}": row}
+
+
+def bench_rx_flow_wide(dev, args, nfl=1 << 20):
+    """2^20 flows, one in-order 1460-byte segment each (synthetic records, the flows in a shuffled order):
+    the update and the build alone."""
+    from rustnetworkstack_amd import _lib
+    from rustnetworkstack_amd.flow import FLOW_DTYPE, RES_DTYPE, flow_update_work, rx_tcp_flow_update, tx_ack_build
+    from rustnetworkstack_amd.place import META_DTYPE
+    order = np.random.default_rng(20).permutation(nfl).astype(np.uint32)
+    m = np.zeros(nfl, dtype=META_DTYPE)
+    m["flow"], m["seq"], m["pay_len"], m["flags"], m["ip_hdr"], m["tcp_hdr"], m["place"] = order, 7 * order, 1460, 0x18, 20, 20, 7
+    fl = np.zeros(nfl, dtype=FLOW_DTYPE)
+    f = np.arange(nfl, dtype=np.uint32)
+    fl["rcv_nxt"] = fl["rcv_max"] = 7 * f
+    fl["delayed_acks"], fl["state"] = f % 5, _lib.RNS_TCP_ESTABLISHED
+    t = lambda a: torch.from_numpy(a.view(np.uint8)).to(dev)  # noqa: E731
+    meta, d_fl = t(m), t(fl)
+    fl_out, seg = torch.empty_like(d_fl), torch.empty(nfl * 8, dtype=torch.uint8, device=dev)
+    res = torch.empty(nfl * 24, dtype=torch.uint8, device=dev)
+    work = torch.empty(flow_update_work(nfl, nfl), dtype=torch.uint8, device=dev)
+    tmpl, hl8 = _flow_templates(nfl, dev)
+    ack_cap = nfl // 4
+    out = torch.empty((ack_cap, 64), dtype=torch.uint8, device=dev)
+    src, ln8 = torch.empty(ack_cap, dtype=torch.int32, device=dev), torch.empty(ack_cap, dtype=torch.uint8, device=dev)
+    n_acks = torch.empty(2, dtype=torch.int32, device=dev)
+    update = lambda: rx_tcp_flow_update(meta, d_fl, None, pend_cap=0, flows_out=fl_out, seg=seg, res=res, work=work)  # noqa: E731
+    build = lambda: tx_ack_build(meta, seg, fl_out, tmpl, hl8, 1, ack_cap=ack_cap, out=out, ack_src=src, ack_len8=ln8,  # noqa: E731
+                                 n_acks=n_acks, work=work)
+    update()
+    build()
+    torch.cuda.synchronize()
+    r = res.cpu().numpy().view(RES_DTYPE)
+    row, med = _flow_rows(nfl, nfl, timed_rounds([update, build], args.steps, args.rounds), ("update", "build"))
+    row.update({"consumed": int(r["consumed"].sum()), "acks": int(n_acks[0].item()),
+                "update_GBps_of_floor": round(32 * nfl / med["update"] / 1e6, 1)})
+    return {"rx_flow_1M_flows_x1": row}
 
 
 def bench_chain_netbuf(lay, dev, args, shuffled=False, runs=False):
