@@ -592,6 +592,96 @@ int rns_tx_ack_build_dev(const rns_rx_tcp_meta *d_meta, const rns_rx_tcp_seg *d_
                          uint8_t *d_out, uint32_t ack_cap, uint32_t *d_ack_src, uint8_t *d_ack_len8,
                          uint32_t *d_n_acks /* 2 */, void *stream);
 
+/* TCP send planning: tcp_write's window gate (tcp.rs:256-292) and retransmit (tcp.rs:329-348) on the
+ * device, with the head fields send_packet sets (tcp.rs:402-447).  It reads the flow records where
+ * rns_rx_tcp_flow_update_dev left them and writes exactly the descriptor set rns_tx_segment_dev takes,
+ * so place -> update -> ACK build -> plan -> segment is one stream of launches.
+ *   The send buffer: flow f's bytes lie contiguous in the arena rns_tx_segment_dev will get; the byte
+ *     with sequence number d_sq_seq[f] is at d_sq_off[f] and d_sq_len[f] bytes follow it — the
+ *     retransmit queue [snd_una, snd_nxt), then the data tcp_write has not sent.  The byte of sequence
+ *     s is at sq_off + (s - sq_seq mod 2^32).  ACKs move snd_una only, so the host leaves the three
+ *     arrays alone between batches.  inflight = snd_nxt - snd_una, a = snd_una - sq_seq, unsent =
+ *     sq_len - a - inflight.  The planner never touches the arena.
+ *   Stops, tested in this order; a stopped flow plans nothing, both its entries are empty and
+ *   d_flow_out[f] == d_flow_in[f] bytewise:
+ *     RNS_PLAN_STATE  state != RNS_TCP_ESTABLISHED.
+ *     RNS_PLAN_BAD    mss == 0; sq_len, snd_wnd or inflight above 0x3fffffff; a > sq_len; a + inflight >
+ *                     sq_len.  Inside this domain no seq_gt of the reference's loop wraps, so the
+ *                     closed form below equals it; outside, the host decides.
+ *     RNS_PLAN_TMPL   the template rule of rns_tx_ack_build_dev: hl = d_head_len8[f] is 40 or 60, hl <=
+ *                     tmpl_stride, IPv4 (40) has t[0] == 0x45 and t[9] == 6, IPv6 (60) t[0] >> 4 == 6
+ *                     and t[6] == 6, the TCP data offset is 5.
+ *   Entries: flow f owns entries 2f and 2f + 1 of the E = 2 * n_flows entries, in that order — one of
+ *   the orders the socket mutex allows between the timer thread and the writer, fixed here.
+ *     2f, retransmit: if d_rexmit is non-NULL, d_rexmit[f] != 0 and inflight > 0, one segment of
+ *       min(mss, inflight) bytes from the byte of snd_una.  Its sequence field is snd_nxt, NOT
+ *       snd_una: the reference's send_packet puts send_next_seq into retransmitted data too
+ *       (tcp.rs:439).  That is pinned as it is.
+ *     2f + 1, new data (data = the unsent bytes): pieces of min(remaining, mss) go while
+ *       !seq_gt(snd_nxt + piece, snd_una + snd_wnd); the first piece that fails ends the loop with why
+ *       = RNS_PLAN_WINDOW (tcp_write would wait there).  So the entry is pay_off = the byte of snd_nxt,
+ *       pay_len = the planned bytes — whole pieces, and the tail piece when everything fits — and mss.
+ *       d_flow_out[f].snd_nxt += pay_len; every other field is copied.
+ *   Template rows: the row of an entry with segments (d_tmpl_out + e * tmpl_stride) is the flow's
+ *   template (d_tmpl + f * tmpl_stride) with TCP [4..8] = snd_nxt as it is before this flow's new
+ *   data, [8..12] = rcv_nxt, [12] = 0x50, [13] = 0x18 (ACK|PSH), [14..16] = (0xffff - (rq_len &
+ *   0xffff)) & 0xffff, and IPv4 [4..6] = ip_id_base + *d_ip_id_add + (the IPv4 segments of all earlier
+ *   kept entries) mod 2^16; rns_tx_segment_dev adds j per segment, so the ids are NEXT_PACKET_ID's in
+ *   entry order.  Only bytes [0, hl) of such a row are written; rows of empty entries are not written.
+ *   Layout: d_seg_first is the exclusive prefix sum of the entries' segment counts (E + 1 entries),
+ *   d_head_off[e] = head_first_off + the head bytes (segments * hl) of the earlier entries, held in 64
+ *   bits.  Cap: an entry whose inclusive segment prefix exceeds seg_cap is dropped, and so is every
+ *   later non-empty one — the kept entries are a prefix.  A dropped entry gets pay_len = 0; a flow
+ *   whose new-data entry was dropped gets why = RNS_PLAN_CAP and snd_nxt not advanced; a dropped
+ *   retransmit gives rexmit_bytes = 0.  (The prefix that decides this counts every entry at most seg_cap
+ *   + 1 segments, mod 2^32: it is exact while those counts sum below 2^32.)  For the kept total N =
+ *   d_n[0] (d_n[1]: the IPv4 segments among them), d_seg_first, d_head_off and the first (N + 63) / 64
+ *   entries of d_blk_flow equal what rns_tx_segment_layout gives for the written pay_len / mss /
+ *   head_len8, and d_blk_flow[b] = E for every block from there to (seg_cap + 63) / 64.  So
+ *   rns_tx_segment_dev(n_flows = E) may be launched with n_seg = N after reading d_n, or with n_seg =
+ *   seg_cap without reading anything: a segment at or past N finds no entry that covers it and gets
+ *   RNS_TX_MALFORMED, no byte written (the one 64-segment block that straddles N walks d_seg_first to
+ *   its end to learn that).
+ *   Every output array is written in full on every call; d_head_len8_out[e] and d_mss_out[e] are the
+ *   flow's values for both entries, d_pay_off is 0 for an empty entry.  n_flows == 0 writes
+ *   d_seg_first[0] = 0, d_n = {0, 0} and d_blk_flow (zeros), and needs no other array.  Whatever the
+ *   inputs hold, nothing outside the argument arrays is read or written.  The in and out arrays must
+ *   not overlap.  The call allocates nothing: d_work is the caller's, at least rns_tx_tcp_plan_work
+ *   bytes; its contents before and after the call mean nothing.
+ * n_flows > 2^30, seg_cap > RNS_CHAIN_MAX_PACKETS, tmpl_stride == 0, a NULL d_seg_first or d_n, a NULL
+ * d_blk_flow with seg_cap > 0, with n_flows > 0 any other NULL pointer but d_rexmit and d_ip_id_add, an
+ * array that is not aligned to its elements (2 bytes for the u16 arrays, 4 for the u32 arrays, the flow
+ * records and the results, 8 for the u64 arrays and d_work) or work_bytes below the need is
+ * RNS_E_INVALID, all before the device is touched. */
+typedef struct rns_tx_plan_res {   /* 16 bytes */
+    uint32_t new_bytes;     /* bytes of new data planned (snd_nxt advanced by this) */
+    uint32_t new_segs;      /* their segments */
+    uint32_t rexmit_bytes;  /* bytes of the one retransmitted piece, 0 if none */
+    uint8_t  why;           /* RNS_PLAN_* */
+    uint8_t  pad[3];        /* zero */
+} rns_tx_plan_res;
+#define RNS_PLAN_NONE   0u  /* all queued data was planned (or there was none) */
+#define RNS_PLAN_WINDOW 1u  /* tcp_write would wait: unsent bytes remain behind the window */
+#define RNS_PLAN_STATE  2u
+#define RNS_PLAN_BAD    3u
+#define RNS_PLAN_TMPL   4u
+#define RNS_PLAN_CAP    5u  /* seg_cap reached: the entry and every later one are dropped */
+int rns_tx_tcp_plan_dev(const rns_tcp_flow *d_flow_in, rns_tcp_flow *d_flow_out, uint32_t n_flows,
+                        const uint64_t *d_sq_off, const uint32_t *d_sq_seq, const uint32_t *d_sq_len, /* n_flows: send buffer */
+                        const uint16_t *d_mss, const uint8_t *d_rexmit /* optional */,
+                        const uint8_t *d_tmpl, uint32_t tmpl_stride, const uint8_t *d_head_len8,
+                        uint16_t ip_id_base, const uint32_t *d_ip_id_add /* optional: one device dword added to the base */,
+                        uint64_t head_first_off, uint32_t seg_cap,
+                        /* outputs: rns_tx_segment_dev's descriptors over E = 2 * n_flows entries */
+                        uint8_t *d_tmpl_out, uint8_t *d_head_len8_out, uint64_t *d_pay_off, uint32_t *d_pay_len,
+                        uint16_t *d_mss_out, uint64_t *d_head_off, uint32_t *d_seg_first /* E + 1 */,
+                        uint32_t *d_blk_flow /* (seg_cap + 63) / 64 */, uint32_t *d_n /* 2: segments, IPv4 segments */,
+                        rns_tx_plan_res *d_res, void *d_work, uint64_t work_bytes, void *stream);
+
+/* The workspace of rns_tx_tcp_plan_dev (CPU only): *bytes for n_flows flows, monotone.  A NULL bytes or
+ * n_flows > 2^30 is RNS_E_INVALID. */
+int rns_tx_tcp_plan_work(uint32_t n_flows, uint64_t *bytes);
+
 /* Transmit finalize (SURVEY a6, §8f row 2 for whole datagrams): for each finished
  * outgoing IP datagram d_arena[d_off[i] .. + d_len[i]), the checksums the stack's
  * transmit path stores — tcp_output (tcp.rs:957-973: pseudo-header from the header's

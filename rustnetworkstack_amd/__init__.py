@@ -14,16 +14,19 @@
 * ``flow``      — TCP flow update and ACK build: tcp_input's Established path over the placement's
                   records, per flow in batch order, and the pure ACKs it sends, on the device; the
                   same walk on the host for what the device stops at (also ``batch.*``);
+* ``send``      — TCP send planning: tcp_write's window gate and retransmit over the flow records on
+                  the device, into the segmentation offload's descriptors; the same plan on the host
+                  (also ``batch.*``);
 * ``workloads`` — the synthetic packet batches BASELINE.json's configs name.
 """
 from . import _lib, util  # noqa: F401
 from ._lib import ChecksumError, ChecksumLibraryMissing  # noqa: F401
 
-__all__ = ["util", "batch", "pool", "segment", "place", "flow", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
+__all__ = ["util", "batch", "pool", "segment", "place", "flow", "send", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
 
 
 def __getattr__(name):
-    if name in ("batch", "pool", "segment", "place", "flow", "workloads"):
+    if name in ("batch", "pool", "segment", "place", "flow", "send", "workloads"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -47,6 +47,8 @@ RNS_SEG_ACK = 0x02
 RNS_SEG_TIMER = 0x04
 RNS_EV_WND = 0x01
 RNS_STOP_NONE, RNS_STOP_MANY, RNS_STOP_STATE, RNS_STOP_FLAGS, RNS_STOP_OPTIONS, RNS_STOP_OUTSIDE, RNS_STOP_PEND = range(7)
+RNS_PLAN_NONE, RNS_PLAN_WINDOW, RNS_PLAN_STATE, RNS_PLAN_BAD, RNS_PLAN_TMPL, RNS_PLAN_CAP = range(6)  # rns_tx_plan_res.why
+RNS_PLAN_MAX = 0x3FFFFFFF  # the planner's domain: sq_len, snd_wnd and inflight at most this
 RNS_TX_IP_FILLED = 0x01
 RNS_TX_L4_FILLED = 0x02
 RNS_TX_MALFORMED = 0x80
@@ -79,6 +81,8 @@ EXPORTED_SYMBOLS = (
     "rns_rx_tcp_flow_update_dev",
     "rns_rx_tcp_flow_update_work",
     "rns_tx_ack_build_dev",
+    "rns_tx_tcp_plan_dev",
+    "rns_tx_tcp_plan_work",
     "rns_tx_fill_dev",
     "rns_tx_fill_packed_dev",
     "rns_tx_fill_chain_dev",
@@ -178,6 +182,9 @@ _SIGNATURES = {
     "rns_rx_tcp_flow_update_work": (_int, [_u32, _u32, ctypes.POINTER(_u64)]),
     "rns_tx_ack_build_dev": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u16, _vp, _u64, _vp, _u32, _vp, _vp, _vp,
                                     _vp]),
+    "rns_tx_tcp_plan_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u16, _vp, _u64, _u32, _vp, _vp,
+                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "rns_tx_tcp_plan_work": (_int, [_u32, ctypes.POINTER(_u64)]),
     "rns_tx_fill_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _vp]),
     "rns_tx_fill_packed_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _u32, _vp, _u32, _vp]),
     "rns_tx_fill_chain_dev": (_int, [_vp, _u64, _vp, _vp, _u32, _vp, _u32, _vp, _vp]),

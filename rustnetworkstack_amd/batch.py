@@ -811,6 +811,9 @@ _PLACE_API = ("META_DTYPE", "Reassembler", "meta_records", "rx_flow_table", "rx_
 # and the TCP flow update and ACK build (flow.py): batch.rx_tcp_flow_update, batch.tx_ack_build, batch.flow_update_host.
 _FLOW_API = ("FLOW_DTYPE", "RES_DTYPE", "SEG_DTYPE", "flow_update_host", "flow_update_work", "rx_tcp_flow_update",
              "tx_ack_build")
+# and TCP send planning (send.py): batch.tx_tcp_plan, batch.tx_tcp_send, batch.plan_host, batch.tx_plan_work,
+# batch.PLAN_RES_DTYPE (send.RES_DTYPE: RES_DTYPE here is the flow update's).
+_SEND_API = ("PLAN_RES_DTYPE", "plan_host", "tx_plan_work", "tx_tcp_plan", "tx_tcp_send")
 
 
 def __getattr__(name):
@@ -826,4 +829,7 @@ def __getattr__(name):
     if name in _FLOW_API:
         from . import flow
         return getattr(flow, name)
+    if name in _SEND_API:
+        from . import send
+        return getattr(send, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -21,6 +21,12 @@ uint32_t blocks_of(uint64_t n) { return static_cast<uint32_t>(scan_blocks(n)); }
 
 }  // namespace
 
+int launch_scan2_parts(uint2 *part, uint32_t nb, uint32_t *total2, hipStream_t st)
+{
+    RNS_LAUNCH(scan2_parts_kernel, 1, kScanBlock, st, part, nb, total2);
+    return RNS_OK;
+}
+
 int launch_flow_update(const FlowArgs &a, hipStream_t st)
 {
     if (a.n_flows == 0) {  // every datagram's record is zero

@@ -541,6 +541,58 @@ int rns_tx_ack_build_dev(const rns_rx_tcp_meta *d_meta, const rns_rx_tcp_seg *d_
     return launch_ack_build(a, static_cast<hipStream_t>(stream));
 }
 
+int rns_tx_tcp_plan_dev(const rns_tcp_flow *d_flow_in, rns_tcp_flow *d_flow_out, uint32_t n_flows, const uint64_t *d_sq_off,
+                        const uint32_t *d_sq_seq, const uint32_t *d_sq_len, const uint16_t *d_mss, const uint8_t *d_rexmit,
+                        const uint8_t *d_tmpl, uint32_t tmpl_stride, const uint8_t *d_head_len8, uint16_t ip_id_base,
+                        const uint32_t *d_ip_id_add, uint64_t head_first_off, uint32_t seg_cap, uint8_t *d_tmpl_out,
+                        uint8_t *d_head_len8_out, uint64_t *d_pay_off, uint32_t *d_pay_len, uint16_t *d_mss_out,
+                        uint64_t *d_head_off, uint32_t *d_seg_first, uint32_t *d_blk_flow, uint32_t *d_n,
+                        rns_tx_plan_res *d_res, void *d_work, uint64_t work_bytes, void *stream)
+{
+    static_assert(sizeof(rns_tx_plan_res) == 4 * kPlanResDw, "rns_k_plan.hpp");
+    const auto mis = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    if (n_flows > kPlanMaxFlows || seg_cap > RNS_CHAIN_MAX_PACKETS || !tmpl_stride || !d_seg_first || !d_n ||
+        (seg_cap && !d_blk_flow) ||
+        (n_flows && (!d_flow_in || !d_flow_out || !d_sq_off || !d_sq_seq || !d_sq_len || !d_mss || !d_tmpl || !d_head_len8 ||
+                     !d_tmpl_out || !d_head_len8_out || !d_pay_off || !d_pay_len || !d_mss_out || !d_head_off || !d_res ||
+                     !d_work || work_bytes < plan_work_bytes(n_flows))) ||
+        mis(d_flow_in, 3) || mis(d_flow_out, 3) || mis(d_sq_off, 7) || mis(d_sq_seq, 3) || mis(d_sq_len, 3) || mis(d_mss, 1) ||
+        mis(d_ip_id_add, 3) || mis(d_pay_off, 7) || mis(d_pay_len, 3) || mis(d_mss_out, 1) || mis(d_head_off, 7) ||
+        mis(d_seg_first, 3) || mis(d_blk_flow, 3) || mis(d_n, 3) || mis(d_res, 3) || mis(d_work, 7))
+        return RNS_E_INVALID;
+    if (int st = check_device())
+        return st;
+    PlanArgs a{};
+    a.flow_in = reinterpret_cast<const uint32_t *>(d_flow_in);
+    a.flow_out = reinterpret_cast<uint32_t *>(d_flow_out);
+    a.sq_off = d_sq_off;
+    a.sq_seq = d_sq_seq;
+    a.sq_len = d_sq_len;
+    a.mss = d_mss;
+    a.rexmit = d_rexmit;
+    a.tmpl = d_tmpl;
+    a.head_len8 = d_head_len8;
+    a.ip_id_add = d_ip_id_add;
+    a.tmpl_out = d_tmpl_out;
+    a.head_len8_out = d_head_len8_out;
+    a.pay_off = d_pay_off;
+    a.pay_len = d_pay_len;
+    a.mss_out = d_mss_out;
+    a.head_off = d_head_off;
+    a.seg_first = d_seg_first;
+    a.blk_flow = d_blk_flow;
+    a.n_out = d_n;
+    a.res = reinterpret_cast<uint32_t *>(d_res);
+    a.part = static_cast<uint2 *>(d_work);
+    a.rec = a.part + scan_blocks(2ull * n_flows) + 2;
+    a.head_first_off = head_first_off;
+    a.n_flows = n_flows;
+    a.tmpl_stride = tmpl_stride;
+    a.ip_id_base = ip_id_base;
+    a.seg_cap = seg_cap;
+    return launch_tx_plan(a, static_cast<hipStream_t>(stream));
+}
+
 int rns_tx_fill_packed_dev(uint8_t *d_arena, uint64_t arena_bytes, const uint64_t *d_blk_off, const uint16_t *d_len16,
                            uint32_t align_log2, uint32_t n, uint8_t *d_status, uint32_t len_hint, void *stream)
 {

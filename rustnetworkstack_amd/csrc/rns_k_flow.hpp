@@ -81,8 +81,9 @@ struct AckArgs {
 };
 
 // The kernels are no templates, so one translation unit alone compiles them: k_flow.hip, which
-// launches them, defines RNS_FLOW_KERNELS.
-#ifdef RNS_FLOW_KERNELS
+// launches them, defines RNS_FLOW_KERNELS.  (k_plan.hip, with RNS_PLAN_KERNELS, takes the scan's block
+// function and its reduce template from here and launches the parts kernel through k_flow.hip.)
+#if defined(RNS_FLOW_KERNELS) || defined(RNS_PLAN_KERNELS)
 
 // --- the scan: pairs of u32, 256 per workgroup ---
 __device__ __forceinline__ uint2 scan2_block(uint2 v, uint2 &total)
@@ -120,6 +121,9 @@ __global__ __launch_bounds__(kScanBlock) void scan2_reduce_kernel(const A a, uin
     if (threadIdx.x == 0)
         part[blockIdx.x] = total;
 }
+
+#endif  // RNS_FLOW_KERNELS || RNS_PLAN_KERNELS
+#ifdef RNS_FLOW_KERNELS
 
 // part[0..nb) to its exclusive prefix sums, part[nb] = the total (and *total2, when given): one workgroup
 __global__ __launch_bounds__(kScanBlock) void scan2_parts_kernel(uint2 *part, uint32_t nb, uint32_t *total2)

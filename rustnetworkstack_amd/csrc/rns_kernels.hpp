@@ -41,3 +41,4 @@
 #include "rns_k_segment.hpp"
 #include "rns_k_pool_place.hpp"
 #include "rns_k_flow.hpp"
+#include "rns_k_plan.hpp"

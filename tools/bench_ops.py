@@ -59,6 +59,13 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              alone, the build alone and all three; and, for the other extreme, 2^20 flows with one
              synthetic segment each.  The rows carry the added passes as a ratio to the placement and
              their record traffic against the floor of 24 B read + 8 B written per datagram
+* tx_plan  — rns_tx_tcp_plan_dev in front of rns_tx_segment_dev: flows with nothing in flight, an open
+             window and k whole segments of 1460 bytes queued (1024 flows x 44, and 2^20 flows x 1), no
+             retransmits.  Timed in alternating rounds: (a) the segmentation alone from descriptors over
+             the flows that the host laid out beforehand (rns_tx_segment_layout, templates patched on the
+             host), (b) the plan and then the segmentation on the planned descriptors, (c) the plan
+             alone; the head bytes of (a) and (b) are compared before timing.  Timed once per run,
+             whatever --configs names
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -198,6 +205,9 @@ def main():
             for shape in args.place_shapes.split(","):
                 r.update(bench_rx_flow(shape, dev, args))
             r.update(bench_rx_flow_wide(dev, args))
+        if "tx_plan" in ops and cfg == args.configs.split(",")[0]:
+            for nfl, k in ((1024, 44), (1 << 20, 1)):
+                r.update(bench_tx_plan(nfl, k, dev, args))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -816,6 +826,84 @@ def bench_rx_flow_wide(dev, args, nfl=1 << 20):
     row.update({"consumed": int(r["consumed"].sum()), "acks": int(n_acks[0].item()),
                 "update_GBps_of_floor": round(32 * nfl / med["update"] / 1e6, 1)})
     return {"rx_flow_1M_flows_x1": row}
+
+
+def bench_tx_plan(nfl, k, dev, args, mss=1460):
+    """The send planner in front of the segmentation offload (see the module docstring): nfl flows, k whole
+    segments queued each."""
+    from rustnetworkstack_amd import _lib
+    from rustnetworkstack_amd.batch import _stream_handle, fill_splitmix64
+    from rustnetworkstack_amd.flow import FLOW_DTYPE
+    from rustnetworkstack_amd.segment import tx_segment_layout
+    from rustnetworkstack_amd.send import RES_DTYPE, tx_plan_work
+    n, E, per = nfl * k, 2 * nfl, k * mss
+    head_first = (nfl * per + 15) // 16 * 16
+    arena = torch.empty(head_first + 40 * n + 64, dtype=torch.uint8, device=dev)
+    fill_splitmix64(arena, 0x5E9D)
+    f = np.arange(nfl, dtype=np.uint64)
+    fl = np.zeros(nfl, dtype=FLOW_DTYPE)
+    fl["snd_una"] = fl["snd_nxt"] = (0x1000 + 77777 * f) & 0xFFFFFFFF
+    fl["snd_wnd"], fl["rcv_nxt"], fl["rq_len"], fl["state"] = 0xFFFF, (5 + 3 * f) & 0xFFFFFFFF, f & 0xFFF, _lib.RNS_TCP_ESTABLISHED
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)  # noqa: E731
+    d_fl, d_fl_out = t(fl.view(np.uint8)), torch.empty(nfl * 40, dtype=torch.uint8, device=dev)
+    d_sq_off, d_sq_seq = t((f * per).view(np.int64)), t(fl["snd_una"].view(np.int32))
+    d_sq_len, d_mss = t(np.full(nfl, per, dtype=np.int32)), t(np.full(nfl, mss, dtype=np.uint16))
+    tmpl, hl8 = _flow_templates(nfl, dev)
+    new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
+    o = {"tmpl": new((E, 64), torch.uint8), "hl8": new(E, torch.uint8), "pay_off": new(E, torch.int64), "pay_len": new(E, torch.int32),
+         "mss": new(E, torch.uint16), "head_off": new(E, torch.int64), "seg_first": new(E + 1, torch.int32),
+         "blk_flow": new((n + 63) // 64, torch.int32), "n": new(2, torch.int32), "res": new(nfl * 16, torch.uint8)}
+    work = new(tx_plan_work(nfl), torch.uint8)
+    status, status_a = new(n, torch.uint8), new(n, torch.uint8)
+    # (a)'s descriptors: the host's layout over the flows, the templates patched as send_packet fills them
+    th = tmpl.cpu().numpy().copy()
+    be = lambda v, nb: np.stack([(v >> (8 * (nb - 1 - i))) & 0xFF for i in range(nb)], axis=1).astype(np.uint8)  # noqa: E731
+    th[:, 4:6] = be((7 + f * k) & 0xFFFF, 2)
+    th[:, 24:28], th[:, 28:32] = be(fl["snd_nxt"].astype(np.uint64), 4), be(fl["rcv_nxt"].astype(np.uint64), 4)
+    th[:, 32], th[:, 33] = 0x50, 0x18
+    th[:, 34:36] = be((0xFFFF - (fl["rq_len"].astype(np.uint64) & 0xFFFF)) & 0xFFFF, 2)
+    sf, ho, bf, n_seg, _ = tx_segment_layout(np.full(nfl, per), np.full(nfl, mss), np.full(nfl, 40), head_first)
+    assert n_seg == n
+    a = {"tmpl": t(th), "pay_off": d_sq_off, "pay_len": d_sq_len, "mss": d_mss, "head_off": t(ho.view(np.int64)),
+         "seg_first": t(sf.view(np.int32)), "blk_flow": t(bf.view(np.int32))}
+    lib, st = _lib.load(), _stream_handle(dev)
+    p = lambda x: x.data_ptr()  # noqa: E731
+    seg_a_args = (p(arena), arena.numel(), p(a["tmpl"]), 64, p(hl8), p(a["pay_off"]), p(a["pay_len"]), p(a["mss"]),
+                  p(a["head_off"]), p(a["seg_first"]), p(a["blk_flow"]), nfl, n, p(status_a), st)
+    seg_b_args = (p(arena), arena.numel(), p(o["tmpl"]), 64, p(o["hl8"]), p(o["pay_off"]), p(o["pay_len"]), p(o["mss"]),
+                  p(o["head_off"]), p(o["seg_first"]), p(o["blk_flow"]), E, n, p(status), st)
+    plan_args = (p(d_fl), p(d_fl_out), nfl, p(d_sq_off), p(d_sq_seq), p(d_sq_len), p(d_mss), None, p(tmpl), 64, p(hl8), 7, None,
+                 head_first, n, p(o["tmpl"]), p(o["hl8"]), p(o["pay_off"]), p(o["pay_len"]), p(o["mss"]), p(o["head_off"]),
+                 p(o["seg_first"]), p(o["blk_flow"]), p(o["n"]), p(o["res"]), p(work), work.numel(), st)
+
+    def seg_alone():
+        _lib.check(lib.rns_tx_segment_dev(*seg_a_args), "rns_tx_segment_dev")
+
+    def plan():
+        _lib.check(lib.rns_tx_tcp_plan_dev(*plan_args), "rns_tx_tcp_plan_dev")
+
+    def both():
+        plan()
+        _lib.check(lib.rns_tx_segment_dev(*seg_b_args), "rns_tx_segment_dev")
+
+    seg_alone()
+    heads_a = arena[head_first:head_first + 40 * n].clone()
+    arena[head_first:head_first + 40 * n] = 0
+    both()
+    torch.cuda.synchronize()
+    res = o["res"].cpu().numpy().view(RES_DTYPE)
+    same = bool(torch.equal(heads_a, arena[head_first:head_first + 40 * n]))
+    filled = int((status == 3).sum().item())
+    names = ("segment", "plan_segment", "plan")
+    row, med = _flow_rows(n, nfl, timed_rounds([seg_alone, both, plan], args.steps, args.rounds), names)
+    row.update({k2 + "_spread_us": round(row[k2 + "_rounds_us"][-1] - row[k2 + "_rounds_us"][0], 1) for k2 in names})
+    row.update({"segments_planned": int(o["n"][0].item()), "new_bytes": int(res["new_bytes"].astype(np.int64).sum()),
+                "filled": filled, "heads_equal_host_layout": same, "payload_bytes": n * mss,
+                "added_us": round((med["plan_segment"] - med["segment"]) * 1e3, 1),
+                "added_ratio_to_segment": round((med["plan_segment"] - med["segment"]) / med["segment"], 4)})
+    del arena, heads_a
+    torch.cuda.empty_cache()
+    return {f"tx_plan_{nfl}_flows_x{k}": row}
 
 
 def bench_chain_netbuf(lay, dev, args, shuffled=False, runs=False):
