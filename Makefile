@@ -16,10 +16,12 @@ LIB      := $(PKG)/librns_checksum.so
 # tests/test_c_caller_tx_pool.py (the transmit finalize over pool buffers),
 # tests/test_c_caller_tx_segment.py (TCP segmentation offload),
 # tests/test_c_caller_rx_place.py (TCP receive placement), tests/test_c_caller_rx_flow.py (TCP flow
-# update and ACK build) and tests/test_c_caller_tx_plan.py (TCP send planning, then segmentation).
+# update and ACK build), tests/test_c_caller_tx_plan.py (TCP send planning, then segmentation) and
+# tests/test_c_caller_icmp_echo.py (the ICMP echo responder).
 CABI_TESTS := tests/c/test_batch_abi tests/c/test_tx_chain_packed_abi tests/c/test_rx_chain_abi \
               tests/c/test_rx_pool_abi tests/c/test_tx_pool_abi tests/c/test_tx_segment_abi \
-              tests/c/test_rx_place_abi tests/c/test_rx_flow_abi tests/c/test_tx_plan_abi
+              tests/c/test_rx_place_abi tests/c/test_rx_flow_abi tests/c/test_tx_plan_abi \
+              tests/c/test_icmp_echo_abi
 
 all: $(LIB) oracle $(CABI_TESTS)
 

@@ -446,6 +446,87 @@ int rns_rx_tcp_place_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
 int rns_rx_flow_table_build(const rns_rx_flow_key *keys, uint32_t n_flows,
                             uint8_t *tbl /* NULL: size only */, uint64_t tbl_bytes, uint64_t *need_bytes);
 
+/* ICMP echo responder over pool buffers: icmp_input_v4 / icmp_input_v6 (icmp.rs:44-85) with their
+ * icmp_output_* and ip_output_* on the device.  For a receive batch in the pool form above, every echo
+ * request becomes a finished echo reply in a transmit pool, described by the compact descriptors
+ * rns_tx_fill_pool_dev and rns_io_send_batch_pool take; its buffers are drawn from a free list on the
+ * device and its IPv4 id is numbered as NEXT_PACKET_ID would number it.  The host touches no datagram.
+ * Both pools have buffers of 2^buf_log2 bytes, B below.
+ * The form is defined by what it expands to:
+ *   Status: d_status[i] and d_l4_sum[i] are exactly what rns_rx_verify_pool_dev gives for the same
+ *     pool and descriptors.
+ *   Request: with T = d_len16[i] and h the IP header length as the verify parses it (IHL * 4, or 40),
+ *     datagram i is a request (RNS_ECHO_REQUEST) iff its status has RNS_RX_ACCEPT, T - h >= 4, and it
+ *     is IPv4 with protocol 1 and L4 byte 0 == 8, or IPv6 with next header 58 and L4 byte 0 == 128.
+ *     The code byte is not looked at.  Everything else has d_echo[i] == 0: bad checksums, echo
+ *     replies, other ICMP types, protocol 1 over IPv6 or 58 over IPv4, TCP, UDP, IPv4 fragments,
+ *     malformed datagrams.  (If the verify accepted the crossed-protocol cases, the reference would
+ *     answer them through icmp_input_v4 with an IPv6 address; and it panics in trim_head(4) for
+ *     T - h < 4.  Parity is unpinned for both.)
+ *   Allocation: request i needs nf_i = 1 + ceil(pay_i / B) buffers, pay_i = T - h - 4.  With R_i and
+ *     F_i the inclusive counts of requests and of their buffers up to i in batch order, it is answered
+ *     iff R_i <= reply_cap and F_i <= n_free; both counts are monotone, so the answered requests are a
+ *     prefix of the requests.  The others get RNS_ECHO_NOBUF and nothing is written for them: the host
+ *     answers those.  Reply r = R_i - 1 takes d_free[F_i - nf_i .. F_i), head buffer first, so the reply
+ *     descriptors' buf_idx IS d_free[0 .. d_count[1]) itself (d_free is read-only), d_tx_blk_first[r / 64]
+ *     is the number of buffers before reply 64 * (r / 64), d_tx_head_len8[r] is 24 or 44, d_tx_pay_len16[r]
+ *     = pay_i, d_tx_src[r] = i, and d_count = {replies, buffers, IPv4 replies}.  Entries of the
+ *     descriptor arrays at and past d_count[0] (for d_tx_blk_first: of blocks without a reply) are not
+ *     written.  (The buffers are counted as payload buffers + requests, the payload buffers in 32 bits:
+ *     always exact up to 2^24 datagrams; a batch whose requests hold 2^32 payload buffers or more is
+ *     outside the domain — still nothing outside the arrays and the pools is read or written.)
+ *   Bytes: the head is the LAST 24 / 44 bytes of the head buffer, as alloc_header(4) and then
+ *     alloc_header(20 / 40) leave it: IPv4 45 00, total length 24 + pay (mod 2^16: an accepted header
+ *     shorter than 20 bytes can pass it), id = (ip_id_base + *d_ip_id_add + the IPv4 replies before it)
+ *     mod 2^16, flags/offset 0, TTL 64, protocol 1, the header checksum, source = the LOCAL address (not
+ *     the request's destination), destination = the requester; IPv6 60 00 00 00, payload length 4 + pay,
+ *     next header 58, hop limit 64, local address, requester, and no id taken.  Then type 0 / 129, code 0
+ *     (alloc_header zeroes: the request's code is not echoed) and the checksum
+ *     compute_buffer_ones_comp(seed, packet) ^ 0xffff, seed 0 (IPv4) or the pseudo-header of (local,
+ *     requester, 4 + pay, 58).  IPv4 options of the request are dropped.  Payload byte k is byte
+ *     o = h + 4 + k of the request — offset o & (B - 1) of buffer d_buf_idx[first_i + (o >> buf_log2)] —
+ *     and goes to offset k & (B - 1) of the reply's buffer 1 + (k >> buf_log2): whole buffers from offset
+ *     0 and a last one with the remainder (append_from_buffer), none for pay == 0.  The stored bytes equal
+ *     those rns_tx_fill_pool_dev produces from the same heads with zeroed checksum fields.
+ *     Only a reply's own buffers are written: the head bytes, the payload bytes, and at most the bytes
+ *     from the payload's end up to the next 16-byte boundary of its last buffer (unspecified values: the
+ *     buffer is the reply's alone and a sender reads pay bytes).  Every other byte of the transmit pool,
+ *     the whole receive pool and every input array stay as they were.  A reply with any buffer index >=
+ *     tx_pool_bytes >> buf_log2 is counted and described, but gets d_tx_head_len8[r] = 0 (malformed to
+ *     rns_tx_fill_pool_dev and the sender) and RNS_ECHO_REQUEST | RNS_ECHO_BADBUF without
+ *     RNS_ECHO_BUILT, and nothing is written for it.  The two pools may be the same memory when no
+ *     d_free buffer is named by d_buf_idx.
+ * The launches after the verify: one that classifies, two one-workgroup scans, and one that copies each
+ * payload once — summing what it copies — and writes the heads, both checksums filled.
+ * n_pkts == 0 is RNS_OK with d_count zeroed.  buf_log2 outside 8..15, a NULL d_rx_pool / d_blk_first /
+ * d_len16 / d_status / d_echo / d_count / d_tx_pool / d_work / local address, a NULL d_buf_idx with
+ * n_frags > 0, a NULL d_free with n_free > 0, a pool that is not 16-byte aligned, a d_work that is not
+ * 8-byte aligned, work_bytes below rns_rx_icmp_echo_work's answer, or n_pkts > RNS_CHAIN_MAX_PACKETS is
+ * RNS_E_INVALID, all before the device is touched.  d_tx_blk_first / d_tx_head_len8 / d_tx_pay_len16 may
+ * be NULL iff reply_cap == 0; d_tx_src, d_l4_sum and d_ip_id_add are optional. */
+#define RNS_ECHO_REQUEST 0x01u  /* an echo request the stack would answer */
+#define RNS_ECHO_BUILT   0x02u  /* its reply was built and is described in the tx descriptors */
+#define RNS_ECHO_NOBUF   0x04u  /* a request past reply_cap or past the free list: the host answers it */
+#define RNS_ECHO_BADBUF  0x08u  /* a buffer it drew from d_free lies outside the tx pool: nothing written */
+int rns_rx_icmp_echo_pool_dev(const uint8_t *d_rx_pool, uint64_t rx_pool_bytes, uint32_t buf_log2,
+                              const uint32_t *d_buf_idx, uint32_t n_frags,
+                              const uint32_t *d_blk_first,   /* (n_pkts + 63) / 64 entries */
+                              const uint16_t *d_len16, uint32_t n_pkts,
+                              const uint8_t *local_ipv4, const uint8_t *local_ipv6,
+                              uint8_t *d_tx_pool, uint64_t tx_pool_bytes,   /* the same buf_log2 */
+                              const uint32_t *d_free, uint32_t n_free,      /* free tx buffers, taken in order */
+                              uint32_t reply_cap,
+                              uint16_t ip_id_base, const uint32_t *d_ip_id_add /* optional device dword, added to the base */,
+                              uint32_t *d_tx_blk_first /* (reply_cap + 63) / 64 */, uint8_t *d_tx_head_len8,
+                              uint16_t *d_tx_pay_len16, uint32_t *d_tx_src /* optional, reply_cap: the request's index */,
+                              uint32_t *d_count /* 3 dwords: replies, buffers taken, IPv4 ids taken */,
+                              uint8_t *d_status, uint16_t *d_l4_sum /* optional */, uint8_t *d_echo /* n_pkts */,
+                              void *d_work, uint64_t work_bytes, void *stream);
+
+/* The responder's workspace in bytes for n_pkts datagrams (CPU only): non-zero and monotone in n_pkts.
+ * RNS_E_INVALID for a NULL bytes or n_pkts > RNS_CHAIN_MAX_PACKETS. */
+int rns_rx_icmp_echo_work(uint32_t n_pkts, uint64_t *bytes);
+
 /* TCP flow update: the rest of tcp_input for an Established socket (tcp.rs:642-740) on the device,
  * over the placement's d_meta as it is — the advance of receive_next_seq and the reassembler's
  * next_sequence, the delayed-ACK count and its immediate ACKs, the ACK-field check that trims the

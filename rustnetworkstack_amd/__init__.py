@@ -17,16 +17,19 @@
 * ``send``      — TCP send planning: tcp_write's window gate and retransmit over the flow records on
                   the device, into the segmentation offload's descriptors; the same plan on the host
                   (also ``batch.*``);
+* ``icmp``      — ICMP echo responder: every accepted echo request of a receive batch becomes a finished
+                  reply in a transmit pool on the device, buffers drawn from a free list; the same on
+                  the host for what the device leaves (also ``batch.*``);
 * ``workloads`` — the synthetic packet batches BASELINE.json's configs name.
 """
 from . import _lib, util  # noqa: F401
 from ._lib import ChecksumError, ChecksumLibraryMissing  # noqa: F401
 
-__all__ = ["util", "batch", "pool", "segment", "place", "flow", "send", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
+__all__ = ["util", "batch", "pool", "segment", "place", "flow", "send", "icmp", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
 
 
 def __getattr__(name):
-    if name in ("batch", "pool", "segment", "place", "flow", "send", "workloads"):
+    if name in ("batch", "pool", "segment", "place", "flow", "send", "icmp", "workloads"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -40,6 +40,10 @@ RNS_PLACE_TCP = 0x01
 RNS_PLACE_FLOW = 0x02
 RNS_PLACE_DONE = 0x04
 RNS_PLACE_OUTSIDE = 0x08
+RNS_ECHO_REQUEST = 0x01  # rns_rx_icmp_echo_pool_dev's d_echo
+RNS_ECHO_BUILT = 0x02
+RNS_ECHO_NOBUF = 0x04
+RNS_ECHO_BADBUF = 0x08
 RNS_TCP_ESTABLISHED = 1  # rns_tcp_flow.state: the only one the flow update's fast path takes
 RNS_FLOW_MAX_SEGS = 1024  # a flow's datagrams per flow-update call
 RNS_SEG_CONSUMED = 0x01
@@ -78,6 +82,8 @@ EXPORTED_SYMBOLS = (
     "rns_rx_pool_layout",
     "rns_rx_tcp_place_pool_dev",
     "rns_rx_flow_table_build",
+    "rns_rx_icmp_echo_pool_dev",
+    "rns_rx_icmp_echo_work",
     "rns_rx_tcp_flow_update_dev",
     "rns_rx_tcp_flow_update_work",
     "rns_tx_ack_build_dev",
@@ -178,6 +184,9 @@ _SIGNATURES = {
     "rns_rx_tcp_place_pool_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _vp, _vp, _vp,
                                          _u32, _vp, _u64, _vp, _vp, _vp, _vp]),
     "rns_rx_flow_table_build": (_int, [_vp, _u32, _vp, _u64, ctypes.POINTER(_u64)]),
+    "rns_rx_icmp_echo_pool_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _vp, _u32, _u32,
+                                         _u16, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "rns_rx_icmp_echo_work": (_int, [_u32, ctypes.POINTER(_u64)]),
     "rns_rx_tcp_flow_update_dev": (_int, [_vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "rns_rx_tcp_flow_update_work": (_int, [_u32, _u32, ctypes.POINTER(_u64)]),
     "rns_tx_ack_build_dev": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u16, _vp, _u64, _vp, _u32, _vp, _vp, _vp,

@@ -814,6 +814,8 @@ _FLOW_API = ("FLOW_DTYPE", "RES_DTYPE", "SEG_DTYPE", "flow_update_host", "flow_u
 # and TCP send planning (send.py): batch.tx_tcp_plan, batch.tx_tcp_send, batch.plan_host, batch.tx_plan_work,
 # batch.PLAN_RES_DTYPE (send.RES_DTYPE: RES_DTYPE here is the flow update's).
 _SEND_API = ("PLAN_RES_DTYPE", "plan_host", "tx_plan_work", "tx_tcp_plan", "tx_tcp_send")
+# and the ICMP echo responder (icmp.py): batch.rx_icmp_echo_pool, batch.echo_host, batch.echo_respond, batch.echo_work.
+_ICMP_API = ("echo_host", "echo_respond", "echo_work", "rx_icmp_echo_pool")
 
 
 def __getattr__(name):
@@ -832,4 +834,7 @@ def __getattr__(name):
     if name in _SEND_API:
         from . import send
         return getattr(send, name)
+    if name in _ICMP_API:
+        from . import icmp
+        return getattr(icmp, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -468,6 +468,67 @@ int rns_rx_tcp_place_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
                            static_cast<hipStream_t>(stream));
 }
 
+int rns_rx_icmp_echo_pool_dev(const uint8_t *d_rx_pool, uint64_t rx_pool_bytes, uint32_t buf_log2,
+                              const uint32_t *d_buf_idx, uint32_t n_frags, const uint32_t *d_blk_first,
+                              const uint16_t *d_len16, uint32_t n_pkts, const uint8_t *local_ipv4,
+                              const uint8_t *local_ipv6, uint8_t *d_tx_pool, uint64_t tx_pool_bytes, const uint32_t *d_free,
+                              uint32_t n_free, uint32_t reply_cap, uint16_t ip_id_base, const uint32_t *d_ip_id_add,
+                              uint32_t *d_tx_blk_first, uint8_t *d_tx_head_len8, uint16_t *d_tx_pay_len16,
+                              uint32_t *d_tx_src, uint32_t *d_count, uint8_t *d_status, uint16_t *d_l4_sum, uint8_t *d_echo,
+                              void *d_work, uint64_t work_bytes, void *stream)
+{
+    const auto mis = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    if (n_pkts == 0) {  // no datagram: the counts alone
+        if (!d_count || mis(d_count, 3))
+            return RNS_E_INVALID;
+        if (int st = check_device())
+            return st;
+        return hip_status(hipMemsetAsync(d_count, 0, 12, static_cast<hipStream_t>(stream)));
+    }
+    // every rejection of the verify's and this entry's own, before the device is touched
+    if (buf_log2 < kEchoMinLog2 || buf_log2 > kPoolMaxLog2 || n_pkts > RNS_CHAIN_MAX_PACKETS || !d_rx_pool || !d_blk_first ||
+        !d_len16 || (n_frags && !d_buf_idx) || !rx_valid(d_status, local_ipv4, local_ipv6) || !d_tx_pool || !d_count ||
+        !d_echo || !d_work || (n_free && !d_free) ||
+        (reply_cap && (!d_tx_blk_first || !d_tx_head_len8 || !d_tx_pay_len16)) || mis(d_rx_pool, 15) || mis(d_tx_pool, 15) ||
+        mis(d_free, 3) || mis(d_ip_id_add, 3) || mis(d_tx_blk_first, 3) || mis(d_tx_pay_len16, 1) || mis(d_tx_src, 3) ||
+        mis(d_count, 3) || mis(d_work, 7) || work_bytes < echo_work_bytes(n_pkts))
+        return RNS_E_INVALID;
+    // the verify as it is: its kernel, its status and L4 sum
+    if (int st = rns_rx_verify_pool_dev(d_rx_pool, rx_pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
+                                        local_ipv4, local_ipv6, d_status, d_l4_sum, stream))
+        return st;
+    EchoArgs a{};
+    a.rx.pool = d_rx_pool;
+    a.rx.pool_bytes = rx_pool_bytes;
+    a.rx.buf_idx = d_buf_idx;
+    a.rx.blk_first = d_blk_first;
+    a.rx.len16 = d_len16;
+    a.rx.status = d_status;
+    a.rx.n = n_pkts;
+    a.rx.n_frags = n_frags;
+    a.rx.blog = buf_log2;
+    a.tx_pool = d_tx_pool;
+    a.tx_bufs = tx_pool_bytes >> buf_log2;
+    a.free = d_free;
+    a.ip_id_add = d_ip_id_add;
+    a.tx_blk_first = d_tx_blk_first;
+    a.tx_head_len8 = d_tx_head_len8;
+    a.tx_pay_len16 = d_tx_pay_len16;
+    a.tx_src = d_tx_src;
+    a.count = d_count;
+    a.echo = d_echo;
+    a.part_a = static_cast<uint2 *>(d_work);
+    a.part_b = a.part_a + scan_blocks(n_pkts) + 1;
+    a.rec = reinterpret_cast<uint32_t *>(a.part_b + scan_blocks(n_pkts) + 1);
+    std::memcpy(&a.local4, local_ipv4, 4);
+    std::memcpy(a.local6, local_ipv6, 16);
+    a.n_free = n_free;
+    a.reply_cap = reply_cap;
+    a.ip_id_base = ip_id_base;
+    return launch_rx_echo(a, chain_nt_from_arena(rx_pool_bytes, n_frags, static_cast<double>(n_frags) / n_pkts),
+                          static_cast<hipStream_t>(stream));
+}
+
 int rns_rx_tcp_flow_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,
                                const rns_tcp_flow *d_flow_in, const uint32_t *d_pend_in, uint32_t pend_cap,
                                rns_tcp_flow *d_flow_out, uint32_t *d_pend_out, rns_rx_tcp_seg *d_seg,

@@ -1,0 +1,316 @@
+// ICMP echo responder over pool buffers (rns_rx_icmp_echo_pool_dev): icmp_input's reply, built on the
+// device from a verified receive batch into the pool transmit form.
+// (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
+#pragma once
+
+#include "rns_k_plan.hpp"
+
+namespace rns {
+
+// ---------------------------------------------------------------------------
+// icmp_input_v4 / icmp_input_v6 (icmp.rs:44-85) verify the request, copy its payload into fresh
+// buffers (append_from_buffer), prepend a zeroed 4-byte ICMP header (alloc_header), checksum the
+// reply and hand it to ip_output, which writes its header in front in the same head buffer.  Here
+// the pool verify runs as it is, then three more steps on the same stream; grid-wide ordering comes
+// from the launch boundaries only:
+//   1. echo_classify_kernel  a lane per datagram, a wave per 64-datagram block (the unit of
+//                            d_blk_first), four blocks per workgroup: reads the status and the first
+//                            buffer's header dwords, decides the request, leaves one dword per
+//                            datagram in the workspace (request, IPv4, payload buffers, IHL) and the
+//                            workgroup's sums of (payload buffers, requests) and (IPv4 requests, 0).
+//   2. scan2_parts_kernel    (rns_k_flow.hpp, through k_flow.hip) over each of the two sum arrays.
+//                            The buffers before a request are payload buffers + requests, added in
+//                            64 bits.
+//   3. echo_build_kernel     the same decomposition: scans its workgroup again, applies reply_cap
+//                            and the free list's length (both counts are monotone: the answered
+//                            requests are a prefix), then each wave walks the destination 16-byte
+//                            chunks of all its replies concatenated — the placement's walk
+//                            (place_owner / place_load / place_second / place_join), with the
+//                            destination in the reply's payload buffers, which start 16-byte aligned:
+//                            every chunk is one whole aligned store, a payload's last chunk with
+//                            zeros after its bytes (the reply's own buffer).  The chunks' little-endian
+//                            word sums are reduced per datagram across the lanes (a range of the wave's
+//                            prefix sum: a datagram's chunks are consecutive lanes) into LDS; chunks start at even
+//                            payload offsets, so the sums add whatever the position.  The owner lane
+//                            then folds in the head and the IPv6 pseudo-header, and stores the head —
+//                            both checksums filled — and the descriptors.  The payload is read once and
+//                            written once after the verify.
+// The counts are stored by one lane of the grid — the first request that is not answered (its exclusive
+// counts) or, when all are, the last request — into the zeroed d_count: no atomics.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kEchoMinLog2 = 8;   // the transmit pool form's: a head fits its buffer
+constexpr uint32_t kEchoWaves = kScanBlock / 64;
+constexpr int kEchoPd = 7;
+// Per answered request in the wave's LDS table: [0] the wave's destination chunks before it, [1] [2] its
+// first fragment's place in d_buf_idx, [3] ip_hdr + 4, [4] pay_len, [5] its first payload buffer's place
+// in d_free, [6] the little-endian word sum of its payload.
+
+// the workspace's dword per datagram
+constexpr uint32_t kEchoRecReq = 1u, kEchoRecV4 = 2u;
+constexpr int kEchoRecBufShift = 2, kEchoRecIhlShift = 12;  // payload buffers (<= 256), ip_hdr / 4 (<= 15)
+
+struct EchoArgs {
+    PlaceArgs rx;  // the receive pool form (pool, pool_bytes, buf_idx, blk_first, len16, status, n, n_frags, blog)
+    uint8_t *tx_pool;
+    uint64_t tx_bufs;  // whole buffers of the transmit pool
+    const uint32_t *free;
+    const uint32_t *ip_id_add;
+    uint32_t *tx_blk_first;
+    uint8_t *tx_head_len8;
+    uint16_t *tx_pay_len16;
+    uint32_t *tx_src;
+    uint32_t *count;
+    uint8_t *echo;
+    uint32_t *rec;        // workspace: a dword per datagram
+    uint2 *part_a;        // workspace: the workgroups' (payload buffers, requests), blocks + 1
+    uint2 *part_b;        // workspace: the workgroups' (IPv4 requests, 0), blocks + 1
+    uint32_t local4;      // the local addresses as they lie in memory
+    uint32_t local6[4];
+    uint32_t n_free, reply_cap, ip_id_base;
+};
+
+// The workspace, 8-byte aligned: the two arrays of block sums, then the datagrams' dwords.
+inline uint64_t echo_work_bytes(uint64_t n_pkts) { return 16ull * (scan_blocks(n_pkts) + 1) + 4ull * n_pkts; }
+
+#ifdef RNS_ECHO_KERNELS
+
+// A datagram's place in the pool form, as the verify and the placement compute it (whole wave).
+struct EchoLane {
+    uint64_t p, gi;
+    uint32_t T, nf;
+    bool live;
+};
+
+__device__ __forceinline__ EchoLane echo_lane(const PlaceArgs &a, uint32_t blk, uint32_t lane)
+{
+    EchoLane e;
+    e.p = static_cast<uint64_t>(blk) * 64 + lane;
+    e.live = e.p < a.n;
+    const uint32_t bmask = (1u << a.blog) - 1u;
+    e.T = e.live ? a.len16[e.p] : 0u;
+    e.nf = (e.T + bmask) >> a.blog;
+    const uint32_t inc = wave_incl_scan(e.nf);
+    const uint32_t first = static_cast<uint64_t>(blk) * 64 < a.n ? a.blk_first[blk] : 0u;  // wave-uniform
+    e.gi = static_cast<uint64_t>(first) + (inc - e.nf);
+    return e;
+}
+
+// sum of the two big-endian 16-bit words of a dword as it lies in memory
+__device__ __forceinline__ uint32_t be_words(uint32_t d)
+{
+    return ((d & 0xffu) << 8) + ((d >> 8) & 0xffu) + ((d >> 8) & 0xff00u) + (d >> 24);
+}
+
+__device__ __forceinline__ uint32_t swap16(uint32_t v) { return ((v & 0xffu) << 8) | ((v >> 8) & 0xffu); }
+
+__global__ __launch_bounds__(kScanBlock) void echo_classify_kernel(const EchoArgs a)
+{
+    const uint32_t lane = threadIdx.x & 63;
+    const uint32_t blk = blockIdx.x * kEchoWaves + (threadIdx.x >> 6);
+    const EchoLane e = echo_lane(a.rx, blk, lane);
+    const uint32_t stv = e.live ? a.rx.status[e.p] : 0u;
+    // accepted: the verify has found every fragment inside d_buf_idx and the pool; checked again for the
+    // bytes read here and in the build, so that nothing depends on what d_status held before the call
+    bool ok = e.live && (stv & RNS_RX_ACCEPT) && e.nf != 0 && e.gi + e.nf <= a.rx.n_frags;
+    uint32_t rec = 0;
+    if (ok) {
+        const uint64_t s0 = static_cast<uint64_t>(a.rx.buf_idx[e.gi]) << a.rx.blog;
+        const uint32_t len0 = min(e.T, 1u << a.rx.blog);
+        ok = s0 <= a.rx.pool_bytes && len0 <= a.rx.pool_bytes - s0 && e.T >= 16u;
+        if (ok) {
+            const uint32_t *h = reinterpret_cast<const uint32_t *>(a.rx.pool + s0);
+            const uint32_t w0 = h[0];
+            const bool v6 = ((w0 >> 4) & 0xfu) == 6u;  // accepted: version 4 or 6
+            const uint32_t ip_hdr = v6 ? 40u : (w0 & 0xfu) * 4u;
+            // accepted: T >= 16 (IPv4) or 40 (IPv6), so the protocol is the datagram's; the ICMP header's
+            // dword lies in the first buffer (ip_hdr + 4 <= 64 <= B) and inside the datagram
+            const uint32_t proto = v6 ? (h[1] >> 16) & 0xffu : (h[2] >> 8) & 0xffu;
+            if (ip_hdr + 4u <= e.T && proto == (v6 ? 58u : 1u) && (h[ip_hdr >> 2] & 0xffu) == (v6 ? 128u : 8u)) {
+                const uint32_t pay = e.T - ip_hdr - 4u;
+                rec = kEchoRecReq | (v6 ? 0u : kEchoRecV4) | (((pay + (1u << a.rx.blog) - 1u) >> a.rx.blog) << kEchoRecBufShift) |
+                      ((ip_hdr >> 2) << kEchoRecIhlShift);
+            }
+        }
+    }
+    if (e.live)
+        a.rec[e.p] = rec;
+    const uint32_t req = rec & kEchoRecReq;
+    uint2 ta, tb;
+    (void)scan2_block(make_uint2((rec >> kEchoRecBufShift) & 0x3ffu, req), ta);
+    (void)scan2_block(make_uint2((rec & kEchoRecV4) ? 1u : 0u, 0u), tb);
+    if (threadIdx.x == 0) {
+        a.part_a[blockIdx.x] = ta;
+        a.part_b[blockIdx.x] = tb;
+    }
+}
+
+// Chunk v of the wave's concatenated destination chunks, its first load issued: place_fetch with the
+// destination in the reply's payload buffers (chunk c of a payload lies in buffer c >> (blog - 4)).
+template <bool NT>
+__device__ __forceinline__ PlaceChunk echo_fetch(const EchoArgs &a, const uint32_t (&pd)[kEchoPd][64], uint32_t v, uint32_t W,
+                                                 uint32_t &c)
+{
+    PlaceChunk ck{};
+    ck.j = ~0u;
+    c = 0;
+    if (v >= W)
+        return ck;
+    const uint32_t j = place_owner(pd, v);
+    c = v - pd[0][j];
+    const uint32_t skip = pd[3][j], plen = pd[4][j];
+    const uint64_t gi = (static_cast<uint64_t>(pd[2][j]) << 32) | pd[1][j];
+    const uint32_t o0 = skip + 16u * c;  // < skip + plen = T <= 65535
+    const uint32_t s = o0 & ~15u;
+    ck.sh = o0 & 15u;
+    ck.x = place_load<NT>(a.rx, gi, s);
+    ck.s2 = (ck.sh && s + 16u < skip + plen) ? s + 16u : 0u;
+    ck.gi = gi;
+    ck.j = j;
+    // the reply's buffers were found inside the transmit pool before its chunks were counted
+    const uint32_t bi = a.free[pd[5][j] + (c >> (a.rx.blog - 4u))];
+    ck.dc = a.tx_pool + (static_cast<uint64_t>(bi) << a.rx.blog) + ((16u * c) & ((1u << a.rx.blog) - 1u));
+    ck.lo = 0u;
+    ck.hi = min(16u, plen - 16u * c);  // >= 1: c is below the payload's chunk count
+    return ck;
+}
+
+// Stores the chunk whole (zeros after a payload's last byte) and adds its little-endian word sum to its
+// datagram's in LDS.  A datagram's chunks are consecutive lanes, so its sum over this step is a range of
+// the wave's prefix sum (DPP, no LDS round trip), as the rows kernels take a packet's: the datagram's last
+// lane of the step subtracts the prefix before its first lane — lane - min(c, lane), c the chunk's index in
+// its payload — and adds the range.  (Called by the whole wave.)
+__device__ __forceinline__ void echo_emit(const PlaceChunk &ck, const uint4 y, uint32_t c, uint32_t (&pd)[kEchoPd][64],
+                                          uint32_t lane)
+{
+    uint32_t sum = 0;
+    if (ck.hi != 0) {
+        uint32_t o[4];
+        place_join(ck, y, o);
+        if (ck.hi != 16u) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                o[k] = keep_bytes(o[k], 0, static_cast<int>(ck.hi), 4 * k);
+        }
+        *reinterpret_cast<uint4 *>(ck.dc) = make_uint4(o[0], o[1], o[2], o[3]);
+        sum = sad4(make_uint4(o[0], o[1], o[2], o[3]), 0u);  // <= 8 * 0xffff
+    }
+    const uint32_t S = wave_incl_scan(sum);  // <= 64 * 8 * 0xffff
+    const uint32_t a = lane - min(c, lane);
+    const uint32_t before = static_cast<uint32_t>(__shfl(static_cast<int>(S), static_cast<int>(max(a, 1u)) - 1, 64));
+    const uint32_t jn = static_cast<uint32_t>(__shfl_down(static_cast<int>(ck.j), 1, 64));
+    if (ck.hi != 0 && (lane == 63u || jn != ck.j))
+        pd[6][ck.j] += S - (a ? before : 0u);  // one lane per datagram; a payload's sum stays below 4096 * 8 * 0xffff < 2^32
+    wave_lds_fence();
+}
+
+template <bool NT>
+__global__ __launch_bounds__(kScanBlock) void echo_build_kernel(const EchoArgs a)
+{
+    __shared__ uint32_t pds[kEchoWaves][kEchoPd][64];
+    const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    uint32_t(&pd)[kEchoPd][64] = pds[wv];
+    const uint32_t blk = blockIdx.x * kEchoWaves + wv;
+    const EchoLane e = echo_lane(a.rx, blk, lane);
+    const uint32_t rec = e.live ? a.rec[e.p] : 0u;
+    const bool req = (rec & kEchoRecReq) != 0, v4 = (rec & kEchoRecV4) != 0;
+    const uint32_t pbufs = (rec >> kEchoRecBufShift) & 0x3ffu, ip_hdr = ((rec >> kEchoRecIhlShift) & 0xfu) * 4u;
+    uint2 ta, tb;
+    const uint2 xa = scan2_block(make_uint2(pbufs, req ? 1u : 0u), ta);
+    const uint2 xb = scan2_block(make_uint2(v4 ? 1u : 0u, 0u), tb);
+    const uint2 ca = a.part_a[blockIdx.x], cb = a.part_b[blockIdx.x];
+    // exclusive counts before this datagram: requests, their buffers (64 bits), IPv4 requests
+    const uint32_t r = ca.y + xa.y, v4_before = cb.x + xb.x;
+    const uint64_t f0 = static_cast<uint64_t>(ca.x + xa.x) + r;
+    const uint32_t nfr = 1u + pbufs;
+    const bool built = req && r < a.reply_cap && f0 + nfr <= a.n_free;
+    const uint32_t pay = req ? e.T - ip_hdr - 4u : 0u;
+    const uint32_t fi = static_cast<uint32_t>(f0);  // built: f0 < n_free
+    bool bad = false;
+    if (built) {
+        for (uint32_t k = 0; k < nfr; ++k)
+            bad = bad || a.free[fi + k] >= a.tx_bufs;
+    }
+    if (e.live)
+        a.echo[e.p] = static_cast<uint8_t>(!req ? 0u : !built ? RNS_ECHO_REQUEST | RNS_ECHO_NOBUF
+                                                   : bad    ? RNS_ECHO_REQUEST | RNS_ECHO_BADBUF
+                                                            : RNS_ECHO_REQUEST | RNS_ECHO_BUILT);
+    // the totals, stored by one lane of the grid: the first request that is not answered holds them as its
+    // exclusive counts (its predecessor was answered: r - 1 < reply_cap and f0 <= n_free), and when every
+    // request is answered the last one holds them as its inclusive counts.  (No request answered: the
+    // zeroed d_count stands.)
+    if (req && (built ? r + 1u == a.part_a[gridDim.x].y : r != 0 && r - 1u < a.reply_cap && f0 <= a.n_free)) {
+        a.count[0] = r + (built ? 1u : 0u);
+        a.count[1] = fi + (built ? nfr : 0u);
+        a.count[2] = v4_before + (built && v4 ? 1u : 0u);
+    }
+    const uint64_t bm = __ballot(built);
+    if (!bm)
+        return;  // (after the workgroup's last barrier)
+    // the wave's destination chunks, concatenated: at most 64 * 4096 of them
+    const bool copy = built && !bad;
+    const uint32_t nck = copy ? (pay + 15u) >> 4 : 0u;
+    const uint32_t cinc = wave_incl_scan(nck);
+    const uint32_t W = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cinc), 63));
+    pd[6][lane] = 0u;
+    if (W != 0) {
+        pd[0][lane] = cinc - nck;
+        pd[1][lane] = static_cast<uint32_t>(e.gi);
+        pd[2][lane] = static_cast<uint32_t>(e.gi >> 32);
+        pd[3][lane] = ip_hdr + 4u;
+        pd[4][lane] = pay;
+        pd[5][lane] = fi + 1u;
+        wave_lds_fence();
+        for (uint32_t vb = 0; vb < W; vb += 128u) {
+            uint32_t i0, i1;  // the chunks' indices in their payloads
+            const PlaceChunk c0 = echo_fetch<NT>(a, pd, vb + lane, W, i0);
+            const PlaceChunk c1 = echo_fetch<NT>(a, pd, vb + 64u + lane, W, i1);
+            const uint4 y0 = place_second<NT>(a.rx, c0, lane), y1 = place_second<NT>(a.rx, c1, lane);
+            echo_emit(c0, y0, i0, pd, lane);
+            echo_emit(c1, y1, i1, pd, lane);
+        }
+    }
+    wave_lds_fence();
+    if (!built)
+        return;
+    // the owner lane: the descriptors, then the head with both checksums
+    a.tx_head_len8[r] = static_cast<uint8_t>(bad ? 0u : v4 ? 24u : 44u);
+    a.tx_pay_len16[r] = static_cast<uint16_t>(pay);
+    if (a.tx_src)
+        a.tx_src[r] = static_cast<uint32_t>(e.p);
+    if ((r & 63u) == 0)
+        a.tx_blk_first[r >> 6] = fi;
+    if (bad)
+        return;
+    const uint32_t B = 1u << a.rx.blog;
+    const uint32_t *h = reinterpret_cast<const uint32_t *>(a.rx.pool + (static_cast<uint64_t>(a.rx.buf_idx[e.gi]) << a.rx.blog));
+    uint8_t *const hb = a.tx_pool + (static_cast<uint64_t>(a.free[fi]) << a.rx.blog) + B;
+    const uint32_t pay_be = swap16(fold16(pd[6][lane]));  // the payload's big-endian word sum, folded (RFC 1071 2(B))
+    if (v4) {
+        // ip_output_v4: 45 00 len | id 0000 | 40 01 csum | local | requester; then 00 00 csum (icmp_output)
+        const uint32_t total = (24u + pay) & 0xffffu;
+        const uint32_t id = (a.ip_id_base + (a.ip_id_add ? *a.ip_id_add : 0u) + v4_before) & 0xffffu;
+        const uint32_t peer = h[3];
+        const uint32_t ipck = fold16(0x4500u + total + id + 0x4001u + be_words(a.local4) + be_words(peer)) ^ 0xffffu;
+        const uint32_t ck = pay_be ^ 0xffffu;  // seed 0, a head of zeros
+        uint8_t *const at = hb - 24u;  // 8 mod 16
+        *reinterpret_cast<uint2 *>(at) = make_uint2(0x45u | (swap16(total) << 16), swap16(id));
+        *reinterpret_cast<uint4 *>(at + 8) = make_uint4(0x0140u | (swap16(ipck) << 16), a.local4, peer, swap16(ck) << 16);
+    } else {
+        // ip_output_v6: 60 00 00 00 | len 3a 40 | local | requester; then 81 00 csum
+        const uint32_t plen = 4u + pay;
+        const uint32_t p0 = h[2], p1 = h[3], p2 = h[4], p3 = h[5];
+        uint32_t s = plen + 58u + 0x8100u + pay_be;
+        s += be_words(a.local6[0]) + be_words(a.local6[1]) + be_words(a.local6[2]) + be_words(a.local6[3]);
+        s += be_words(p0) + be_words(p1) + be_words(p2) + be_words(p3);
+        const uint32_t ck = fold16(s) ^ 0xffffu;
+        uint8_t *const at = hb - 44u;  // 4 mod 16
+        *reinterpret_cast<uint32_t *>(at) = 0x60u;
+        *reinterpret_cast<uint2 *>(at + 4) = make_uint2(swap16(plen) | (58u << 16) | (64u << 24), a.local6[0]);
+        *reinterpret_cast<uint4 *>(at + 12) = make_uint4(a.local6[1], a.local6[2], a.local6[3], p0);
+        *reinterpret_cast<uint4 *>(at + 28) = make_uint4(p1, p2, p3, 0x81u | (swap16(ck) << 16));
+    }
+}
+
+#endif  // RNS_ECHO_KERNELS
+
+}  // namespace rns

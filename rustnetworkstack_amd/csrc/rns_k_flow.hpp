@@ -82,8 +82,9 @@ struct AckArgs {
 
 // The kernels are no templates, so one translation unit alone compiles them: k_flow.hip, which
 // launches them, defines RNS_FLOW_KERNELS.  (k_plan.hip, with RNS_PLAN_KERNELS, takes the scan's block
-// function and its reduce template from here and launches the parts kernel through k_flow.hip.)
-#if defined(RNS_FLOW_KERNELS) || defined(RNS_PLAN_KERNELS)
+// function and its reduce template from here and launches the parts kernel through k_flow.hip; so does
+// k_echo.hip, with RNS_ECHO_KERNELS.)
+#if defined(RNS_FLOW_KERNELS) || defined(RNS_PLAN_KERNELS) || defined(RNS_ECHO_KERNELS)
 
 // --- the scan: pairs of u32, 256 per workgroup ---
 __device__ __forceinline__ uint2 scan2_block(uint2 v, uint2 &total)
@@ -122,7 +123,7 @@ __global__ __launch_bounds__(kScanBlock) void scan2_reduce_kernel(const A a, uin
         part[blockIdx.x] = total;
 }
 
-#endif  // RNS_FLOW_KERNELS || RNS_PLAN_KERNELS
+#endif  // RNS_FLOW_KERNELS || RNS_PLAN_KERNELS || RNS_ECHO_KERNELS
 #ifdef RNS_FLOW_KERNELS
 
 // part[0..nb) to its exclusive prefix sums, part[nb] = the total (and *total2, when given): one workgroup

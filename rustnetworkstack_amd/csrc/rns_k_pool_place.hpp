@@ -130,6 +130,19 @@ struct PlaceChunk {
     uint32_t j;         // its datagram's lane, ~0: no chunk
 };
 
+// The datagram that owns chunk v of the wave's concatenated destination chunks (row 0 of the wave's
+// LDS table: the chunks before each datagram): the last one whose chunks start at or before v.
+// (Shared with the echo build, rns_k_echo.hpp.)
+template <int ROWS>
+__device__ __forceinline__ uint32_t place_owner(const uint32_t (&pd)[ROWS][64], uint32_t v)
+{
+    uint32_t j = 0;
+#pragma unroll
+    for (uint32_t step = 32; step; step >>= 1)
+        j += pd[0][j + step] <= v ? step : 0u;
+    return j;
+}
+
 // Chunk v of the wave's concatenated destination chunks, its first load issued.
 template <bool NT>
 __device__ __forceinline__ PlaceChunk place_fetch(const PlaceArgs &a, const uint32_t (&pd)[kPlacePd][64], uint32_t v,
@@ -139,10 +152,7 @@ __device__ __forceinline__ PlaceChunk place_fetch(const PlaceArgs &a, const uint
     ck.j = ~0u;
     if (v >= W)
         return ck;
-    uint32_t j = 0;  // the last datagram whose chunks start at or before v: v is one of its own
-#pragma unroll
-    for (uint32_t step = 32; step; step >>= 1)
-        j += pd[0][j + step] <= v ? step : 0u;
+    const uint32_t j = place_owner(pd, v);
     const uint32_t c = v - pd[0][j], skip = pd[3][j], plen = pd[4][j];
     const uint64_t gi = (static_cast<uint64_t>(pd[2][j]) << 32) | pd[1][j];
     uint8_t *const d0 = a.stream + ((static_cast<uint64_t>(pd[6][j]) << 32) | pd[5][j]);
@@ -179,19 +189,26 @@ __device__ __forceinline__ uint4 place_second(const PlaceArgs &a, const PlaceChu
     return y;
 }
 
-__device__ __forceinline__ void place_emit(const PlaceChunk &ck, const uint4 y)
+// The destination chunk's 16 bytes: the two source chunks joined at the byte shift.
+__device__ __forceinline__ void place_join(const PlaceChunk &ck, const uint4 y, uint32_t (&o)[4])
 {
-    if (ck.hi == 0)
-        return;
     const uint32_t q = ck.sh >> 2, bs = ck.sh & 3u;
     const uint32_t w[8] = {ck.x.x, ck.x.y, ck.x.z, ck.x.w, y.x, y.y, y.z, y.w};
-    uint32_t d[5], o[4];
+    uint32_t d[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k)
         d[k] = q == 0 ? w[k] : q == 1 ? w[k + 1] : q == 2 ? w[k + 2] : w[k + 3];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
         o[k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], bs);
+}
+
+__device__ __forceinline__ void place_emit(const PlaceChunk &ck, const uint4 y)
+{
+    if (ck.hi == 0)
+        return;
+    uint32_t o[4];
+    place_join(ck, y, o);
     if (ck.lo == 0 && ck.hi == 16u) {
         *reinterpret_cast<uint4 *>(ck.dc) = make_uint4(o[0], o[1], o[2], o[3]);
     } else {

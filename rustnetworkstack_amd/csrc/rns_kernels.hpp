@@ -42,3 +42,4 @@
 #include "rns_k_pool_place.hpp"
 #include "rns_k_flow.hpp"
 #include "rns_k_plan.hpp"
+#include "rns_k_echo.hpp"

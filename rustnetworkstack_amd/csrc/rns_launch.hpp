@@ -1,7 +1,7 @@
 // Host-side launchers of the checksum kernels (rns_kernels.hpp), one translation unit per
 // kernel family so the build compiles them in parallel: k_shapes.hip (the explicit-descriptor
 // shapes and the tuning entry), k_packed.hip (the packed form), k_chain.hip (fragment chains),
-// k_segment.hip (TCP segmentation offload), k_place.hip (TCP receive placement), k_flow.hip (TCP flow update and ACK build), k_plan.hip (TCP send planning), k_stash.hip (transmit fill / receive verify / transmit finalize).  rns_checksum.hip holds the
+// k_segment.hip (TCP segmentation offload), k_place.hip (TCP receive placement), k_flow.hip (TCP flow update and ACK build), k_plan.hip (TCP send planning), k_echo.hip (the ICMP echo responder), k_stash.hip (transmit fill / receive verify / transmit finalize).  rns_checksum.hip holds the
 // device entry points of the C ABI, rns_pipeline.hip the host-resident pipeline and the
 // multi-GPU contexts.
 #pragma once
@@ -140,6 +140,8 @@ int launch_ack_build(const AckArgs &a, hipStream_t st);
 int launch_scan2_parts(uint2 *part, uint32_t nb, uint32_t *total2, hipStream_t st);  // the scan's one-workgroup middle launch
 // k_plan.hip: TCP send planning (plan, scan, cap, finish), a sequence of launches
 int launch_tx_plan(const PlanArgs &a, hipStream_t st);
+// k_echo.hip: the ICMP echo responder (classify, two scans, build), after launch_rx_pool on the same stream
+int launch_rx_echo(const EchoArgs &a, bool nt, hipStream_t st);
 // k_stash.hip: the class kernel's stash modes on one-wave workgroups
 int launch_fill(const CsumArgs &a, dim3 grid, hipStream_t st);
 int launch_rx(const CsumArgs &a, dim3 grid, hipStream_t st);

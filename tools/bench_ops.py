@@ -66,6 +66,12 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              host), (b) the plan and then the segmentation on the planned descriptors, (c) the plan
              alone; the head bytes of (a) and (b) are compared before timing.  Timed once per run,
              whatever --configs names
+* rx_echo  — rns_rx_icmp_echo_pool_dev: 2^20 IPv4 pings of 84 bytes, 2^20 of 1500 bytes, and 2^23
+             IMIX-sized datagrams (40 / 576 / 1500 at 7:4:1) of which every fourth is a ping and the rest
+             UDP, in 512-byte buffers.  Timed in alternating rounds: (a) the responder, (b) the pool verify
+             alone, (c) the pool verify and then rns_tx_fill_pool_dev over prebuilt replies of the same
+             shapes — the floor that copies nothing; the replies of (a) are compared with echo_host on a
+             sample before timing.  Timed once per run, whatever --configs names
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -157,6 +163,8 @@ def main():
     ap.add_argument("--place-shapes", default="bulk,imix", help="rx_place: bulk (1500-byte datagrams) and / or imix")
     ap.add_argument("--place-n", type=int, default=0, help="rx_place: datagrams per shape (0 = 2^20 bulk, 2^23 imix)")
     ap.add_argument("--place-flows", type=int, default=1024, help="rx_place: flows (a divisor of the datagram count)")
+    ap.add_argument("--echo-shapes", default="ping84,ping1500,imix", help="rx_echo: the shapes to time")
+    ap.add_argument("--echo-n", type=int, default=0, help="rx_echo: datagrams per shape (0 = 2^20 pings, 2^23 imix)")
     ap.add_argument("--tx-modes", default="plain,runs,txpacked", help="chain_fill: hint flags to time")
     args = ap.parse_args()
     ops = set(args.ops.split(","))
@@ -208,6 +216,9 @@ def main():
         if "tx_plan" in ops and cfg == args.configs.split(",")[0]:
             for nfl, k in ((1024, 44), (1 << 20, 1)):
                 r.update(bench_tx_plan(nfl, k, dev, args))
+        if "rx_echo" in ops and cfg == args.configs.split(",")[0]:
+            for shape in args.echo_shapes.split(","):
+                r.update(bench_rx_echo(shape, dev, args))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -904,6 +915,130 @@ def bench_tx_plan(nfl, k, dev, args, mss=1460):
     del arena, heads_a
     torch.cuda.empty_cache()
     return {f"tx_plan_{nfl}_flows_x{k}": row}
+
+
+def _be_words(rows):
+    """Per row: the folded sum of its big-endian 16-bit words (int64 tensor)."""
+    s = rows[:, 0::2].sum(dim=1, dtype=torch.int64) * 256 + rows[:, 1::2].sum(dim=1, dtype=torch.int64)
+    for _ in range(3):
+        s = (s & 0xFFFF) + (s >> 16)
+    return s
+
+
+def _echo_batch(shape, n, dev, B=512):
+    """n datagrams from 192.168.1.1 to L4 in a pool of B-byte buffers, built on the device: every one an
+    IPv4 ping (ping84, ping1500), or IMIX sizes with every fourth a ping and the others UDP.  Datagram i
+    lies in consecutive buffers from i * stride on, zeros after its end.  (pool, buf_idx, blk_first, len16
+    as device tensors; the lengths and the request mask as numpy.)"""
+    from rustnetworkstack_amd.batch import rx_pool_layout
+    i = np.arange(n)
+    if shape == "imix":
+        T = np.where(i % 12 < 7, 40, np.where(i % 12 < 11, 576, 1500)).astype(np.int64)
+        req = i % 4 == 0
+    else:
+        T = np.full(n, int(shape[4:]), dtype=np.int64)
+        req = np.ones(n, dtype=bool)
+    stride = int(-(-int(T.max()) // B))
+    W = stride * B
+    blk, first, nf = rx_pool_layout(T, B)
+    nfr = -(-T // B)
+    idx = (np.repeat(i * stride, nfr) + (np.arange(nf) - np.repeat(first[:-1].astype(np.int64), nfr))).astype(np.uint32)
+    pool = torch.zeros(n * W, dtype=torch.uint8, device=dev)
+    rows = pool.view(n, W)
+    Tt, reqt = torch.from_numpy(T).to(dev), torch.from_numpy(req).to(dev)
+    col = torch.arange(W, device=dev)
+    for lo in range(0, n, 1 << 18):  # the payloads: random bytes inside the datagram, zeros after it
+        hi = min(n, lo + (1 << 18))
+        rnd = torch.randint(0, 256, (hi - lo, W), dtype=torch.uint8, device=dev)
+        rows[lo:hi] = rnd * (col[None, :] < Tt[lo:hi, None]).to(torch.uint8)
+        del rnd
+    hdr = torch.zeros((n, 24), dtype=torch.uint8, device=dev)
+    hdr[:, 0], hdr[:, 8] = 0x45, 64
+    hdr[:, 2], hdr[:, 3] = (Tt >> 8).to(torch.uint8), (Tt & 255).to(torch.uint8)
+    hdr[:, 9] = torch.where(reqt, 1, 17).to(torch.uint8)
+    hdr[:, 12:16] = torch.tensor([192, 168, 1, 1], dtype=torch.uint8, device=dev)
+    hdr[:, 16:20] = torch.tensor(list(L4), dtype=torch.uint8, device=dev)
+    ck = 0xFFFF ^ _be_words(hdr[:, :20])
+    hdr[:, 10], hdr[:, 11] = (ck >> 8).to(torch.uint8), (ck & 255).to(torch.uint8)
+    hdr[:, 20] = 8  # echo request, code 0, checksum below (UDP: these are its port bytes)
+    rows[:, :24] = hdr
+    for lo in range(0, n, 1 << 18):
+        hi = min(n, lo + (1 << 18))
+        ck = 0xFFFF ^ _be_words(rows[lo:hi, 20:])
+        rows[lo:hi, 22], rows[lo:hi, 23] = (ck >> 8).to(torch.uint8), (ck & 255).to(torch.uint8)
+    dv = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).to(dev)  # noqa: E731
+    return pool, dv(idx, np.int32), dv(blk, np.int32), dv(T.astype(np.uint16), np.int16), T, req
+
+
+def bench_rx_echo(shape, dev, args, B=512):
+    """rns_rx_icmp_echo_pool_dev against the pool verify alone and against the verify followed by
+    rns_tx_fill_pool_dev over prebuilt replies of the same shapes (the floor that copies nothing), in
+    alternating rounds."""
+    from rustnetworkstack_amd.batch import echo_host, echo_work, rx_icmp_echo_pool, rx_verify_pool, tx_fill_pool
+    n = args.echo_n or (1 << 23 if shape == "imix" else 1 << 20)
+    pool, idx, blk, len16, T, req = _echo_batch(shape, n, dev, B)
+    nreq, pay = int(req.sum()), T[req] - 24
+    nbuf = int((1 + -(-pay // B)).sum())
+    rng = np.random.default_rng(15)
+    free_h = rng.permutation(nbuf).astype(np.uint32)
+    free = torch.from_numpy(free_h.view(np.int32)).to(dev)
+    tx = torch.zeros(nbuf * B, dtype=torch.uint8, device=dev)
+    keep = dict(status=torch.empty(n, dtype=torch.uint8, device=dev), echo=torch.empty(n, dtype=torch.uint8, device=dev),
+                tx_blk_first=torch.empty((nreq + 63) // 64, dtype=torch.int32, device=dev),
+                tx_head_len8=torch.empty(nreq, dtype=torch.uint8, device=dev),
+                tx_pay_len16=torch.empty(nreq, dtype=torch.uint16, device=dev), tx_src=torch.empty(nreq, dtype=torch.int32, device=dev),
+                count=torch.empty(3, dtype=torch.int32, device=dev),
+                work=torch.empty((echo_work(n) + 7) // 8, dtype=torch.int64, device=dev))
+
+    def echo():
+        rx_icmp_echo_pool(pool, idx, blk, len16, L4, L6, tx, free, buf_bytes=B, reply_cap=nreq, ip_id_base=1, **keep)
+
+    echo()
+    torch.cuda.synchronize()
+    cnt = keep["count"].cpu().numpy().view(np.uint32)
+    assert cnt.tolist() == [nreq, nbuf, nreq], cnt
+    assert int((keep["echo"] == 3).sum().item()) == nreq
+    # a sample against the host path: the first 256 datagrams' replies, byte for byte
+    m = 256
+    W = pool.numel() // n
+    small = int(-(-T[:m] // B).sum())
+    k = int((1 + -(-(T[:m][req[:m]] - 24) // B)).sum())
+    txh = np.zeros(k * B, dtype=np.uint8)
+    e = echo_host(pool[:m * W].cpu().numpy(), idx[:small].cpu().numpy().view(np.uint32), blk[:m // 64].cpu().numpy().view(np.uint32),
+                  T[:m].astype(np.uint16), L4, L6, txh, np.arange(k, dtype=np.uint32), buf_bytes=B, ip_id_base=1)
+    got = tx.view(-1, B)[torch.from_numpy(free_h[:k].astype(np.int64)).to(dev)].cpu().numpy()
+    want, nb = txh.reshape(-1, B), 0
+    for hl, pl in zip(e[4].tolist(), e[5].tolist()):  # the head's bytes and the payload's, not the slack after them
+        npay = -(-pl // B)
+        assert np.array_equal(got[nb, B - hl:], want[nb, B - hl:])
+        assert np.array_equal(got[nb + 1:nb + 1 + npay].reshape(-1)[:pl], want[nb + 1:nb + 1 + npay].reshape(-1)[:pl])
+        nb += 1 + npay
+    assert nb == k
+    st2 = torch.empty(n, dtype=torch.uint8, device=dev)
+    tst = torch.empty(nreq, dtype=torch.uint8, device=dev)
+
+    def verify():
+        rx_verify_pool(pool, idx, blk, len16, L4, L6, buf_bytes=B, status=st2)
+
+    def verify_fill():
+        verify()
+        tx_fill_pool(tx, free, keep["tx_blk_first"], keep["tx_head_len8"], keep["tx_pay_len16"], buf_bytes=B, status=tst)
+
+    verify_fill()
+    torch.cuda.synchronize()
+    assert int((tst == 3).sum().item()) == nreq and torch.equal(st2, keep["status"])
+    rs = timed_rounds([echo, verify, verify_fill], args.steps, args.rounds)
+    med = [r[len(r) // 2] for r in rs]
+    rx_bytes, pay_bytes = int(T.sum()), int(pay.sum())
+    row = {"datagrams": n, "requests": nreq, "reply_buffers": nbuf, "rx_bytes": rx_bytes, "payload_bytes": pay_bytes,
+           "echo_us": round(med[0] * 1e3, 1), "verify_us": round(med[1] * 1e3, 1), "verify_fill_us": round(med[2] * 1e3, 1),
+           "echo_over_verify": round(med[0] / med[1], 3), "echo_over_verify_fill": round(med[0] / med[2], 3),
+           "added_us_per_copied_GB": round((med[0] - med[1]) * 1e3 / max(pay_bytes / 1e9, 1e-9), 1),
+           "echo_GBps_rx_plus_copied": round((rx_bytes + 2 * pay_bytes) / med[0] / 1e6, 1),
+           "rounds_us": {k: [round(x * 1e3, 1) for x in r] for k, r in zip(("echo", "verify", "verify_fill"), rs)}}
+    del pool, tx
+    torch.cuda.empty_cache()
+    return {f"rx_echo_{shape}": row}
 
 
 def bench_chain_netbuf(lay, dev, args, shuffled=False, runs=False):
