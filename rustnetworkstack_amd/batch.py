@@ -158,6 +158,48 @@ def _call(name: str, dev: torch.device, *args) -> None:
     _lib.check(st, name)
 
 
+def _ptr(t: torch.Tensor | None):
+    """A tensor's address; None (a null pointer) for no tensor and for an empty one (place, flow, send, icmp)."""
+    return t.data_ptr() if t is not None and t.numel() else None
+
+
+def _nonnull(dev: torch.device):
+    """``ptr(t)`` for an entry point that wants a pointer even where nothing is read: an empty tensor's (its
+    data_ptr is null) is the address of 16 bytes that live as long as ``ptr``."""
+    keep = torch.empty(16, dtype=torch.uint8, device=dev)
+    return lambda t: t.data_ptr() or keep.data_ptr()
+
+
+def _bytes_of(t: torch.Tensor, name: str, n: int, item: int, dev) -> None:
+    _require_cuda(t, name, _U8)
+    if t.numel() != n * item or (dev is not None and t.device != dev):
+        raise ValueError(f"{name} must hold {n} records of {item} bytes on the meta's device")
+
+
+def _work_bytes(name: str, *args) -> int:
+    """A workspace size query of the C ABI (``rns_..._work``): its last argument is the u64 result."""
+    need = ctypes.c_uint64(0)
+    _lib.check(getattr(_lib.load(), name)(*args, ctypes.byref(need)), name)
+    return int(need.value)
+
+
+def _workspace(work: torch.Tensor | None, need: int, dev, dtype=torch.uint8, complaint: str | None = None) -> torch.Tensor:
+    """The caller's workspace (``dtype`` uint8 or int64) checked for ``need`` bytes, 8-byte aligned, or a new one."""
+    item = 8 if dtype == torch.int64 else 1
+    if work is None:
+        return torch.empty(-(-max(need, 8) // item), dtype=dtype, device=dev)
+    _require_cuda(work, "work", (dtype,))
+    if work.numel() * item < need or work.device != dev or work.data_ptr() & 7:
+        raise ValueError(complaint or f"work must hold {need} bytes, 8-byte aligned, on the meta's device")
+    return work
+
+
+def _seq_gt(a: int, b: int) -> bool:
+    """util.rs:155-158."""
+    d = (a - b) & 0xFFFFFFFF
+    return d < 0x80000000 and d != 0
+
+
 class _BoundBatch:
     """A batch bound to one C ABI entry point: the subclass's constructor validates and
     marshals (``_bind``), so each launch is a single ctypes call with pre-marshalled

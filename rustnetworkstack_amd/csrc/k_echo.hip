@@ -1,31 +1,17 @@
 // ICMP echo responder (rns_rx_icmp_echo_pool_dev): the launch sequence after the pool verify — every
 // grid-wide dependency is a launch boundary on the one stream — and the workspace's host-side sizing.
-#define RNS_ECHO_KERNELS
 #include "rns_launch.hpp"
+#include "rns_k_echo.hpp"
 
 namespace rns {
-
-namespace {
-
-#define RNS_LAUNCH(kernel, grid, block, st, ...)                                      \
-    do {                                                                              \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);      \
-        if (int e = hip_status(hipGetLastError()))                                    \
-            return e;                                                                 \
-    } while (0)
-
-}  // namespace
 
 int launch_rx_echo(const EchoArgs &a, bool nt, hipStream_t st)
 {
     const uint32_t nb = static_cast<uint32_t>(scan_blocks(a.rx.n));
-    if (int e = hip_status(hipMemsetAsync(a.count, 0, 12, st)))
-        return e;
+    RNS_TRY(hip_status(hipMemsetAsync(a.count, 0, 12, st)));
     RNS_LAUNCH(echo_classify_kernel, nb, kScanBlock, st, a);
-    if (int e = launch_scan2_parts(a.part_a, nb, nullptr, st))
-        return e;
-    if (int e = launch_scan2_parts(a.part_b, nb, nullptr, st))
-        return e;
+    RNS_TRY(launch_scan2_parts(a.part_a, nb, nullptr, st));
+    RNS_TRY(launch_scan2_parts(a.part_b, nb, nullptr, st));
     return with_flags(
         [&](auto NT) {
             RNS_LAUNCH(echo_build_kernel<NT()>, nb, kScanBlock, st, a);

@@ -1,31 +1,12 @@
 // TCP flow update and ACK build (rns_rx_tcp_flow_update_dev, rns_tx_ack_build_dev): the launch
 // sequences — every grid-wide dependency is a launch boundary on the one stream — and the
 // workspace's host-side sizing.
-#define RNS_FLOW_KERNELS
-#include <algorithm>
-
 #include "rns_launch.hpp"
+#include "rns_k_flow.hpp"
 
 namespace rns {
 
-namespace {
-
-#define RNS_LAUNCH(kernel, grid, block, st, ...)                                      \
-    do {                                                                              \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);      \
-        if (int e = hip_status(hipGetLastError()))                                    \
-            return e;                                                                 \
-    } while (0)
-
-uint32_t blocks_of(uint64_t n) { return static_cast<uint32_t>(scan_blocks(n)); }
-
-}  // namespace
-
-int launch_scan2_parts(uint2 *part, uint32_t nb, uint32_t *total2, hipStream_t st)
-{
-    RNS_LAUNCH(scan2_parts_kernel, 1, kScanBlock, st, part, nb, total2);
-    return RNS_OK;
-}
+static uint32_t blocks_of(uint64_t n) { return static_cast<uint32_t>(scan_blocks(n)); }
 
 int launch_flow_update(const FlowArgs &a, hipStream_t st)
 {
@@ -33,14 +14,13 @@ int launch_flow_update(const FlowArgs &a, hipStream_t st)
         RNS_LAUNCH(flow_count_kernel, blocks_of(a.n_pkts), kScanBlock, st, a);
         return RNS_OK;
     }
-    if (int e = hip_status(hipMemsetAsync(a.cnt, 0, 4ull * a.n_flows, st)))
-        return e;
+    RNS_TRY(hip_status(hipMemsetAsync(a.cnt, 0, 4ull * a.n_flows, st)));
     if (a.n_pkts) {
         const uint32_t nb = blocks_of(a.n_flows);
         RNS_LAUNCH(flow_count_kernel, blocks_of(a.n_pkts), kScanBlock, st, a);
         RNS_LAUNCH((scan2_reduce_kernel<FlowCountValue, FlowArgs>), nb, kScanBlock, st, a, static_cast<uint64_t>(a.n_flows),
                    a.part);
-        RNS_LAUNCH(scan2_parts_kernel, 1, kScanBlock, st, a.part, nb, static_cast<uint32_t *>(nullptr));
+        RNS_TRY(launch_scan2_parts(a.part, nb, nullptr, st));
         RNS_LAUNCH(flow_cursor_kernel, nb, kScanBlock, st, a);
         RNS_LAUNCH(flow_scatter_kernel, blocks_of(a.n_pkts), kScanBlock, st, a);
     }
@@ -56,7 +36,7 @@ int launch_ack_build(const AckArgs &a, hipStream_t st)
         return hip_status(hipMemsetAsync(a.n_acks, 0, 8, st));
     const uint32_t nb = blocks_of(a.n_pkts);
     RNS_LAUNCH((scan2_reduce_kernel<AckValue, AckArgs>), nb, kScanBlock, st, a, static_cast<uint64_t>(a.n_pkts), a.part);
-    RNS_LAUNCH(scan2_parts_kernel, 1, kScanBlock, st, a.part, nb, a.n_acks);
+    RNS_TRY(launch_scan2_parts(a.part, nb, a.n_acks, st));
     if (a.ack_cap)
         RNS_LAUNCH(ack_build_kernel, nb, kScanBlock, st, a);
     return RNS_OK;

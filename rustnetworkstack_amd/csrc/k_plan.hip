@@ -1,30 +1,15 @@
 // TCP send planning (rns_tx_tcp_plan_dev): the launch sequence — every grid-wide dependency is a
 // launch boundary on the one stream — and the workspace's host-side sizing.
-#define RNS_PLAN_KERNELS
-#include <algorithm>
-
 #include "rns_launch.hpp"
+#include "rns_k_plan.hpp"
 
 namespace rns {
-
-namespace {
-
-#define RNS_LAUNCH(kernel, grid, block, st, ...)                                      \
-    do {                                                                              \
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);      \
-        if (int e = hip_status(hipGetLastError()))                                    \
-            return e;                                                                 \
-    } while (0)
-
-}  // namespace
 
 int launch_tx_plan(const PlanArgs &a, hipStream_t st)
 {
     if (a.n_flows == 0) {  // no entry: E = 0 names every block, and the totals are zero
-        if (int e = hip_status(hipMemsetAsync(a.seg_first, 0, 4, st)))
-            return e;
-        if (int e = hip_status(hipMemsetAsync(a.n_out, 0, 8, st)))
-            return e;
+        RNS_TRY(hip_status(hipMemsetAsync(a.seg_first, 0, 4, st)));
+        RNS_TRY(hip_status(hipMemsetAsync(a.n_out, 0, 8, st)));
         const uint64_t nblk = (static_cast<uint64_t>(a.seg_cap) + 63) / 64;
         return nblk ? hip_status(hipMemsetAsync(a.blk_flow, 0, 4 * nblk, st)) : RNS_OK;
     }
@@ -32,8 +17,7 @@ int launch_tx_plan(const PlanArgs &a, hipStream_t st)
     const uint32_t nf = static_cast<uint32_t>(scan_blocks(a.n_flows)), nb = static_cast<uint32_t>(scan_blocks(E));
     RNS_LAUNCH(plan_flow_kernel, nf, kScanBlock, st, a);
     RNS_LAUNCH((scan2_reduce_kernel<PlanValue, PlanArgs>), nb, kScanBlock, st, a, E, a.part);
-    if (int e = launch_scan2_parts(a.part, nb, nullptr, st))
-        return e;
+    RNS_TRY(launch_scan2_parts(a.part, nb, nullptr, st));
     RNS_LAUNCH(plan_cap_kernel, 1, kScanBlock, st, a);
     RNS_LAUNCH(plan_finish_kernel, nf, kScanBlock, st, a);
     return RNS_OK;

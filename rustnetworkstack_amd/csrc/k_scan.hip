@@ -1,0 +1,36 @@
+// The scan's one-workgroup middle launch (rns_k_scan.hpp): the one kernel of the scan that is no
+// template, and its launcher.
+#include "rns_launch.hpp"
+
+namespace rns {
+
+// part[0..nb) to its exclusive prefix sums, part[nb] = the total (and *total2, when given): one workgroup
+__global__ __launch_bounds__(kScanBlock) void scan2_parts_kernel(uint2 *part, uint32_t nb, uint32_t *total2)
+{
+    uint2 carry = make_uint2(0u, 0u);
+    for (uint32_t base = 0; base < nb; base += kScanBlock) {
+        const uint32_t i = base + threadIdx.x;
+        const uint2 v = i < nb ? part[i] : make_uint2(0u, 0u);
+        uint2 total;
+        const uint2 ex = scan2_block(v, total);
+        if (i < nb)
+            part[i] = make_uint2(carry.x + ex.x, carry.y + ex.y);
+        carry.x += total.x;
+        carry.y += total.y;
+    }
+    if (threadIdx.x == 0) {
+        part[nb] = carry;
+        if (total2) {
+            total2[0] = carry.x;
+            total2[1] = carry.y;
+        }
+    }
+}
+
+int launch_scan2_parts(uint2 *part, uint32_t nb, uint32_t *total2, hipStream_t st)
+{
+    RNS_LAUNCH(scan2_parts_kernel, 1, kScanBlock, st, part, nb, total2);
+    return RNS_OK;
+}
+
+}  // namespace rns

@@ -44,8 +44,7 @@ int entry(uint32_t n, bool valid, const uint8_t *d_arena, uint64_t arena_bytes, 
         return RNS_OK;
     if (!d_arena || !valid)
         return RNS_E_INVALID;
-    if (int st = check_device())
-        return st;
+    RNS_TRY(check_device());
     CsumArgs a{};
     set_arena(a, d_arena, arena_bytes);
     a.n = n;
@@ -219,6 +218,23 @@ dim3 stash_grid(uint64_t n, uint64_t arena_bytes, bool tiny_cap)
     if (cap && blocks > kRxGridCap)
         blocks = kRxGridCap;
     return dim3(static_cast<uint32_t>(blocks));
+}
+
+bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+// The pool-receive part of PlaceArgs: the placement's and the echo responder's view of a verified batch.
+void set_pool_rx(PlaceArgs &p, const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2, const uint32_t *d_buf_idx,
+                 uint32_t n_frags, const uint32_t *d_blk_first, const uint16_t *d_len16, uint32_t n_pkts, uint8_t *d_status)
+{
+    p.pool = d_pool;
+    p.pool_bytes = pool_bytes;
+    p.buf_idx = d_buf_idx;
+    p.blk_first = d_blk_first;
+    p.len16 = d_len16;
+    p.status = d_status;
+    p.n = n_pkts;
+    p.n_frags = n_frags;
+    p.blog = buf_log2;
 }
 
 }  // namespace
@@ -437,21 +453,14 @@ int rns_rx_tcp_place_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
     if (n_pkts == 0)
         return RNS_OK;
     const uint64_t slots = flow_slots(n_flows);
-    if (buf_log2 < kPlaceMinLog2 || !d_meta || (reinterpret_cast<uintptr_t>(d_meta) & 3) || !d_next_seq || !d_win_off ||
-        !d_win_len || !d_stream ||
-        (n_flows && (!d_tbl || (reinterpret_cast<uintptr_t>(d_tbl) & 3) || tbl_bytes < slots * kFlowSlotBytes)))
+    if (buf_log2 < kPlaceMinLog2 || !d_meta || misaligned(d_meta, 3) || !d_next_seq || !d_win_off || !d_win_len ||
+        !d_stream || (n_flows && (!d_tbl || misaligned(d_tbl, 3) || tbl_bytes < slots * kFlowSlotBytes)))
         return RNS_E_INVALID;
     // the verify as it is: its rejections, its kernel, its status and L4 sum
-    if (int st = rns_rx_verify_pool_dev(d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
-                                        local_ipv4, local_ipv6, d_status, d_l4_sum, stream))
-        return st;
+    RNS_TRY(rns_rx_verify_pool_dev(d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
+                                   local_ipv4, local_ipv6, d_status, d_l4_sum, stream));
     PlaceArgs p{};
-    p.pool = d_pool;
-    p.pool_bytes = pool_bytes;
-    p.buf_idx = d_buf_idx;
-    p.blk_first = d_blk_first;
-    p.len16 = d_len16;
-    p.status = d_status;
+    set_pool_rx(p, d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, d_status);
     p.tbl = reinterpret_cast<const uint32_t *>(d_tbl);
     p.next_seq = d_next_seq;
     p.win_off = d_win_off;
@@ -459,11 +468,8 @@ int rns_rx_tcp_place_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
     p.stream = d_stream;
     p.stream_bytes = stream_bytes;
     p.meta = reinterpret_cast<uint32_t *>(d_meta);
-    p.n = n_pkts;
-    p.n_frags = n_frags;
     p.n_flows = n_flows;
     p.slots = static_cast<uint32_t>(slots);
-    p.blog = buf_log2;
     return launch_rx_place(p, chain_nt_from_arena(pool_bytes, n_frags, static_cast<double>(n_frags) / n_pkts),
                            static_cast<hipStream_t>(stream));
 }
@@ -477,36 +483,26 @@ int rns_rx_icmp_echo_pool_dev(const uint8_t *d_rx_pool, uint64_t rx_pool_bytes, 
                               uint32_t *d_tx_src, uint32_t *d_count, uint8_t *d_status, uint16_t *d_l4_sum, uint8_t *d_echo,
                               void *d_work, uint64_t work_bytes, void *stream)
 {
-    const auto mis = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
     if (n_pkts == 0) {  // no datagram: the counts alone
-        if (!d_count || mis(d_count, 3))
+        if (!d_count || misaligned(d_count, 3))
             return RNS_E_INVALID;
-        if (int st = check_device())
-            return st;
+        RNS_TRY(check_device());
         return hip_status(hipMemsetAsync(d_count, 0, 12, static_cast<hipStream_t>(stream)));
     }
     // every rejection of the verify's and this entry's own, before the device is touched
     if (buf_log2 < kEchoMinLog2 || buf_log2 > kPoolMaxLog2 || n_pkts > RNS_CHAIN_MAX_PACKETS || !d_rx_pool || !d_blk_first ||
         !d_len16 || (n_frags && !d_buf_idx) || !rx_valid(d_status, local_ipv4, local_ipv6) || !d_tx_pool || !d_count ||
         !d_echo || !d_work || (n_free && !d_free) ||
-        (reply_cap && (!d_tx_blk_first || !d_tx_head_len8 || !d_tx_pay_len16)) || mis(d_rx_pool, 15) || mis(d_tx_pool, 15) ||
-        mis(d_free, 3) || mis(d_ip_id_add, 3) || mis(d_tx_blk_first, 3) || mis(d_tx_pay_len16, 1) || mis(d_tx_src, 3) ||
-        mis(d_count, 3) || mis(d_work, 7) || work_bytes < echo_work_bytes(n_pkts))
+        (reply_cap && (!d_tx_blk_first || !d_tx_head_len8 || !d_tx_pay_len16)) || misaligned(d_rx_pool, 15) ||
+        misaligned(d_tx_pool, 15) || misaligned(d_free, 3) || misaligned(d_ip_id_add, 3) || misaligned(d_tx_blk_first, 3) ||
+        misaligned(d_tx_pay_len16, 1) || misaligned(d_tx_src, 3) || misaligned(d_count, 3) || misaligned(d_work, 7) ||
+        work_bytes < echo_work_bytes(n_pkts))
         return RNS_E_INVALID;
     // the verify as it is: its kernel, its status and L4 sum
-    if (int st = rns_rx_verify_pool_dev(d_rx_pool, rx_pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
-                                        local_ipv4, local_ipv6, d_status, d_l4_sum, stream))
-        return st;
+    RNS_TRY(rns_rx_verify_pool_dev(d_rx_pool, rx_pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
+                                   local_ipv4, local_ipv6, d_status, d_l4_sum, stream));
     EchoArgs a{};
-    a.rx.pool = d_rx_pool;
-    a.rx.pool_bytes = rx_pool_bytes;
-    a.rx.buf_idx = d_buf_idx;
-    a.rx.blk_first = d_blk_first;
-    a.rx.len16 = d_len16;
-    a.rx.status = d_status;
-    a.rx.n = n_pkts;
-    a.rx.n_frags = n_frags;
-    a.rx.blog = buf_log2;
+    set_pool_rx(a.rx, d_rx_pool, rx_pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, d_status);
     a.tx_pool = d_tx_pool;
     a.tx_bufs = tx_pool_bytes >> buf_log2;
     a.free = d_free;
@@ -536,19 +532,17 @@ int rns_rx_tcp_flow_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, u
 {
     static_assert(sizeof(rns_tcp_flow) == 4 * kFlowDw && sizeof(rns_rx_tcp_seg) == 8 &&
                       sizeof(rns_tcp_flow_res) == 4 * kFlowResDw,
-                  "rns_k_flow.hpp");
+                  "rns_k_args.hpp");
     if (n_pkts == 0 && n_flows == 0)
         return RNS_OK;
-    const auto mis = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
     const bool pend = n_flows && pend_cap;
     if (n_pkts > RNS_CHAIN_MAX_PACKETS || n_flows > kFlowMaxFlows || (n_pkts && (!d_meta || !d_seg)) ||
         (n_flows && (!d_flow_in || !d_flow_out || !d_res)) || (pend && (!d_pend_in || !d_pend_out)) || !d_work ||
-        mis(d_meta, 3) || mis(d_seg, 3) || mis(d_flow_in, 3) || mis(d_flow_out, 3) || mis(d_res, 3) ||
-        (pend && (mis(d_pend_in, 3) || mis(d_pend_out, 3))) || mis(d_work, 7) ||
+        misaligned(d_meta, 3) || misaligned(d_seg, 3) || misaligned(d_flow_in, 3) || misaligned(d_flow_out, 3) ||
+        misaligned(d_res, 3) || (pend && (misaligned(d_pend_in, 3) || misaligned(d_pend_out, 3))) || misaligned(d_work, 7) ||
         work_bytes < flow_work_bytes(n_pkts, n_flows))
         return RNS_E_INVALID;
-    if (int st = check_device())
-        return st;
+    RNS_TRY(check_device());
     FlowArgs a{};
     a.meta = reinterpret_cast<const uint32_t *>(d_meta);
     a.flow_in = reinterpret_cast<const uint32_t *>(d_flow_in);
@@ -574,15 +568,14 @@ int rns_tx_ack_build_dev(const rns_rx_tcp_meta *d_meta, const rns_rx_tcp_seg *d_
                          uint8_t *d_out, uint32_t ack_cap, uint32_t *d_ack_src, uint8_t *d_ack_len8, uint32_t *d_n_acks,
                          void *stream)
 {
-    const auto mis = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
     if (!d_n_acks || n_pkts > RNS_CHAIN_MAX_PACKETS ||
         (n_pkts && (!d_meta || !d_seg || !d_work || work_bytes < ack_work_bytes(n_pkts))) ||
         (n_pkts && n_flows && (!d_flow || !d_tmpl || !d_head_len8 || !tmpl_stride)) ||
-        (ack_cap && (!d_out || !d_ack_src || !d_ack_len8)) || mis(d_meta, 3) || mis(d_seg, 3) || mis(d_flow, 3) ||
-        mis(d_out, 3) || mis(d_ack_src, 3) || mis(d_n_acks, 3) || mis(d_work, 7))
+        (ack_cap && (!d_out || !d_ack_src || !d_ack_len8)) || misaligned(d_meta, 3) || misaligned(d_seg, 3) ||
+        misaligned(d_flow, 3) || misaligned(d_out, 3) || misaligned(d_ack_src, 3) || misaligned(d_n_acks, 3) ||
+        misaligned(d_work, 7))
         return RNS_E_INVALID;
-    if (int st = check_device())
-        return st;
+    RNS_TRY(check_device());
     AckArgs a{};
     a.meta = reinterpret_cast<const uint32_t *>(d_meta);
     a.seg = reinterpret_cast<const uint32_t *>(d_seg);
@@ -610,19 +603,18 @@ int rns_tx_tcp_plan_dev(const rns_tcp_flow *d_flow_in, rns_tcp_flow *d_flow_out,
                         uint64_t *d_head_off, uint32_t *d_seg_first, uint32_t *d_blk_flow, uint32_t *d_n,
                         rns_tx_plan_res *d_res, void *d_work, uint64_t work_bytes, void *stream)
 {
-    static_assert(sizeof(rns_tx_plan_res) == 4 * kPlanResDw, "rns_k_plan.hpp");
-    const auto mis = [](const void *p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+    static_assert(sizeof(rns_tx_plan_res) == 4 * kPlanResDw, "rns_k_args.hpp");
     if (n_flows > kPlanMaxFlows || seg_cap > RNS_CHAIN_MAX_PACKETS || !tmpl_stride || !d_seg_first || !d_n ||
         (seg_cap && !d_blk_flow) ||
         (n_flows && (!d_flow_in || !d_flow_out || !d_sq_off || !d_sq_seq || !d_sq_len || !d_mss || !d_tmpl || !d_head_len8 ||
                      !d_tmpl_out || !d_head_len8_out || !d_pay_off || !d_pay_len || !d_mss_out || !d_head_off || !d_res ||
                      !d_work || work_bytes < plan_work_bytes(n_flows))) ||
-        mis(d_flow_in, 3) || mis(d_flow_out, 3) || mis(d_sq_off, 7) || mis(d_sq_seq, 3) || mis(d_sq_len, 3) || mis(d_mss, 1) ||
-        mis(d_ip_id_add, 3) || mis(d_pay_off, 7) || mis(d_pay_len, 3) || mis(d_mss_out, 1) || mis(d_head_off, 7) ||
-        mis(d_seg_first, 3) || mis(d_blk_flow, 3) || mis(d_n, 3) || mis(d_res, 3) || mis(d_work, 7))
+        misaligned(d_flow_in, 3) || misaligned(d_flow_out, 3) || misaligned(d_sq_off, 7) || misaligned(d_sq_seq, 3) ||
+        misaligned(d_sq_len, 3) || misaligned(d_mss, 1) || misaligned(d_ip_id_add, 3) || misaligned(d_pay_off, 7) ||
+        misaligned(d_pay_len, 3) || misaligned(d_mss_out, 1) || misaligned(d_head_off, 7) || misaligned(d_seg_first, 3) ||
+        misaligned(d_blk_flow, 3) || misaligned(d_n, 3) || misaligned(d_res, 3) || misaligned(d_work, 7))
         return RNS_E_INVALID;
-    if (int st = check_device())
-        return st;
+    RNS_TRY(check_device());
     PlanArgs a{};
     a.flow_in = reinterpret_cast<const uint32_t *>(d_flow_in);
     a.flow_out = reinterpret_cast<uint32_t *>(d_flow_out);
@@ -760,8 +752,7 @@ int rns_fill_splitmix64_dev(uint8_t *d_buf, uint64_t nbytes, uint64_t seed, void
         return RNS_OK;
     if (!d_buf || (reinterpret_cast<uintptr_t>(d_buf) & 7))
         return RNS_E_INVALID;
-    if (int st = check_device())
-        return st;
+    RNS_TRY(check_device());
     const uint64_t words = (nbytes + 7) / 8;
     const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>((words + kBlock - 1) / kBlock, 8192));
     hipLaunchKernelGGL(splitmix64_fill_kernel, dim3(blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream),

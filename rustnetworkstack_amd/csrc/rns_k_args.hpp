@@ -1,0 +1,113 @@
+// What every translation unit sees of the entry points that are sequences of launches: their kernel
+// arguments, constants and workspace sizes.  Their kernels are no templates, so each family's header is
+// included by the one translation unit that launches it (k_flow.hip, k_plan.hip, k_echo.hip).
+// (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
+#pragma once
+
+#include "rns_k_pool_place.hpp"
+#include "rns_k_scan.hpp"
+
+namespace rns {
+
+// --- the flow update and the ACK build (rns_k_flow.hpp) ---
+constexpr uint32_t kFlowDw = 10, kFlowResDw = 6, kFlowMaxFlows = 0x7fffffffu;  // (flow indices stay below 2^31)
+constexpr uint32_t kStopNone = 0, kStopMany = 1, kStopState = 2, kStopFlags = 3, kStopOptions = 4, kStopOutside = 5,
+                   kStopPend = 6;
+static_assert(kStopMany == RNS_STOP_MANY && kStopState == RNS_STOP_STATE && kStopFlags == RNS_STOP_FLAGS &&
+                  kStopOptions == RNS_STOP_OPTIONS && kStopOutside == RNS_STOP_OUTSIDE && kStopPend == RNS_STOP_PEND,
+              "rns_checksum.h's stop reasons");
+
+struct FlowArgs {
+    const uint32_t *meta;     // 6 dwords per datagram
+    const uint32_t *flow_in;  // 10 dwords per flow
+    const uint32_t *pend_in;  // pend_cap (seq, len) pairs per flow
+    uint32_t *flow_out, *pend_out;
+    uint32_t *seg;            // 2 dwords per datagram
+    uint32_t *res;            // 6 dwords per flow
+    uint32_t *cnt, *cursor;   // workspace: n_flows each
+    uint32_t *longs;          // workspace: n_flows, the flows with two datagrams or more
+    uint32_t *list;           // workspace: n_pkts
+    uint2 *part;              // workspace: the scan's block sums, blocks + 1
+    uint32_t n_pkts, n_flows, pend_cap;
+};
+
+// The workspace, 8-byte aligned: the scan's block sums as pairs first (the flows' blocks + 1 for the
+// update; the datagrams' blocks + 1 for the ACK build, which uses nothing else and may share the
+// update's workspace once the update is done), then cnt, cursor and longs (n_flows dwords each) and
+// list (n_pkts).
+inline uint64_t flow_work_bytes(uint64_t n_pkts, uint64_t n_flows)
+{
+    return 4ull * (3 * n_flows + n_pkts + 2 * (scan_blocks(n_flows) + 1) + 2 * (scan_blocks(n_pkts) + 1));
+}
+inline uint64_t ack_work_bytes(uint64_t n_pkts) { return 8ull * (scan_blocks(n_pkts) + 1); }
+
+struct AckArgs {
+    const uint32_t *meta, *seg, *flow;
+    const uint8_t *tmpl, *head_len8;
+    uint8_t *out;
+    uint32_t *ack_src;
+    uint8_t *ack_len8;
+    uint32_t *n_acks;
+    uint2 *part;
+    uint32_t n_pkts, n_flows, tmpl_stride, ip_id_base, ack_cap;
+};
+
+// --- the send planning (rns_k_plan.hpp) ---
+constexpr uint32_t kPlanNone = 0, kPlanWindow = 1, kPlanState = 2, kPlanBad = 3, kPlanTmpl = 4, kPlanCap = 5;
+static_assert(kPlanNone == RNS_PLAN_NONE && kPlanWindow == RNS_PLAN_WINDOW && kPlanState == RNS_PLAN_STATE &&
+                  kPlanBad == RNS_PLAN_BAD && kPlanTmpl == RNS_PLAN_TMPL && kPlanCap == RNS_PLAN_CAP,
+              "rns_checksum.h's plan reasons");
+constexpr uint32_t kPlanMax = 0x3fffffffu, kPlanMaxFlows = 1u << 30, kPlanResDw = 4;
+
+struct PlanArgs {
+    const uint32_t *flow_in;  // 10 dwords per flow
+    uint32_t *flow_out;
+    const uint64_t *sq_off;
+    const uint32_t *sq_seq, *sq_len;
+    const uint16_t *mss;
+    const uint8_t *rexmit, *tmpl, *head_len8;
+    const uint32_t *ip_id_add;
+    uint8_t *tmpl_out, *head_len8_out;
+    uint64_t *pay_off;
+    uint32_t *pay_len;
+    uint16_t *mss_out;
+    uint64_t *head_off;
+    uint32_t *seg_first, *blk_flow, *n_out;
+    uint32_t *res;   // 4 dwords per flow
+    uint2 *part;     // workspace: the scan's block sums, blocks + 2 (the total, then the kept total)
+    uint2 *rec;      // workspace: two pairs per flow, (rexmit bytes, new bytes), (new segments, why | IPv4 << 8)
+    uint64_t head_first_off;
+    uint32_t n_flows, tmpl_stride, ip_id_base, seg_cap;
+};
+
+// The workspace, 8-byte aligned: the block sums of the E = 2 n_flows entries and two more pairs, then
+// the flows' records.
+inline uint64_t plan_work_bytes(uint64_t n_flows) { return 8ull * (scan_blocks(2 * n_flows) + 2) + 16ull * n_flows; }
+
+// --- the echo responder (rns_k_echo.hpp) ---
+constexpr uint32_t kEchoMinLog2 = 8;  // the transmit pool form's: a head fits its buffer
+
+struct EchoArgs {
+    PlaceArgs rx;  // the receive pool form (pool, pool_bytes, buf_idx, blk_first, len16, status, n, n_frags, blog)
+    uint8_t *tx_pool;
+    uint64_t tx_bufs;  // whole buffers of the transmit pool
+    const uint32_t *free;
+    const uint32_t *ip_id_add;
+    uint32_t *tx_blk_first;
+    uint8_t *tx_head_len8;
+    uint16_t *tx_pay_len16;
+    uint32_t *tx_src;
+    uint32_t *count;
+    uint8_t *echo;
+    uint32_t *rec;        // workspace: a dword per datagram
+    uint2 *part_a;        // workspace: the workgroups' (payload buffers, requests), blocks + 1
+    uint2 *part_b;        // workspace: the workgroups' (IPv4 requests, 0), blocks + 1
+    uint32_t local4;      // the local addresses as they lie in memory
+    uint32_t local6[4];
+    uint32_t n_free, reply_cap, ip_id_base;
+};
+
+// The workspace, 8-byte aligned: the two arrays of block sums, then the datagrams' dwords.
+inline uint64_t echo_work_bytes(uint64_t n_pkts) { return 16ull * (scan_blocks(n_pkts) + 1) + 4ull * n_pkts; }
+
+}  // namespace rns

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "rns_checksum.h"
+#include "rns_k_tcp_head.hpp"
 
 namespace rns {
 

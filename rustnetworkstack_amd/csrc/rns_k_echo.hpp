@@ -1,9 +1,9 @@
 // ICMP echo responder over pool buffers (rns_rx_icmp_echo_pool_dev): icmp_input's reply, built on the
 // device from a verified receive batch into the pool transmit form.
-// (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
+// (The kernels of k_echo.hip alone: two of them are no templates.  Their arguments are in rns_k_args.hpp.)
 #pragma once
 
-#include "rns_k_plan.hpp"
+#include "rns_k_args.hpp"
 
 namespace rns {
 
@@ -18,7 +18,7 @@ namespace rns {
 //                            buffer's header dwords, decides the request, leaves one dword per
 //                            datagram in the workspace (request, IPv4, payload buffers, IHL) and the
 //                            workgroup's sums of (payload buffers, requests) and (IPv4 requests, 0).
-//   2. scan2_parts_kernel    (rns_k_flow.hpp, through k_flow.hip) over each of the two sum arrays.
+//   2. scan2_parts_kernel    (rns_k_scan.hpp, through k_scan.hip) over each of the two sum arrays.
 //                            The buffers before a request are payload buffers + requests, added in
 //                            64 bits.
 //   3. echo_build_kernel     the same decomposition: scans its workgroup again, applies reply_cap
@@ -38,7 +38,6 @@ namespace rns {
 // The counts are stored by one lane of the grid — the first request that is not answered (its exclusive
 // counts) or, when all are, the last request — into the zeroed d_count: no atomics.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kEchoMinLog2 = 8;   // the transmit pool form's: a head fits its buffer
 constexpr uint32_t kEchoWaves = kScanBlock / 64;
 constexpr int kEchoPd = 7;
 // Per answered request in the wave's LDS table: [0] the wave's destination chunks before it, [1] [2] its
@@ -48,31 +47,6 @@ constexpr int kEchoPd = 7;
 // the workspace's dword per datagram
 constexpr uint32_t kEchoRecReq = 1u, kEchoRecV4 = 2u;
 constexpr int kEchoRecBufShift = 2, kEchoRecIhlShift = 12;  // payload buffers (<= 256), ip_hdr / 4 (<= 15)
-
-struct EchoArgs {
-    PlaceArgs rx;  // the receive pool form (pool, pool_bytes, buf_idx, blk_first, len16, status, n, n_frags, blog)
-    uint8_t *tx_pool;
-    uint64_t tx_bufs;  // whole buffers of the transmit pool
-    const uint32_t *free;
-    const uint32_t *ip_id_add;
-    uint32_t *tx_blk_first;
-    uint8_t *tx_head_len8;
-    uint16_t *tx_pay_len16;
-    uint32_t *tx_src;
-    uint32_t *count;
-    uint8_t *echo;
-    uint32_t *rec;        // workspace: a dword per datagram
-    uint2 *part_a;        // workspace: the workgroups' (payload buffers, requests), blocks + 1
-    uint2 *part_b;        // workspace: the workgroups' (IPv4 requests, 0), blocks + 1
-    uint32_t local4;      // the local addresses as they lie in memory
-    uint32_t local6[4];
-    uint32_t n_free, reply_cap, ip_id_base;
-};
-
-// The workspace, 8-byte aligned: the two arrays of block sums, then the datagrams' dwords.
-inline uint64_t echo_work_bytes(uint64_t n_pkts) { return 16ull * (scan_blocks(n_pkts) + 1) + 4ull * n_pkts; }
-
-#ifdef RNS_ECHO_KERNELS
 
 // A datagram's place in the pool form, as the verify and the placement compute it (whole wave).
 struct EchoLane {
@@ -94,14 +68,6 @@ __device__ __forceinline__ EchoLane echo_lane(const PlaceArgs &a, uint32_t blk, 
     e.gi = static_cast<uint64_t>(first) + (inc - e.nf);
     return e;
 }
-
-// sum of the two big-endian 16-bit words of a dword as it lies in memory
-__device__ __forceinline__ uint32_t be_words(uint32_t d)
-{
-    return ((d & 0xffu) << 8) + ((d >> 8) & 0xffu) + ((d >> 8) & 0xff00u) + (d >> 24);
-}
-
-__device__ __forceinline__ uint32_t swap16(uint32_t v) { return ((v & 0xffu) << 8) | ((v >> 8) & 0xffu); }
 
 __global__ __launch_bounds__(kScanBlock) void echo_classify_kernel(const EchoArgs a)
 {
@@ -284,33 +250,32 @@ __global__ __launch_bounds__(kScanBlock) void echo_build_kernel(const EchoArgs a
     const uint32_t B = 1u << a.rx.blog;
     const uint32_t *h = reinterpret_cast<const uint32_t *>(a.rx.pool + (static_cast<uint64_t>(a.rx.buf_idx[e.gi]) << a.rx.blog));
     uint8_t *const hb = a.tx_pool + (static_cast<uint64_t>(a.free[fi]) << a.rx.blog) + B;
-    const uint32_t pay_be = swap16(fold16(pd[6][lane]));  // the payload's big-endian word sum, folded (RFC 1071 2(B))
+    const uint32_t pay_be = bswap16_u32(fold16(pd[6][lane]));  // the payload's big-endian word sum, folded (RFC 1071 2(B))
     if (v4) {
         // ip_output_v4: 45 00 len | id 0000 | 40 01 csum | local | requester; then 00 00 csum (icmp_output)
         const uint32_t total = (24u + pay) & 0xffffu;
         const uint32_t id = (a.ip_id_base + (a.ip_id_add ? *a.ip_id_add : 0u) + v4_before) & 0xffffu;
         const uint32_t peer = h[3];
-        const uint32_t ipck = fold16(0x4500u + total + id + 0x4001u + be_words(a.local4) + be_words(peer)) ^ 0xffffu;
+        const uint32_t ipck = fold16(0x4500u + total + id + 0x4001u + be2(a.local4) + be2(peer)) ^ 0xffffu;
         const uint32_t ck = pay_be ^ 0xffffu;  // seed 0, a head of zeros
         uint8_t *const at = hb - 24u;  // 8 mod 16
-        *reinterpret_cast<uint2 *>(at) = make_uint2(0x45u | (swap16(total) << 16), swap16(id));
-        *reinterpret_cast<uint4 *>(at + 8) = make_uint4(0x0140u | (swap16(ipck) << 16), a.local4, peer, swap16(ck) << 16);
+        *reinterpret_cast<uint2 *>(at) = make_uint2(0x45u | (bswap16_u32(total) << 16), bswap16_u32(id));
+        *reinterpret_cast<uint4 *>(at + 8) =
+            make_uint4(0x0140u | (bswap16_u32(ipck) << 16), a.local4, peer, bswap16_u32(ck) << 16);
     } else {
         // ip_output_v6: 60 00 00 00 | len 3a 40 | local | requester; then 81 00 csum
         const uint32_t plen = 4u + pay;
         const uint32_t p0 = h[2], p1 = h[3], p2 = h[4], p3 = h[5];
         uint32_t s = plen + 58u + 0x8100u + pay_be;
-        s += be_words(a.local6[0]) + be_words(a.local6[1]) + be_words(a.local6[2]) + be_words(a.local6[3]);
-        s += be_words(p0) + be_words(p1) + be_words(p2) + be_words(p3);
+        s += be2(a.local6[0]) + be2(a.local6[1]) + be2(a.local6[2]) + be2(a.local6[3]);
+        s += be2(p0) + be2(p1) + be2(p2) + be2(p3);
         const uint32_t ck = fold16(s) ^ 0xffffu;
         uint8_t *const at = hb - 44u;  // 4 mod 16
         *reinterpret_cast<uint32_t *>(at) = 0x60u;
-        *reinterpret_cast<uint2 *>(at + 4) = make_uint2(swap16(plen) | (58u << 16) | (64u << 24), a.local6[0]);
+        *reinterpret_cast<uint2 *>(at + 4) = make_uint2(bswap16_u32(plen) | (58u << 16) | (64u << 24), a.local6[0]);
         *reinterpret_cast<uint4 *>(at + 12) = make_uint4(a.local6[1], a.local6[2], a.local6[3], p0);
-        *reinterpret_cast<uint4 *>(at + 28) = make_uint4(p1, p2, p3, 0x81u | (swap16(ck) << 16));
+        *reinterpret_cast<uint4 *>(at + 28) = make_uint4(p1, p2, p3, 0x81u | (bswap16_u32(ck) << 16));
     }
 }
-
-#endif  // RNS_ECHO_KERNELS
 
 }  // namespace rns

@@ -1,9 +1,9 @@
 // TCP flow update (rns_rx_tcp_flow_update_dev) and ACK build (rns_tx_ack_build_dev): tcp_input's
 // Established path over the placement's meta records, and the pure ACKs it sends.
-// (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
+// (The kernels of k_flow.hip alone: they are no templates.  Their arguments are in rns_k_args.hpp.)
 #pragma once
 
-#include "rns_k_pool_place.hpp"
+#include "rns_k_args.hpp"
 
 namespace rns {
 
@@ -14,7 +14,7 @@ namespace rns {
 // on another workgroup.
 //   1. flow_count_kernel    a lane per datagram: cnt[flow] += 1 (an integer atomic) for the flow's
 //                           datagrams, a zero d_seg record for every other datagram.
-//   2. scan (three launches, scan2_*) the exclusive prefix sum of cnt into cursor.
+//   2. scan (three launches, rns_k_scan.hpp) the exclusive prefix sum of cnt into cursor.
 //   3. flow_scatter_kernel  a lane per datagram: list[cursor[flow]++] = its index.  The order within
 //                           a flow's list is whatever the atomics gave.
 //   4. flow_walk_lane_kernel  a lane per flow, for the flows with at most one datagram (no order to
@@ -33,122 +33,9 @@ namespace rns {
 // Both walks run flow_step, the one restatement of the reference's step, with the pending list in
 // the flow's d_pend_out range (global memory: it is touched only by out-of-order arrivals).
 //
-// The scan is shared with the ACK build, whose ACK k is the k-th datagram in batch order with
-// RNS_SEG_ACK: pairs (ACKs, IPv4 ACKs) are summed per 256-datagram block, the block sums scanned by
-// one workgroup, and the consumer kernel scans its block again and builds the heads.
+// The ACK build's ACK k is the k-th datagram in batch order with RNS_SEG_ACK: the same scan over the
+// pairs (ACKs, IPv4 ACKs), and the consumer kernel builds the heads (rns_k_tcp_head.hpp).
 // ---------------------------------------------------------------------------
-constexpr uint32_t kFlowDw = 10, kFlowResDw = 6, kScanBlock = 256, kFlowMaxFlows = 0x7fffffffu;  // (flow indices stay below 2^31)
-constexpr uint32_t kStopNone = 0, kStopMany = 1, kStopState = 2, kStopFlags = 3, kStopOptions = 4, kStopOutside = 5,
-                   kStopPend = 6;
-static_assert(kStopMany == RNS_STOP_MANY && kStopState == RNS_STOP_STATE && kStopFlags == RNS_STOP_FLAGS &&
-                  kStopOptions == RNS_STOP_OPTIONS && kStopOutside == RNS_STOP_OUTSIDE && kStopPend == RNS_STOP_PEND,
-              "rns_checksum.h's stop reasons");
-
-struct FlowArgs {
-    const uint32_t *meta;     // 6 dwords per datagram
-    const uint32_t *flow_in;  // 10 dwords per flow
-    const uint32_t *pend_in;  // pend_cap (seq, len) pairs per flow
-    uint32_t *flow_out, *pend_out;
-    uint32_t *seg;            // 2 dwords per datagram
-    uint32_t *res;            // 6 dwords per flow
-    uint32_t *cnt, *cursor;   // workspace: n_flows each
-    uint32_t *longs;          // workspace: n_flows, the flows with two datagrams or more
-    uint32_t *list;           // workspace: n_pkts
-    uint2 *part;              // workspace: the scan's block sums, blocks + 1
-    uint32_t n_pkts, n_flows, pend_cap;
-};
-
-// The workspace, 8-byte aligned: the scan's block sums as pairs first (the flows' blocks + 1 for the
-// update; the datagrams' blocks + 1 for the ACK build, which uses nothing else and may share the
-// update's workspace once the update is done), then cnt, cursor and longs (n_flows dwords each) and
-// list (n_pkts).
-__host__ __device__ inline uint64_t scan_blocks(uint64_t n) { return (n + kScanBlock - 1) / kScanBlock; }
-inline uint64_t flow_work_bytes(uint64_t n_pkts, uint64_t n_flows)
-{
-    return 4ull * (3 * n_flows + n_pkts + 2 * (scan_blocks(n_flows) + 1) + 2 * (scan_blocks(n_pkts) + 1));
-}
-inline uint64_t ack_work_bytes(uint64_t n_pkts) { return 8ull * (scan_blocks(n_pkts) + 1); }
-
-struct AckArgs {
-    const uint32_t *meta, *seg, *flow;
-    const uint8_t *tmpl, *head_len8;
-    uint8_t *out;
-    uint32_t *ack_src;
-    uint8_t *ack_len8;
-    uint32_t *n_acks;
-    uint2 *part;
-    uint32_t n_pkts, n_flows, tmpl_stride, ip_id_base, ack_cap;
-};
-
-// The kernels are no templates, so one translation unit alone compiles them: k_flow.hip, which
-// launches them, defines RNS_FLOW_KERNELS.  (k_plan.hip, with RNS_PLAN_KERNELS, takes the scan's block
-// function and its reduce template from here and launches the parts kernel through k_flow.hip; so does
-// k_echo.hip, with RNS_ECHO_KERNELS.)
-#if defined(RNS_FLOW_KERNELS) || defined(RNS_PLAN_KERNELS) || defined(RNS_ECHO_KERNELS)
-
-// --- the scan: pairs of u32, 256 per workgroup ---
-__device__ __forceinline__ uint2 scan2_block(uint2 v, uint2 &total)
-{
-    __shared__ uint2 ws[kScanBlock / 64];
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const uint2 inc = make_uint2(wave_incl_scan(v.x), wave_incl_scan(v.y));
-    __syncthreads();  // a call before this one has read ws
-    if (lane == 63)
-        ws[w] = inc;
-    __syncthreads();
-    uint2 before = make_uint2(0u, 0u);
-    total = make_uint2(0u, 0u);
-#pragma unroll
-    for (uint32_t k = 0; k < kScanBlock / 64; ++k) {
-        const uint2 s = ws[k];
-        if (k < w) {
-            before.x += s.x;
-            before.y += s.y;
-        }
-        total.x += s.x;
-        total.y += s.y;
-    }
-    return make_uint2(before.x + inc.x - v.x, before.y + inc.y - v.y);
-}
-
-// part[b] = the sum of block b's values
-template <class V, class A>
-__global__ __launch_bounds__(kScanBlock) void scan2_reduce_kernel(const A a, uint64_t n, uint2 *part)
-{
-    const uint64_t i = static_cast<uint64_t>(blockIdx.x) * kScanBlock + threadIdx.x;
-    const uint2 v = i < n ? V::value(a, i) : make_uint2(0u, 0u);
-    uint2 total;
-    (void)scan2_block(v, total);
-    if (threadIdx.x == 0)
-        part[blockIdx.x] = total;
-}
-
-#endif  // RNS_FLOW_KERNELS || RNS_PLAN_KERNELS || RNS_ECHO_KERNELS
-#ifdef RNS_FLOW_KERNELS
-
-// part[0..nb) to its exclusive prefix sums, part[nb] = the total (and *total2, when given): one workgroup
-__global__ __launch_bounds__(kScanBlock) void scan2_parts_kernel(uint2 *part, uint32_t nb, uint32_t *total2)
-{
-    uint2 carry = make_uint2(0u, 0u);
-    for (uint32_t base = 0; base < nb; base += kScanBlock) {
-        const uint32_t i = base + threadIdx.x;
-        const uint2 v = i < nb ? part[i] : make_uint2(0u, 0u);
-        uint2 total;
-        const uint2 ex = scan2_block(v, total);
-        if (i < nb)
-            part[i] = make_uint2(carry.x + ex.x, carry.y + ex.y);
-        carry.x += total.x;
-        carry.y += total.y;
-    }
-    if (threadIdx.x == 0) {
-        part[nb] = carry;
-        if (total2) {
-            total2[0] = carry.x;
-            total2[1] = carry.y;
-        }
-    }
-}
-
 // --- the flows' lists ---
 // A datagram is on flow f's list iff place & RNS_PLACE_FLOW and flow == f < n_flows.
 __device__ __forceinline__ uint32_t flow_of(const uint32_t *meta, uint64_t p, uint32_t n_flows)
@@ -510,31 +397,6 @@ struct AckValue {
     }
 };
 
-// Dword k of the ACK's head from the template's dword d, both checksum fields zero.
-__device__ __forceinline__ uint32_t ack_patch(uint32_t k, uint32_t d, bool v4, uint32_t ipd, uint32_t id, uint32_t seq,
-                                              uint32_t ack, uint32_t window)
-{
-    if (v4) {
-        if (k == 0)  // ip.rs:146: total length
-            d = (d & 0xffffu) | (bswap16_u32(40u) << 16);
-        if (k == 1)  // ip.rs:147: id
-            d = (d & 0xffff0000u) | bswap16_u32(id);
-        if (k == 2)
-            d &= 0xffffu;
-    } else if (k == 1) {  // ip.rs:170: payload length
-        d = (d & 0xffff0000u) | bswap16_u32(20u);
-    }
-    if (k == ipd + 1u)  // tcp.rs:947-951
-        d = __builtin_bswap32(seq);
-    if (k == ipd + 2u)
-        d = __builtin_bswap32(ack);
-    if (k == ipd + 3u)
-        d = 0x50u | (0x10u << 8) | (bswap16_u32(window) << 16);
-    if (k == ipd + 4u)
-        d &= 0xffff0000u;
-    return d;
-}
-
 __global__ __launch_bounds__(kScanBlock) void ack_build_kernel(const AckArgs a)
 {
     const uint64_t p = static_cast<uint64_t>(blockIdx.x) * kScanBlock + threadIdx.x;
@@ -549,13 +411,8 @@ __global__ __launch_bounds__(kScanBlock) void ack_build_kernel(const AckArgs a)
         return;
     const uint32_t f = a.meta[6 * p], hl = a.head_len8[f];
     const uint8_t *t = a.tmpl + static_cast<uint64_t>(f) * a.tmpl_stride;
-    const bool v4 = hl == 40u;
-    const uint32_t iphdr = v4 ? 20u : 40u, ipd = iphdr >> 2, nd = hl >> 2;
-    bool ok = (hl == 40u || hl == 60u) && hl <= a.tmpl_stride;
-    if (ok) {
-        const uint32_t b0 = t[0];
-        ok = (v4 ? b0 == 0x45u && t[9] == 6u : (b0 >> 4) == 6u && t[6] == 6u) && (t[iphdr + 12u] >> 4) == 5u;
-    }
+    const bool v4 = hl == 40u, ok = tcp_tmpl_ok(t, hl, a.tmpl_stride);
+    const uint32_t ipd = v4 ? 5u : 10u, nd = hl >> 2;
     a.ack_src[k] = static_cast<uint32_t>(p);
     a.ack_len8[k] = ok ? static_cast<uint8_t>(hl) : static_cast<uint8_t>(0);
     if (!ok)
@@ -563,30 +420,26 @@ __global__ __launch_bounds__(kScanBlock) void ack_build_kernel(const AckArgs a)
     const uint32_t id = (a.ip_id_base + base.y + ex.y) & 0xffffu;
     const uint32_t seq = a.flow[static_cast<uint64_t>(f) * kFlowDw + 3], ack = a.seg[2 * p];
     const uint32_t window = a.seg[2 * p + 1] & 0xffffu;
-    uint32_t ipsum = 0, tcpsum = 0, addr = 0;
-    for (uint32_t j = 0; j < nd; ++j) {
-        uint32_t d;
-        __builtin_memcpy(&d, t + 4u * j, 4);
-        const uint32_t b = be2(ack_patch(j, d, v4, ipd, id, seq, ack, window));
-        ipsum += j < ipd ? b : 0u;
-        tcpsum += j < ipd ? 0u : b;
-        addr += (j >= (v4 ? 3u : 2u) && j < ipd) ? b : 0u;
-    }
-    const uint32_t ipv = fold16(ipsum) ^ 0xffffu;                           // ip.rs:158-159
-    const uint32_t l4 = fold16(fold16(addr + 6u + 20u) + tcpsum) ^ 0xffffu;  // tcp.rs:957-973
+    // one pass: every dword but the two that hold a checksum is stored as it is summed
     uint32_t *o = reinterpret_cast<uint32_t *>(a.out + 64ull * k);
+    const uint32_t kip = v4 ? 2u : ~0u, kl4 = ipd + 4u;
+    uint32_t dip = 0, dl4 = 0;
+    TcpHeadSum hs;
     for (uint32_t j = 0; j < nd; ++j) {
         uint32_t d;
         __builtin_memcpy(&d, t + 4u * j, 4);
-        d = ack_patch(j, d, v4, ipd, id, seq, ack, window);
-        if (v4 && j == 2)
-            d |= bswap16_u32(ipv) << 16;
-        if (j == ipd + 4u)
-            d |= bswap16_u32(l4);
-        o[j] = d;
+        d = tcp_head_patch(j, d, v4, ipd, id, seq, ack, window, 0x10u, true);
+        hs.add(j, d, v4, ipd);
+        if (j == kip)
+            dip = d;
+        else if (j == kl4)
+            dl4 = d;
+        else
+            o[j] = d;
     }
+    if (v4)
+        o[2] = dip | (bswap16_u32(hs.ip_csum()) << 16);
+    o[kl4] = dl4 | bswap16_u32(hs.l4_head(20u) ^ 0xffffu);  // tcp.rs:957-973, no payload
 }
-
-#endif  // RNS_FLOW_KERNELS
 
 }  // namespace rns

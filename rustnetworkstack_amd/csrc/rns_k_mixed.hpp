@@ -391,13 +391,6 @@ enum : uint32_t {
     kMetaL4Checked = 16, kMetaUnchecked = 32, kMetaUnknown = 64,
 };
 
-__device__ __forceinline__ uint32_t fold16(uint32_t x)
-{
-    while (x > 0xffff)
-        x = (x & 0xffff) + (x >> 16);
-    return x;
-}
-
 struct RxParse {
     uint32_t meta;  // kMeta* bits
     uint32_t hdr;   // IP header bytes (IHL*4 or 40)

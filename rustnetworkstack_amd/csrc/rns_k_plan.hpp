@@ -1,9 +1,9 @@
 // TCP send planning (rns_tx_tcp_plan_dev): tcp_write's window gate and retransmit on the device,
 // over the flow records the update left, into the descriptors rns_tx_segment_dev takes.
-// (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
+// (The kernels of k_plan.hip alone: they are no templates.  Their arguments are in rns_k_args.hpp.)
 #pragma once
 
-#include "rns_k_flow.hpp"
+#include "rns_k_args.hpp"
 
 namespace rns {
 
@@ -19,7 +19,7 @@ namespace rns {
 // Grid-wide ordering comes from launch boundaries on the one stream only:
 //   1. plan_flow_kernel    a lane per flow: the stops and both entries' byte and segment counts into
 //                          a 16-byte record of the workspace.
-//   2. scan2_reduce_kernel / scan2_parts_kernel (rns_k_flow.hpp) over the E = 2 n_flows entries: the
+//   2. scan2_reduce_kernel / scan2_parts_kernel (rns_k_scan.hpp) over the E = 2 n_flows entries: the
 //                          pair (segments, IPv4 segments) per 256-entry block.  An entry with segments has
 //                          a head of 40 (IPv4) or 60 bytes, so the head bytes before an entry are
 //                          60 * segments - 20 * IPv4 segments: three prefixes from one pass.  The
@@ -34,39 +34,6 @@ namespace rns {
 //                          fills d_blk_flow — an entry that owns more than one 64-segment block is
 //                          spread over its wave.
 // ---------------------------------------------------------------------------
-constexpr uint32_t kPlanNone = 0, kPlanWindow = 1, kPlanState = 2, kPlanBad = 3, kPlanTmpl = 4, kPlanCap = 5;
-static_assert(kPlanNone == RNS_PLAN_NONE && kPlanWindow == RNS_PLAN_WINDOW && kPlanState == RNS_PLAN_STATE &&
-                  kPlanBad == RNS_PLAN_BAD && kPlanTmpl == RNS_PLAN_TMPL && kPlanCap == RNS_PLAN_CAP,
-              "rns_checksum.h's plan reasons");
-constexpr uint32_t kPlanMax = 0x3fffffffu, kPlanMaxFlows = 1u << 30, kPlanResDw = 4;
-
-struct PlanArgs {
-    const uint32_t *flow_in;  // 10 dwords per flow
-    uint32_t *flow_out;
-    const uint64_t *sq_off;
-    const uint32_t *sq_seq, *sq_len;
-    const uint16_t *mss;
-    const uint8_t *rexmit, *tmpl, *head_len8;
-    const uint32_t *ip_id_add;
-    uint8_t *tmpl_out, *head_len8_out;
-    uint64_t *pay_off;
-    uint32_t *pay_len;
-    uint16_t *mss_out;
-    uint64_t *head_off;
-    uint32_t *seg_first, *blk_flow, *n_out;
-    uint32_t *res;   // 4 dwords per flow
-    uint2 *part;     // workspace: the scan's block sums, blocks + 2 (the total, then the kept total)
-    uint2 *rec;      // workspace: two pairs per flow, (rexmit bytes, new bytes), (new segments, why | IPv4 << 8)
-    uint64_t head_first_off;
-    uint32_t n_flows, tmpl_stride, ip_id_base, seg_cap;
-};
-
-// The workspace, 8-byte aligned: the block sums of the E = 2 n_flows entries and two more pairs, then
-// the flows' records.
-inline uint64_t plan_work_bytes(uint64_t n_flows) { return 8ull * (scan_blocks(2 * n_flows) + 2) + 16ull * n_flows; }
-
-#ifdef RNS_PLAN_KERNELS
-
 // (segments, IPv4 segments) of entry e, the count clamped to seg_cap + 1
 struct PlanValue {
     __device__ static uint2 value(const PlanArgs &a, uint64_t e)
@@ -76,16 +43,6 @@ struct PlanValue {
         return make_uint2(n, (r1.y & 0x100u) ? n : 0u);
     }
 };
-
-// The template rule of rns_tx_ack_build_dev.
-__device__ __forceinline__ bool plan_tmpl_ok(const uint8_t *t, uint32_t hl, uint32_t tmpl_stride)
-{
-    if ((hl != 40u && hl != 60u) || hl > tmpl_stride)
-        return false;
-    const bool v4 = hl == 40u;
-    const uint32_t b0 = t[0], iphdr = v4 ? 20u : 40u;
-    return (v4 ? b0 == 0x45u && t[9] == 6u : (b0 >> 4) == 6u && t[6] == 6u) && (t[iphdr + 12u] >> 4) == 5u;
-}
 
 __global__ __launch_bounds__(kScanBlock) void plan_flow_kernel(const PlanArgs a)
 {
@@ -102,7 +59,7 @@ __global__ __launch_bounds__(kScanBlock) void plan_flow_kernel(const PlanArgs a)
     } else if (mss == 0u || sq_len > kPlanMax || wnd > kPlanMax || inflight > kPlanMax || av > sq_len ||
                av + inflight > sq_len) {
         why = kPlanBad;
-    } else if (!plan_tmpl_ok(a.tmpl + f * a.tmpl_stride, hl, a.tmpl_stride)) {
+    } else if (!tcp_tmpl_ok(a.tmpl + f * a.tmpl_stride, hl, a.tmpl_stride)) {
         why = kPlanTmpl;
     } else {
         v4 = hl == 40u ? 1u : 0u;
@@ -164,21 +121,6 @@ __global__ __launch_bounds__(kScanBlock) void plan_cap_kernel(const PlanArgs a)
     }
 }
 
-// Dword k of an entry's template row from the template's dword d (send_packet, tcp_output).
-__device__ __forceinline__ uint32_t plan_patch(uint32_t k, uint32_t d, bool v4, uint32_t ipd, uint32_t id, uint32_t seq,
-                                               uint32_t ack, uint32_t window)
-{
-    if (v4 && k == 1u)  // ip.rs:147: id
-        d = (d & 0xffff0000u) | bswap16_u32(id);
-    if (k == ipd + 1u)  // tcp.rs:947-951
-        d = __builtin_bswap32(seq);
-    if (k == ipd + 2u)
-        d = __builtin_bswap32(ack);
-    if (k == ipd + 3u)
-        d = 0x50u | (0x18u << 8) | (bswap16_u32(window) << 16);
-    return d;
-}
-
 // Bytes [0, hl) of an entry's row: 16-byte chunks at a 16-byte-aligned row, dwords at a 4-byte-aligned
 // one, bytes otherwise (hl is 40 or 60).
 __device__ __forceinline__ void plan_row(const uint8_t *t, uint8_t *o, uint32_t hl, uint32_t id, uint32_t seq, uint32_t ack,
@@ -196,7 +138,7 @@ __device__ __forceinline__ void plan_row(const uint8_t *t, uint8_t *o, uint32_t 
             uint32_t d = 0;
             if (k < nd) {
                 __builtin_memcpy(&d, t + 4u * k, 4);
-                d = plan_patch(k, d, v4, ipd, id, seq, ack, window);
+                d = tcp_head_patch(k, d, v4, ipd, id, seq, ack, window, 0x18u, false);
             }
             q[i] = d;
         }
@@ -208,14 +150,7 @@ __device__ __forceinline__ void plan_row(const uint8_t *t, uint8_t *o, uint32_t 
                 const uint32_t k = 4u * c + i;
                 if (k >= nd)
                     continue;
-                if ((mis & 3u) == 0u) {
-                    reinterpret_cast<uint32_t *>(o)[k] = q[i];
-                } else {
-                    o[4u * k] = static_cast<uint8_t>(q[i]);
-                    o[4u * k + 1u] = static_cast<uint8_t>(q[i] >> 8);
-                    o[4u * k + 2u] = static_cast<uint8_t>(q[i] >> 16);
-                    o[4u * k + 3u] = static_cast<uint8_t>(q[i] >> 24);
-                }
+                store_dword(o + 4u * k, q[i], (mis & 3u) == 0u);
             }
         }
     }
@@ -327,7 +262,5 @@ __global__ __launch_bounds__(kScanBlock) void plan_finish_kernel(const PlanArgs 
             plan_row(t, a.tmpl_out + static_cast<uint64_t>(e1) * a.tmpl_stride, hl, (id0 + v1) & 0xffffu, nxt, r[0], window);
     }
 }
-
-#endif  // RNS_PLAN_KERNELS
 
 }  // namespace rns

@@ -29,15 +29,6 @@ namespace rns {
 #endif
 constexpr uint32_t kNoField = 0xFFFFFFFFu;
 
-__device__ __forceinline__ uint32_t bswap16_u32(uint32_t x) { return ((x & 0xff) << 8) | (x >> 8); }
-
-// Two big-endian 16-bit words of a dword held little-endian (bytes b0 b1 b2 b3): b0b1 + b2b3.
-__device__ __forceinline__ uint32_t be2(uint32_t d)
-{
-    const uint32_t x = ((d & 0x00ff00ffu) << 8) | ((d >> 8) & 0x00ff00ffu);
-    return (x & 0xffffu) + (x >> 16);
-}
-
 // The first 40 bytes of a datagram (version, IHL, protocol and both addresses of either
 // family) as ten dwords in datagram byte order, from its chunks (s = start & 15; chunk 0 is
 // the 16-byte boundary at or below the start; s > 0 needs NS >= 4).

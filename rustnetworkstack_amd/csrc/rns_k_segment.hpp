@@ -121,7 +121,7 @@ __global__ __launch_bounds__(64, (NT && BUF) ? 4 : 3) void tx_segment_kernel(con
     const uint32_t T = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(posd + nd), 63));  // <= 64 * 25
     uint32_t *slot = hd + posd;
     [[maybe_unused]] uint32_t keep = 0;
-    uint32_t ipsum = 0, tcpsum = 0, addr = 0;
+    TcpHeadSum hs;
     for (uint32_t k = 0; k < nd; ++k) {
         uint32_t d;
         __builtin_memcpy(&d, t + 4u * k, 4);
@@ -140,14 +140,9 @@ __global__ __launch_bounds__(64, (NT && BUF) ? 4 : 3) void tx_segment_kernel(con
         if (k == ipd + 4u)  // the TCP checksum as zero
             d &= 0xffff0000u;
         slot[k] = d;
-        const uint32_t b = be2(d);
-        ipsum += k < ipd ? b : 0u;
-        tcpsum += k < ipd ? 0u : b;
-        addr += (k >= (v4 ? 3u : 2u) && k < ipd) ? b : 0u;
+        hs.add(k, d, v4, ipd);
     }
-    const uint32_t ipv = fold16(ipsum) ^ 0xffffu;  // ip.rs:158-159
-    const uint32_t t1 = fold16(addr + 6u + (tcplen & 0xffffu)) + fold16(tcpsum);  // tcp.rs:957-966, then the head's L4 part
-    const uint32_t acc1 = (t1 & 0xffffu) + (t1 >> 16);
+    const uint32_t ipv = hs.ip_csum(), acc1 = hs.l4_head(tcplen);
 
     // the payload slice
     uint64_t d_start = ok ? po + a.base_adjust + skip : 0u;

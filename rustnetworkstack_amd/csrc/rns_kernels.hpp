@@ -25,7 +25,11 @@
 // bandwidth; algorithmic bytes per packet = len + 2.
 #pragma once
 
-// The device code, by kernel family (each part includes the one before it):
+// The device code, by kernel family (each part includes the ones it builds on): first the byte-order
+// helpers and the TCP head builder, last the scan and the arguments of the multi-launch entry points.
+// rns_k_flow.hpp, rns_k_plan.hpp and rns_k_echo.hpp hold kernels that are no templates and are not
+// listed: k_flow.hip, k_plan.hip and k_echo.hip, which launch them, include them.
+#include "rns_k_tcp_head.hpp"
 #include "rns_k_common.hpp"
 #include "rns_k_rounds.hpp"
 #include "rns_k_mixed.hpp"
@@ -40,6 +44,5 @@
 #include "rns_k_pool_tx.hpp"
 #include "rns_k_segment.hpp"
 #include "rns_k_pool_place.hpp"
-#include "rns_k_flow.hpp"
-#include "rns_k_plan.hpp"
-#include "rns_k_echo.hpp"
+#include "rns_k_scan.hpp"
+#include "rns_k_args.hpp"

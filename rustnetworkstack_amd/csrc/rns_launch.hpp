@@ -1,9 +1,12 @@
 // Host-side launchers of the checksum kernels (rns_kernels.hpp), one translation unit per
-// kernel family so the build compiles them in parallel: k_shapes.hip (the explicit-descriptor
-// shapes and the tuning entry), k_packed.hip (the packed form), k_chain.hip (fragment chains),
-// k_segment.hip (TCP segmentation offload), k_place.hip (TCP receive placement), k_flow.hip (TCP flow update and ACK build), k_plan.hip (TCP send planning), k_echo.hip (the ICMP echo responder), k_stash.hip (transmit fill / receive verify / transmit finalize).  rns_checksum.hip holds the
-// device entry points of the C ABI, rns_pipeline.hip the host-resident pipeline and the
-// multi-GPU contexts.
+// kernel family so the build compiles them in parallel (the declarations below say what each holds):
+//   k_shapes.hip, k_packed.hip, k_chain.hip, k_stash.hip  the checksum, fill, verify and finalize forms
+//   k_segment.hip, k_place.hip                            TCP segmentation offload, receive placement
+//   k_flow.hip, k_plan.hip, k_echo.hip                    the sequences of launches; each includes its own
+//                                                         kernels header (rns_k_flow / plan / echo.hpp)
+//   k_scan.hip                                            the scan's middle launch, which those three share
+// rns_checksum.hip holds the device entry points of the C ABI, rns_pipeline.hip the host-resident
+// pipeline and the multi-GPU contexts.
 #pragma once
 
 #include <type_traits>
@@ -103,6 +106,18 @@ inline int launch(void (*kernel)(const CsumArgs), dim3 grid, dim3 block, size_t 
     return hip_status(hipGetLastError());
 }
 
+// One step inside a launcher that is a sequence of them: a status other than RNS_OK is the launcher's.
+#define RNS_TRY(status)          \
+    do {                         \
+        if (int e = (status))    \
+            return e;            \
+    } while (0)
+#define RNS_LAUNCH(kernel, grid, block, st, ...)                                      \
+    do {                                                                              \
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, st, __VA_ARGS__);      \
+        RNS_TRY(hip_status(hipGetLastError()));                                       \
+    } while (0)
+
 // k_shapes.hip: the explicit-descriptor kernels by (variant, lanes per packet, chunks in flight)
 template <bool S>
 int dispatch(const CsumArgs &a, uint32_t variant, uint32_t G, uint32_t U, uint32_t max_blocks, hipStream_t st);
@@ -137,7 +152,8 @@ int launch_rx_place(const PlaceArgs &a, bool nt, hipStream_t st);
 // k_flow.hip: TCP flow update (count, scan, scatter, walk) and ACK build (scan, build), each a sequence of launches
 int launch_flow_update(const FlowArgs &a, hipStream_t st);
 int launch_ack_build(const AckArgs &a, hipStream_t st);
-int launch_scan2_parts(uint2 *part, uint32_t nb, uint32_t *total2, hipStream_t st);  // the scan's one-workgroup middle launch
+// k_scan.hip: the scan's one-workgroup middle launch
+int launch_scan2_parts(uint2 *part, uint32_t nb, uint32_t *total2, hipStream_t st);
 // k_plan.hip: TCP send planning (plan, scan, cap, finish), a sequence of launches
 int launch_tx_plan(const PlanArgs &a, hipStream_t st);
 // k_echo.hip: the ICMP echo responder (classify, two scans, build), after launch_rx_pool on the same stream

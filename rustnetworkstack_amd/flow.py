@@ -12,13 +12,11 @@ per flow, not 24 per datagram.  The functions are re-exported by ``batch``.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
-from .batch import _I32, _U8, _call, _require_cuda
+from .batch import _I32, _U8, _bytes_of, _call, _ptr as ptr, _require_cuda, _seq_gt, _work_bytes, _workspace
 from .place import META_DTYPE
 
 # rns_tcp_flow, rns_rx_tcp_seg, rns_tcp_flow_res (rns_checksum.h)
@@ -35,24 +33,7 @@ _M32 = 0xFFFFFFFF
 
 def flow_update_work(n_pkts: int, n_flows: int) -> int:
     """Bytes of workspace ``rx_tcp_flow_update`` (and ``tx_ack_build``) need (rns_rx_tcp_flow_update_work)."""
-    need = ctypes.c_uint64(0)
-    _lib.check(_lib.load().rns_rx_tcp_flow_update_work(n_pkts, n_flows, ctypes.byref(need)), "rns_rx_tcp_flow_update_work")
-    return int(need.value)
-
-
-def _bytes_of(t: torch.Tensor, name: str, n: int, item: int, dev) -> None:
-    _require_cuda(t, name, _U8)
-    if t.numel() != n * item or (dev is not None and t.device != dev):
-        raise ValueError(f"{name} must hold {n} records of {item} bytes on the meta's device")
-
-
-def _work(work, need: int, dev) -> torch.Tensor:
-    if work is None:
-        return torch.empty(max(need, 8), dtype=torch.uint8, device=dev)
-    _require_cuda(work, "work", _U8)
-    if work.numel() < need or work.device != dev or work.data_ptr() & 7:
-        raise ValueError(f"work must hold {need} bytes, 8-byte aligned, on the meta's device")
-    return work
+    return _work_bytes("rns_rx_tcp_flow_update_work", n_pkts, n_flows)
 
 
 def rx_tcp_flow_update(meta: torch.Tensor, flows: torch.Tensor, pend: torch.Tensor | None, *, pend_cap: int,
@@ -100,9 +81,7 @@ def rx_tcp_flow_update(meta: torch.Tensor, flows: torch.Tensor, pend: torch.Tens
         res = torch.empty((nfl, RES_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     else:
         _bytes_of(res, "res", nfl, RES_DTYPE.itemsize, dev)
-    need = flow_update_work(n, nfl)
-    work = _work(work, need, dev)
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    work = _workspace(work, flow_update_work(n, nfl), dev)
     _call("rns_rx_tcp_flow_update_dev", dev, ptr(meta), n, nfl, ptr(flows), ptr(pend) if pend_cap else None, pend_cap,
           ptr(flows_out), ptr(pend_out) if pend_cap else None, ptr(seg), ptr(res), work.data_ptr(), work.numel())
     return flows_out, pend_out, seg, res
@@ -154,8 +133,7 @@ def tx_ack_build(meta: torch.Tensor, seg: torch.Tensor, flows: torch.Tensor, tmp
         _require_cuda(n_acks, "n_acks", _I32)
         if n_acks.numel() != 2 or n_acks.device != dev:
             raise ValueError("n_acks holds two int32 entries on the meta's device")
-    work = _work(work, flow_update_work(n, 0), dev)
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
+    work = _workspace(work, flow_update_work(n, 0), dev)
     _call("rns_tx_ack_build_dev", dev, ptr(meta), ptr(seg), n, ptr(flows), nfl, ptr(tmpl), tmpl_stride, ptr(head_len8),
           int(ip_id_base), work.data_ptr(), work.numel(), ptr(out) if ack_cap else None, ack_cap,
           ptr(ack_src) if ack_cap else None, ptr(ack_len8) if ack_cap else None, n_acks.data_ptr())
@@ -165,12 +143,6 @@ def tx_ack_build(meta: torch.Tensor, seg: torch.Tensor, flows: torch.Tensor, tmp
 # ---------------------------------------------------------------------------
 # the same walk on the host
 # ---------------------------------------------------------------------------
-def _seq_gt(a: int, b: int) -> bool:
-    """util.rs:155-158."""
-    d = (a - b) & _M32
-    return d < 0x80000000 and d != 0
-
-
 def _seq_le(a: int, b: int) -> bool:
     return not _seq_gt(a, b)
 

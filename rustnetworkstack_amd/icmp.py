@@ -12,21 +12,18 @@ and ``echo_respond`` one receive -> device -> send step.  The functions are re-e
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
-from .batch import _I32, _U8, _U16, _call, _descriptors, _local_addrs, _per_packet, _require_cuda, _status
+from .batch import (_I32, _U8, _U16, _call, _descriptors, _local_addrs, _nonnull, _per_packet, _require_cuda, _status,
+                    _work_bytes, _workspace)
 from .pool import _buf_log2, recv_batch_pool, send_batch_pool
 
 
 def echo_work(n_pkts: int) -> int:
     """Bytes of workspace ``rx_icmp_echo_pool`` needs for ``n_pkts`` datagrams (rns_rx_icmp_echo_work)."""
-    need = ctypes.c_uint64(0)
-    _lib.check(_lib.load().rns_rx_icmp_echo_work(int(n_pkts), ctypes.byref(need)), "rns_rx_icmp_echo_work")
-    return int(need.value)
+    return _work_bytes("rns_rx_icmp_echo_work", int(n_pkts))
 
 
 def _new(t: torch.Tensor | None, name: str, n: int, dtype, dev) -> torch.Tensor:
@@ -86,14 +83,8 @@ def rx_icmp_echo_pool(rx_pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: t
     tx_src = _new(tx_src, "tx_src", cap, torch.int32, dev)
     count = _new(count, "count", 3, torch.int32, dev)
     need = echo_work(n)
-    if work is None:
-        work = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
-    else:
-        _require_cuda(work, "work", (torch.int64,))
-        if work.numel() * 8 < need or work.device != dev:
-            raise ValueError(f"work needs {need} bytes (echo_work) on {dev}")
-    keep = torch.empty(16, dtype=torch.uint8, device=dev)  # (empty tensors have a null data_ptr)
-    ptr = lambda t: t.data_ptr() or keep.data_ptr()  # noqa: E731
+    work = _workspace(work, need, dev, torch.int64, f"work needs {need} bytes (echo_work) on {dev}")
+    ptr = _nonnull(dev)
     _call("rns_rx_icmp_echo_pool_dev", dev, rx_pool.data_ptr(), rx_pool.numel(), log2, buf_idx.data_ptr(), nf,
           ptr(blk_first), ptr(len16), n, ip4, ip6, ptr(tx_pool), tx_pool.numel(), free.data_ptr(), n_free, cap,
           int(ip_id_base), None if ip_id_add is None else ip_id_add.data_ptr(), tx_blk_first.data_ptr(),

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import _I32, _I64, _U8, _U16, _call, _descriptors, _local_addrs, _per_packet, _status
+from .batch import _I32, _I64, _U8, _U16, _call, _descriptors, _local_addrs, _nonnull, _per_packet, _seq_gt, _status
 from .pool import _buf_log2
 
 # rns_rx_tcp_meta (rns_checksum.h), one record per datagram
@@ -103,20 +103,12 @@ def rx_tcp_place_pool(pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: torc
         meta = torch.empty((n, META_DTYPE.itemsize), dtype=torch.uint8, device=dev)
     else:
         _per_packet(meta, "meta", n * META_DTYPE.itemsize, dev, _U8)
-    # (empty tensors have a null data_ptr: the entry point wants the pointers even where nothing is read)
-    keep = torch.empty(16, dtype=torch.uint8, device=dev) if min(nfl, stream.numel()) == 0 else None
-    ptr = lambda t: t.data_ptr() or keep.data_ptr()  # noqa: E731
+    ptr = _nonnull(dev)
     _call("rns_rx_tcp_place_pool_dev", dev, pool.data_ptr(), pool.numel(), log2, buf_idx.data_ptr(), nf,
           blk_first.data_ptr(), len16.data_ptr(), n, ip4, ip6, table.data_ptr(), table.numel(), ptr(next_seq),
           ptr(win_off), ptr(win_len), nfl, ptr(stream), stream.numel(), status.data_ptr(),
           _per_packet(l4_sum, "l4_sum", n, dev), meta.data_ptr())
     return status, l4_sum, meta
-
-
-def _seq_gt(a: int, b: int) -> bool:
-    """util.rs:155-158."""
-    diff = (a - b) & 0xFFFFFFFF
-    return diff < 0x80000000 and diff != 0
 
 
 class Reassembler:

@@ -11,14 +11,12 @@ by ``batch``.
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
-from .batch import _I32, _I64, _U8, _U16, _call, _require_cuda
-from .flow import FLOW_DTYPE, _bytes_of, _work
+from .batch import _I32, _I64, _U8, _U16, _bytes_of, _call, _ptr as ptr, _require_cuda, _work_bytes, _workspace
+from .flow import FLOW_DTYPE
 
 # rns_tx_plan_res (rns_checksum.h)
 RES_DTYPE = np.dtype([("new_bytes", "<u4"), ("new_segs", "<u4"), ("rexmit_bytes", "<u4"), ("why", "u1"), ("pad", "u1", (3,))])
@@ -29,9 +27,7 @@ _M32 = 0xFFFFFFFF
 
 def tx_plan_work(n_flows: int) -> int:
     """Bytes of workspace ``tx_tcp_plan`` needs (rns_tx_tcp_plan_work)."""
-    need = ctypes.c_uint64(0)
-    _lib.check(_lib.load().rns_tx_tcp_plan_work(n_flows, ctypes.byref(need)), "rns_tx_tcp_plan_work")
-    return int(need.value)
+    return _work_bytes("rns_tx_tcp_plan_work", n_flows)
 
 
 def _per_flow(t: torch.Tensor, name: str, n: int, dtypes, dev) -> None:
@@ -83,14 +79,13 @@ def tx_tcp_plan(flows: torch.Tensor, sq_off: torch.Tensor, sq_seq: torch.Tensor,
         flows_out = torch.empty_like(flows)
     else:
         _bytes_of(flows_out, "flows_out", nfl, FLOW_DTYPE.itemsize, dev)
-    work = _work(work, tx_plan_work(nfl), dev)
+    work = _workspace(work, tx_plan_work(nfl), dev)
     E = 2 * nfl
     new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)  # noqa: E731
     p = {"tmpl": new((E, stride), torch.uint8), "head_len8": new(E, torch.uint8), "pay_off": new(E, torch.int64),
          "pay_len": new(E, torch.int32), "mss": new(E, torch.uint16), "head_off": new(E, torch.int64),
          "seg_first": new(E + 1, torch.int32), "blk_flow": new((seg_cap + 63) // 64, torch.int32),
          "n": new(2, torch.int32), "res": new((nfl, RES_DTYPE.itemsize), torch.uint8), "flows_out": flows_out}
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None  # noqa: E731
     _call("rns_tx_tcp_plan_dev", dev, ptr(flows), ptr(flows_out), nfl, ptr(sq_off), ptr(sq_seq), ptr(sq_len), ptr(mss),
           ptr(rexmit), ptr(tmpl), stride, ptr(head_len8), int(ip_id_base), ptr(ip_id_add), head_first_off & (2 ** 64 - 1),
           seg_cap, ptr(p["tmpl"]), ptr(p["head_len8"]), ptr(p["pay_off"]), ptr(p["pay_len"]), ptr(p["mss"]),
@@ -123,7 +118,7 @@ def tx_tcp_send(arena: torch.Tensor, flows: torch.Tensor, sq_off: torch.Tensor, 
 # the same plan on the host
 # ---------------------------------------------------------------------------
 def _tmpl_ok(t: np.ndarray, hl: int, stride: int) -> bool:
-    """The template rule of rns_tx_ack_build_dev."""
+    """The template rule of the ACK build and the planning (tcp_tmpl_ok, rns_k_tcp_head.hpp)."""
     if hl not in (40, 60) or hl > stride:
         return False
     if hl == 40:

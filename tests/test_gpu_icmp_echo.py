@@ -242,6 +242,26 @@ def test_both_pools_in_one(B):
     assert (r["echo"] == (REQ | BUILT)).all()
 
 
+@pytest.mark.parametrize("n", [255, 256, 257, 65537])
+def test_scan_block_boundaries(n):
+    """The scan under the responder at its block boundaries: n 84-byte pings, IPv4 and IPv6 alternating (the
+    scan's components differ), one workgroup short by one, one, one more, and one more than 256 workgroups
+    (the middle kernel's loop runs twice).  run() compares every output with echo_host; at the three small
+    counts the replies are also the restated reference's (respond_ref is a Python object per buffer: at
+    65537 it would take most of a minute, and echo_host is pinned to it by test_icmp_echo_ref.py)."""
+    B = 256
+    kinds = [H.ping4(H.body(k, 60)) if k % 2 == 0 else H.ping6(H.body(k, 40)) for k in range(16)]
+    assert all(len(p) == 84 for p in kinds)
+    pkts = [kinds[i % 16] for i in range(n)]
+    r = run(pkts, B, ip_id_base=0xFFF0)
+    assert (r["echo"] == (REQ | BUILT)).all() and r["count"].tolist() == [n, 2 * n, (n + 1) // 2]
+    assert r["src"].tolist() == list(range(n))
+    if n <= 257:
+        ntx = tx_needed(pkts, B) + 5
+        ans, ref, _, _ = H.respond_ref(pkts, B, np.full(ntx * B, TXFILL, dtype=np.uint8), r["free"], next_id=0xFFF0)
+        assert all(ans) and replies(r, B) == H.reply_datagrams(ref)
+
+
 def test_no_datagrams():
     cnt = Guarded(12)
     batch._call("rns_rx_icmp_echo_pool_dev", torch.device(DEV), None, 0, 9, None, 0, None, None, 0, H.L4, H.L6, None, 0, None, 0,

@@ -267,6 +267,51 @@ def test_ack_build_counts_only():
     assert n_acks.cpu().tolist() == [0, 0]
 
 
+def scan_ack_case(n):
+    """n flows with one data segment each (in reverse flow order), every flow one short of an immediate
+    ACK, IPv4 and IPv6 heads alternating: every datagram is an ACK, every other one takes an id."""
+    f = np.arange(n)
+    tmpl = np.full((n, 64), 0xA5, dtype=np.uint8)
+    t4, t6 = template(L4, V4A, 80, 4000, junk=0x5A), template(L6, V6A, 80, 4000, junk=0x3C)
+    tmpl[0::2, :40], tmpl[1::2, :60] = np.frombuffer(t4, dtype=np.uint8), np.frombuffer(t6, dtype=np.uint8)
+    hl = np.where(f % 2 == 0, 40, 60).astype(np.uint8)
+    ports = (1024 + f % 60000).astype(">u2").view(np.uint8).reshape(n, 2)
+    tmpl[0::2, 22:24], tmpl[1::2, 42:44] = ports[0::2], ports[1::2]   # the destination port
+    flows = np.zeros(n, dtype=FLOW)
+    flows["rcv_nxt"] = flows["rcv_max"] = 1000 + 7 * f
+    flows["snd_nxt"], flows["rq_len"], flows["delayed_acks"], flows["state"] = 0xFFFF0000 + f, f % 65536, 4, 1
+    meta = np.zeros(n, dtype=META)
+    meta["flow"], meta["tcp_hdr"], meta["ip_hdr"], meta["place"] = f[::-1], 20, 20, P_TCP | P_FLOW | 4
+    meta["seq"], meta["pay_len"], meta["flags"] = 1000 + 7 * f[::-1], 1 + f % 50, ACK | PSH
+    return meta, flows, tmpl, hl
+
+
+@pytest.mark.parametrize("n", [255, 256, 257, 65537])
+def test_ack_build_scan_block_boundaries(n):
+    """The scan under the ACK build at its block boundaries: one block short by one, one block, one more,
+    and one more than 256 blocks (the middle kernel's loop runs twice).  The two scan components differ."""
+    meta, flows, tmpl, hl = scan_ack_case(n)
+    (fl, _, seg, _), _ = check_update(meta, flows, None, 0)
+    base = 0xFFF0
+    heads, n4 = ack_heads_ref(meta, seg, fl, [bytes(r) for r in tmpl], hl, base)
+    assert len(heads) == n and n4 == (n + 1) // 2 and all(h is not None for _, h in heads)
+    want_out = np.full((n, 64), FILL, dtype=np.uint8)
+    for k, (_, head) in enumerate(heads):
+        want_out[k, :len(head)] = np.frombuffer(head, dtype=np.uint8)
+    want_len = np.array([len(h) for _, h in heads], dtype=np.uint8)
+    assert set(want_len[:2].tolist()) == {40, 60}
+    o_out, o_src, o_len, o_n = Guarded(64 * n), Guarded(4 * n, torch.int32), Guarded(n), Guarded(8, torch.int32)
+    tx_ack_build(dev(meta), dev(seg), dev(fl), torch.from_numpy(tmpl).to(DEV), torch.from_numpy(hl).to(DEV), base, ack_cap=n,
+                 out=o_out.t, ack_src=o_src.t, ack_len8=o_len.t, n_acks=o_n.t)
+    torch.cuda.synchronize()
+    assert o_n.host(np.uint32).tolist() == [n, n4]
+    assert np.array_equal(o_src.host(np.uint32), np.array([i for i, _ in heads], dtype=np.uint32))
+    assert np.array_equal(o_len.host(np.uint8), want_len)
+    got = o_out.host(np.uint8).reshape(n, 64)
+    bad = np.flatnonzero((got != want_out).any(axis=1))
+    assert bad.size == 0, (bad[:5].tolist(), got[bad[0]].tobytes().hex(), want_out[bad[0]].tobytes().hex())
+
+
 # 10. end to end: placement -> update -> build ---------------------------------------------------------
 @pytest.mark.parametrize("buf", [128, 512])
 def test_end_to_end(buf):
