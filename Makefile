@@ -9,23 +9,13 @@ CSRC     := $(PKG)/csrc
 BUILD    := $(PKG)/build
 LIB      := $(PKG)/librns_checksum.so
 
-# Plain C callers of the C ABI (no torch): built here, run on a GPU by tests/test_c_caller.py
-# (test_batch_abi), tests/test_c_caller_tx_chain_packed.py (the compact-descriptor chain finalize),
-# tests/test_c_caller_rx_chain.py (the receive verify over fragment chains),
-# tests/test_c_caller_rx_pool.py (the receive verify over pool buffers),
-# tests/test_c_caller_tx_pool.py (the transmit finalize over pool buffers),
-# tests/test_c_caller_tx_segment.py (TCP segmentation offload),
-# tests/test_c_caller_rx_place.py (TCP receive placement), tests/test_c_caller_rx_flow.py (TCP flow
-# update and ACK build), tests/test_c_caller_tx_plan.py (TCP send planning, then segmentation) and
-# tests/test_c_caller_icmp_echo.py (the ICMP echo responder).
-CABI_TESTS := tests/c/test_batch_abi tests/c/test_tx_chain_packed_abi tests/c/test_rx_chain_abi \
-              tests/c/test_rx_pool_abi tests/c/test_tx_pool_abi tests/c/test_tx_segment_abi \
-              tests/c/test_rx_place_abi tests/c/test_rx_flow_abi tests/c/test_tx_plan_abi \
-              tests/c/test_icmp_echo_abi
+# Plain C callers of the C ABI (no torch) over the one harness tests/c/abi_test.h: built here, run by
+# tests/test_c_caller.py (one PROGRAMS line each).
+CABI_TESTS := $(patsubst %.c,%,$(wildcard tests/c/test_*_abi.c))
 
 all: $(LIB) oracle $(CABI_TESTS)
 
-$(CABI_TESTS): tests/c/%: tests/c/%.c oracle/csum_oracle.c include/rns_checksum.h $(LIB)
+$(CABI_TESTS): tests/c/%: tests/c/%.c tests/c/abi_test.h oracle/csum_oracle.c include/rns_checksum.h $(LIB)
 	gcc -std=gnu11 -O1 -Wall -Wextra -Werror -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include \
 	    $< oracle/csum_oracle.c -L$(PKG) -lrns_checksum -Wl,-rpath,'$$ORIGIN/../../$(PKG)' \
 	    -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread -o $@
@@ -53,10 +43,10 @@ $(LIB): $(HIP_OBJS) $(BUILD)/host_checksum.o $(BUILD)/host_io.o
 oracle:
 	$(MAKE) -C oracle
 
-# A/B experiment build: `make -j8 ab ABDEF="-DRNS_ROWS_D=4" ABNAME=d4` -> tools/ab/librns_checksum_d4.so
+# A/B experiment build: `make -j8 ab ABDEF="-DRNS_RX_ROWS_D=4" ABNAME=d4` -> tools/ab/librns_checksum_d4.so
 # (load it with RNS_CHECKSUM_LIB=...).  Knobs: RNS_CLASS_LOG2G / RNS_CLASS_U (class-kernel shapes),
-# RNS_MIXED_OCC / RNS_FILL_OCC / RNS_CHAIN_OCC (waves/SIMD bounds), RNS_ROWS_D, RNS_STREAM_MAXLEN, ...
-ABDEF  ?= -DRNS_ROWS_D=4
+# RNS_MIXED_OCC / RNS_FILL_OCC / RNS_CHAIN_OCC (waves/SIMD bounds), RNS_RX_ROWS_D / RNS_TXROWS_D, RNS_STREAM_NT, ...
+ABDEF  ?= -DRNS_RX_ROWS_D=4
 ABNAME ?= d4
 AB_BUILD := $(BUILD)/ab_$(ABNAME)
 AB_OBJS  := $(patsubst $(CSRC)/%.hip,$(AB_BUILD)/%.o,$(HIP_SRCS))

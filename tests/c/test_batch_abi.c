@@ -4,62 +4,10 @@
  * only for device memory.  Every result is checked against the oracle
  * (oracle/csum_oracle.c, linked here as test infrastructure only).
  *
- *   gcc -std=gnu11 -D__HIP_PLATFORM_AMD__ -I include -I /opt/rocm/include tests/c/test_batch_abi.c \
- *       oracle/csum_oracle.c -L rustnetworkstack_amd -lrns_checksum -L /opt/rocm/lib -lamdhip64 -lpthread
- *
  * Prints "all checks passed" and exits 0 on success.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "rns_checksum.h"
-
-int32_t oracle_compute_ones_comp(uint16_t in_checksum, const uint8_t *slice, size_t len);
-int32_t oracle_compute_checksum(const uint8_t *slice, size_t len);
-int32_t oracle_compute_pseudo_header_checksum(const uint8_t *src, size_t src_len, const uint8_t *dst, size_t dst_len,
-                                              uint64_t length, uint8_t protocol);
-void oracle_chain_batch(const uint8_t *arena, const uint64_t *frag_off, const uint32_t *frag_len, const uint32_t *first,
-                        const uint16_t *seed, uint16_t *out, size_t npkts, int complement);
-
-static uint64_t rng_state = 0x5EEDC0DEull;
-static uint64_t next_u64(void)
-{
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-static int failures = 0;
-#define CHECK(cond, ...)                                                                           \
-    do {                                                                                           \
-        if (!(cond)) {                                                                             \
-            if (failures++ < 10) {                                                                 \
-                fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__);                               \
-                fprintf(stderr, __VA_ARGS__);                                                      \
-                fprintf(stderr, "\n");                                                             \
-            }                                                                                      \
-        }                                                                                          \
-    } while (0)
-#define HIP_OK(x)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_));              \
-            return 2;                                                                              \
-        }                                                                                          \
-    } while (0)
-
-static void fill_random(uint8_t *p, uint64_t bytes)
-{
-    for (uint64_t b = 0; b < bytes; b += 8) {
-        const uint64_t w = next_u64();
-        memcpy(p + b, &w, bytes - b < 8 ? bytes - b : 8);
-    }
-}
+#define ABI_TEST_SEED 0x5EEDC0DEull
+#include "abi_test.h"
 
 /* rns_csum_batch_packed_dev (util.rs:88-110 per packet, offsets implied by the lengths):
  * lengths 1..1600 plus some jumbo ones, packed at 16-byte alignment by rns_packed_layout,
@@ -85,41 +33,35 @@ static int test_packed(hipStream_t st)
         CHECK(off[i] % 16 == 0 && (i == 0 || off[i] >= off[i - 1] + len16[i - 1]), "packed layout packet %u", i);
         want[i] = (uint16_t)(0xffffu ^ (uint32_t)oracle_compute_ones_comp(seed[i], arena + off[i], len16[i]));
     }
-    uint8_t *d_arena;
-    uint64_t *d_blk;
-    uint16_t *d_len16, *d_seed, *d_out;
-    uint32_t *d_bad, bad = 1;
-    HIP_OK(hipMalloc((void **)&d_arena, bytes));
-    HIP_OK(hipMalloc((void **)&d_blk, ((n + 63) / 64) * sizeof *blk));
-    HIP_OK(hipMalloc((void **)&d_len16, n * sizeof *len16));
-    HIP_OK(hipMalloc((void **)&d_seed, n * sizeof *seed));
-    HIP_OK(hipMalloc((void **)&d_out, n * sizeof *got));
-    HIP_OK(hipMalloc((void **)&d_bad, sizeof *d_bad));
-    HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_blk, blk, ((n + 63) / 64) * sizeof *blk, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_len16, len16, n * sizeof *len16, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_seed, seed, n * sizeof *seed, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_bad, 0, sizeof *d_bad));
+    uint8_t *d_arena = NULL;
+    uint64_t *d_blk = NULL;
+    uint16_t *d_len16 = NULL, *d_seed = NULL, *d_out = NULL;
+    uint32_t *d_bad = NULL, bad = 1;
+    UP(d_arena, arena, bytes);
+    UP(d_blk, blk, ((n + 63) / 64) * sizeof *blk);
+    UP(d_len16, len16, n * sizeof *len16);
+    UP(d_seed, seed, n * sizeof *seed);
+    OUT(d_bad, sizeof *d_bad, 0);
     const uint32_t hints[3] = {64u, 340u, 1500u};  /* tiny-packet rounds kernel, mixed, mixed nt */
     for (int h = 0; h < 3; ++h) {
-        HIP_OK(hipMemset(d_out, 0, n * sizeof *got));
+        OUT(d_out, n * sizeof *got, 0);
         CHECK(rns_csum_batch_packed_dev(d_arena, bytes, d_blk, d_len16, 4, d_seed, d_out, n, RNS_FLAG_COMPLEMENT,
                                         hints[h], d_bad, st) == RNS_OK,
               "rns_csum_batch_packed_dev hint %u", hints[h]);
         HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipMemcpy(got, d_out, n * sizeof *got, hipMemcpyDeviceToHost));
+        DOWN(got, d_out, n * sizeof *got);
         for (uint32_t i = 0; i < n; ++i)
             CHECK(got[i] == want[i], "packed batch (hint %u) packet %u (len %u): %04x != %04x", hints[h], i, len16[i],
                   got[i], want[i]);
     }
     /* a cut-short arena: the packets past it are rejected (0) and counted */
     const uint64_t cut = off[n - 5];
-    HIP_OK(hipMemset(d_out, 0xff, n * sizeof *got));
+    OUT(d_out, n * sizeof *got, 0xff);
     CHECK(rns_csum_batch_packed_dev(d_arena, cut, d_blk, d_len16, 4, d_seed, d_out, n, RNS_FLAG_COMPLEMENT, 340u,
                                     d_bad, st) == RNS_OK, "packed, short arena");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(got, d_out, n * sizeof *got, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost));
+    DOWN(got, d_out, n * sizeof *got);
+    DOWN(&bad, d_bad, sizeof bad);
     for (uint32_t i = 0; i < n; ++i)
         CHECK(got[i] == (i < n - 5 ? want[i] : 0u), "short arena packet %u: %04x", i, got[i]);
     CHECK(bad == 5, "short arena: d_bad = %u (want 5)", bad);
@@ -139,14 +81,14 @@ static int test_packed(hipStream_t st)
         f[0] = f0;
         f[1] = f1;
     }
-    HIP_OK(hipMemset(d_bad, 0, sizeof *d_bad));
+    OUT(d_bad, sizeof *d_bad, 0);
     CHECK(rns_csum_fill_packed_dev(d_arena, bytes, d_blk, d_len16, 4, d_seed, NULL, 16, d_out, n, RNS_FLAG_COMPLEMENT,
                                    340u, d_bad, st) == RNS_OK, "rns_csum_fill_packed_dev");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(got, d_out, n * sizeof *got, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost));
+    DOWN(got, d_out, n * sizeof *got);
+    DOWN(&bad, d_bad, sizeof bad);
     uint8_t *back = malloc(bytes);
-    HIP_OK(hipMemcpy(back, d_arena, bytes, hipMemcpyDeviceToHost));
+    DOWN(back, d_arena, bytes);
     uint64_t changed = 0;
     for (uint32_t i = 0; i < n; ++i) {
         CHECK(got[i] == want[i], "packed fill packet %u (len %u): %04x != %04x", i, len16[i], got[i], want[i]);
@@ -163,7 +105,6 @@ static int test_packed(hipStream_t st)
     CHECK(changed == 0, "packed fill: %llu bytes outside the fields changed", (unsigned long long)changed);
     CHECK(bad == short_pkts, "packed fill: d_bad = %u (want %u)", bad, short_pkts);
     free(back);
-    hipFree(d_arena); hipFree(d_blk); hipFree(d_len16); hipFree(d_seed); hipFree(d_out); hipFree(d_bad);
     free(len16); free(seed); free(want); free(got); free(off); free(blk); free(len32); free(arena);
     return 0;
 }
@@ -185,22 +126,18 @@ static int test_strided(hipStream_t st)
             want[i] = (uint16_t)(0xffffu ^ (uint32_t)oracle_compute_ones_comp(
                                                seed[i], arena + cases[c].first + (uint64_t)i * cases[c].stride,
                                                cases[c].len));
-        uint8_t *d_arena;
-        uint16_t *d_seed, *d_out;
-        HIP_OK(hipMalloc((void **)&d_arena, bytes));
-        HIP_OK(hipMalloc((void **)&d_seed, n * sizeof *seed));
-        HIP_OK(hipMalloc((void **)&d_out, n * sizeof *got));
-        HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(d_seed, seed, n * sizeof *seed, hipMemcpyHostToDevice));
-        HIP_OK(hipMemset(d_out, 0, n * sizeof *got));
+        uint8_t *d_arena = NULL;
+        uint16_t *d_seed = NULL, *d_out = NULL;
+        UP(d_arena, arena, bytes);
+        UP(d_seed, seed, n * sizeof *seed);
+        OUT(d_out, n * sizeof *got, 0);
         CHECK(rns_csum_batch_strided_dev(d_arena, bytes, cases[c].first, cases[c].stride, cases[c].len, d_seed, d_out,
                                          n, RNS_FLAG_COMPLEMENT, NULL, st) == RNS_OK,
               "rns_csum_batch_strided_dev case %d", c);
         HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipMemcpy(got, d_out, n * sizeof *got, hipMemcpyDeviceToHost));
+        DOWN(got, d_out, n * sizeof *got);
         for (uint32_t i = 0; i < n; ++i)
             CHECK(got[i] == want[i], "strided case %d packet %u: %04x != %04x", c, i, got[i], want[i]);
-        hipFree(d_arena); hipFree(d_seed); hipFree(d_out);
         free(arena);
     }
     free(seed); free(want); free(got);
@@ -242,39 +179,30 @@ static int test_chains(hipStream_t st)
     uint8_t *arena = malloc(bytes);
     fill_random(arena, bytes);
     oracle_chain_batch(arena, foff, flen, first, seed, want, npk, 1);
-    uint8_t *d_arena;
-    uint64_t *d_foff;
-    uint32_t *d_flen, *d_first, *d_bad, bad = 1;
-    uint16_t *d_seed, *d_out;
-    HIP_OK(hipMalloc((void **)&d_arena, bytes));
-    HIP_OK(hipMalloc((void **)&d_foff, nf * sizeof *foff));
-    HIP_OK(hipMalloc((void **)&d_flen, nf * sizeof *flen));
-    HIP_OK(hipMalloc((void **)&d_first, (npk + 1) * sizeof *first));
-    HIP_OK(hipMalloc((void **)&d_seed, npk * sizeof *seed));
-    HIP_OK(hipMalloc((void **)&d_out, npk * sizeof *got));
-    HIP_OK(hipMalloc((void **)&d_bad, sizeof *d_bad));
-    HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_foff, foff, nf * sizeof *foff, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_flen, flen, nf * sizeof *flen, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_first, first, (npk + 1) * sizeof *first, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_seed, seed, npk * sizeof *seed, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_bad, 0, sizeof *d_bad));
+    uint8_t *d_arena = NULL;
+    uint64_t *d_foff = NULL;
+    uint32_t *d_flen = NULL, *d_first = NULL, *d_bad = NULL, bad = 1;
+    uint16_t *d_seed = NULL, *d_out = NULL;
+    UP(d_arena, arena, bytes);
+    UP(d_foff, foff, nf * sizeof *foff);
+    UP(d_flen, flen, nf * sizeof *flen);
+    UP(d_first, first, (npk + 1) * sizeof *first);
+    UP(d_seed, seed, npk * sizeof *seed);
+    OUT(d_bad, sizeof *d_bad, 0);
     const uint32_t flags[2] = {RNS_FLAG_COMPLEMENT, RNS_FLAG_COMPLEMENT | RNS_FLAG_CHAIN_RUNS};
     for (int f = 0; f < 2; ++f) {
-        HIP_OK(hipMemset(d_out, 0, npk * sizeof *got));
+        OUT(d_out, npk * sizeof *got, 0);
         CHECK(rns_csum_chain_dev(d_arena, bytes, d_foff, d_flen, nf, d_first, d_seed, d_out, npk, flags[f], 350u, NULL,
                                  d_bad, st) == RNS_OK,
               "rns_csum_chain_dev flags %u", flags[f]);
         HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipMemcpy(got, d_out, npk * sizeof *got, hipMemcpyDeviceToHost));
+        DOWN(got, d_out, npk * sizeof *got);
         for (uint32_t i = 0; i < npk; ++i)
             CHECK(got[i] == want[i], "chain (flags %u) packet %u (%u fragments): %04x != %04x", flags[f], i,
                   first[i + 1] - first[i], got[i], want[i]);
     }
-    HIP_OK(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost));
+    DOWN(&bad, d_bad, sizeof bad);
     CHECK(bad == 0, "chains: d_bad = %u", bad);
-    hipFree(d_arena); hipFree(d_foff); hipFree(d_flen); hipFree(d_first); hipFree(d_seed); hipFree(d_out);
-    hipFree(d_bad);
     free(first); free(foff); free(flen); free(seed); free(want); free(got); free(arena);
     return 0;
 }
@@ -317,38 +245,31 @@ static int test_chain_fill(hipStream_t st)
         expect[foff[first[i]] + fo] = expect[foff[first[i]] + fo + 1] = 0;
     oracle_chain_batch(expect, foff, flen, first, seed, want, npk, 1);
     for (uint32_t i = 0; i < npk; ++i) {
-        expect[foff[first[i]] + fo] = (uint8_t)(want[i] >> 8);
-        expect[foff[first[i]] + fo + 1] = (uint8_t)want[i];
+        put16(expect + foff[first[i]] + fo, want[i]);
     }
-    uint8_t *d_arena;
-    uint64_t *d_foff;
-    uint32_t *d_flen, *d_first, *d_bad, bad = 1;
-    uint16_t *d_seed, *d_out;
-    HIP_OK(hipMalloc((void **)&d_arena, bytes));
-    HIP_OK(hipMalloc((void **)&d_foff, nf * sizeof *foff));
-    HIP_OK(hipMalloc((void **)&d_flen, nf * sizeof *flen));
-    HIP_OK(hipMalloc((void **)&d_first, (npk + 1) * sizeof *first));
-    HIP_OK(hipMalloc((void **)&d_seed, npk * sizeof *seed));
-    HIP_OK(hipMalloc((void **)&d_out, npk * sizeof *got));
-    HIP_OK(hipMalloc((void **)&d_bad, sizeof *d_bad));
-    HIP_OK(hipMemcpy(d_foff, foff, nf * sizeof *foff, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_flen, flen, nf * sizeof *flen, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_first, first, (npk + 1) * sizeof *first, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_seed, seed, npk * sizeof *seed, hipMemcpyHostToDevice));
+    uint8_t *d_arena = NULL;
+    uint64_t *d_foff = NULL;
+    uint32_t *d_flen = NULL, *d_first = NULL, *d_bad = NULL, bad = 1;
+    uint16_t *d_seed = NULL, *d_out = NULL;
+    UP(d_foff, foff, nf * sizeof *foff);
+    UP(d_flen, flen, nf * sizeof *flen);
+    UP(d_first, first, (npk + 1) * sizeof *first);
+    UP(d_seed, seed, npk * sizeof *seed);
+    OUT(d_out, npk * sizeof *got, 0);
     /* the chain kernel at two hints, then the transmit-rows kernel (RNS_FLAG_CHAIN_TX_PACKED:
      * these scattered payloads take its exact per-packet loop) */
     const uint32_t hints[3] = {512u, 100u, 512u};
     const uint32_t flags[3] = {RNS_FLAG_COMPLEMENT, RNS_FLAG_COMPLEMENT, RNS_FLAG_COMPLEMENT | RNS_FLAG_CHAIN_TX_PACKED};
     for (int h = 0; h < 3; ++h) {
-        HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
-        HIP_OK(hipMemset(d_bad, 0, sizeof *d_bad));
+        UP(d_arena, arena, bytes);
+        OUT(d_bad, sizeof *d_bad, 0);
         CHECK(rns_csum_chain_fill_dev(d_arena, bytes, d_foff, d_flen, nf, d_first, d_seed, NULL, fo, d_out, npk,
                                       flags[h], hints[h], d_bad, st) == RNS_OK,
               "rns_csum_chain_fill_dev hint %u flags %x", hints[h], flags[h]);
         HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipMemcpy(got, d_out, npk * sizeof *got, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(after, d_arena, bytes, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost));
+        DOWN(got, d_out, npk * sizeof *got);
+        DOWN(after, d_arena, bytes);
+        DOWN(&bad, d_bad, sizeof bad);
         for (uint32_t i = 0; i < npk; ++i)
             CHECK(got[i] == want[i], "chain fill (hint %u) packet %u: %04x != %04x", hints[h], i, got[i], want[i]);
         uint64_t diff = 0;
@@ -357,8 +278,6 @@ static int test_chain_fill(hipStream_t st)
         CHECK(diff == 0, "chain fill (hint %u): %llu arena bytes differ", hints[h], (unsigned long long)diff);
         CHECK(bad == 0, "chain fill: d_bad = %u", bad);
     }
-    hipFree(d_arena); hipFree(d_foff); hipFree(d_flen); hipFree(d_first); hipFree(d_seed); hipFree(d_out);
-    hipFree(d_bad);
     free(first); free(foff); free(flen); free(seed); free(want); free(got); free(arena); free(expect); free(after);
     return 0;
 }
@@ -398,33 +317,26 @@ static int test_chain_fill_txpacked(hipStream_t st)
         expect[foff[first[i]] + fo] = expect[foff[first[i]] + fo + 1] = 0;
     oracle_chain_batch(expect, foff, flen, first, seed, want, npk, 1);
     for (uint32_t i = 0; i < npk; ++i) {
-        expect[foff[first[i]] + fo] = (uint8_t)(want[i] >> 8);
-        expect[foff[first[i]] + fo + 1] = (uint8_t)want[i];
+        put16(expect + foff[first[i]] + fo, want[i]);
     }
-    uint8_t *d_arena;
-    uint64_t *d_foff;
-    uint32_t *d_flen, *d_first, *d_bad, bad = 1;
-    uint16_t *d_seed, *d_out;
-    HIP_OK(hipMalloc((void **)&d_arena, bytes));
-    HIP_OK(hipMalloc((void **)&d_foff, nf * sizeof *foff));
-    HIP_OK(hipMalloc((void **)&d_flen, nf * sizeof *flen));
-    HIP_OK(hipMalloc((void **)&d_first, (npk + 1) * sizeof *first));
-    HIP_OK(hipMalloc((void **)&d_seed, npk * sizeof *seed));
-    HIP_OK(hipMalloc((void **)&d_out, npk * sizeof *got));
-    HIP_OK(hipMalloc((void **)&d_bad, sizeof *d_bad));
-    HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_foff, foff, nf * sizeof *foff, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_flen, flen, nf * sizeof *flen, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_first, first, (npk + 1) * sizeof *first, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_seed, seed, npk * sizeof *seed, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_bad, 0, sizeof *d_bad));
+    uint8_t *d_arena = NULL;
+    uint64_t *d_foff = NULL;
+    uint32_t *d_flen = NULL, *d_first = NULL, *d_bad = NULL, bad = 1;
+    uint16_t *d_seed = NULL, *d_out = NULL;
+    UP(d_arena, arena, bytes);
+    UP(d_foff, foff, nf * sizeof *foff);
+    UP(d_flen, flen, nf * sizeof *flen);
+    UP(d_first, first, (npk + 1) * sizeof *first);
+    UP(d_seed, seed, npk * sizeof *seed);
+    OUT(d_bad, sizeof *d_bad, 0);
+    OUT(d_out, npk * sizeof *got, 0);
     CHECK(rns_csum_chain_fill_dev(d_arena, bytes, d_foff, d_flen, nf, d_first, d_seed, NULL, fo, d_out, npk,
                                   RNS_FLAG_COMPLEMENT | RNS_FLAG_CHAIN_TX_PACKED, 750u, d_bad, st) == RNS_OK,
           "rns_csum_chain_fill_dev (transmit-packed)");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(got, d_out, npk * sizeof *got, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(after, d_arena, bytes, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost));
+    DOWN(got, d_out, npk * sizeof *got);
+    DOWN(after, d_arena, bytes);
+    DOWN(&bad, d_bad, sizeof bad);
     for (uint32_t i = 0; i < npk; ++i)
         CHECK(got[i] == want[i], "transmit-packed chain fill packet %u: %04x != %04x", i, got[i], want[i]);
     uint64_t diff = 0;
@@ -432,8 +344,6 @@ static int test_chain_fill_txpacked(hipStream_t st)
         diff += after[b] != expect[b];
     CHECK(diff == 0, "transmit-packed chain fill: %llu arena bytes differ", (unsigned long long)diff);
     CHECK(bad == 0, "transmit-packed chain fill: d_bad = %u", bad);
-    hipFree(d_arena); hipFree(d_foff); hipFree(d_flen); hipFree(d_first); hipFree(d_seed); hipFree(d_out);
-    hipFree(d_bad);
     free(first); free(foff); free(flen); free(seed); free(want); free(got); free(arena); free(expect); free(after);
     return 0;
 }
@@ -464,42 +374,29 @@ static int test_tx_rx(hipStream_t st)
     uint8_t *arena = malloc(bytes), *ref = malloc(bytes), *back = malloc(bytes);
     fill_random(arena, bytes);
     for (uint32_t i = 0; i < n; ++i) {
-        uint8_t *h = arena + off[i];
-        h[0] = 0x45; h[1] = 0; h[2] = (uint8_t)(len[i] >> 8); h[3] = (uint8_t)len[i];
-        h[6] = 0x40; h[7] = 0; h[8] = 64; h[9] = proto[i];
-        memcpy(h + 12, src, 4);
-        memcpy(h + 16, dst, 4);                      /* header checksum and L4 field keep their garbage */
+        ipv4_fields(arena + off[i], len[i], proto[i], src, dst);  /* header checksum and L4 field keep their garbage */
     }
     /* expected bytes: the fields zeroed, then filled as the reference's output paths fill them */
     memcpy(ref, arena, bytes);
     for (uint32_t i = 0; i < n; ++i) {
-        uint8_t *h = ref + off[i], *seg = h + 20;
-        const uint32_t seglen = len[i] - 20, field = proto[i] == 6 ? 16u : proto[i] == 17 ? 6u : 2u;
-        h[10] = h[11] = 0;
-        const uint32_t ipc = (uint32_t)oracle_compute_checksum(h, 20);
-        h[10] = (uint8_t)(ipc >> 8); h[11] = (uint8_t)ipc;
-        seg[field] = seg[field + 1] = 0;
-        const int32_t ph = proto[i] == 1 ? 0 : oracle_compute_pseudo_header_checksum(src, 4, dst, 4, seglen, proto[i]);
-        const uint32_t l4 = 0xffffu ^ (uint32_t)oracle_compute_ones_comp((uint16_t)ph, seg, seglen);
-        seg[field] = (uint8_t)(l4 >> 8); seg[field + 1] = (uint8_t)l4;
+        uint8_t *h = ref + off[i];
+        ipv4_checksum(h, 20);
+        l4_checksum(h + 20, len[i] - 20, proto[i] == 6 ? 16u : proto[i] == 17 ? 6u : 2u, src, dst, 4, proto[i]);
         want_st[i] = RNS_TX_IP_FILLED | RNS_TX_L4_FILLED;
     }
-    uint8_t *d_arena, *d_status;
-    uint64_t *d_off;
-    uint32_t *d_len;
-    uint16_t *d_l4;
-    HIP_OK(hipMalloc((void **)&d_arena, bytes));
-    HIP_OK(hipMalloc((void **)&d_off, n * sizeof *off));
-    HIP_OK(hipMalloc((void **)&d_len, n * sizeof *len));
-    HIP_OK(hipMalloc((void **)&d_status, n));
-    HIP_OK(hipMalloc((void **)&d_l4, n * sizeof *d_l4));
-    HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_off, off, n * sizeof *off, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_len, len, n * sizeof *len, hipMemcpyHostToDevice));
+    uint8_t *d_arena = NULL, *d_status = NULL;
+    uint64_t *d_off = NULL;
+    uint32_t *d_len = NULL;
+    uint16_t *d_l4 = NULL;
+    UP(d_arena, arena, bytes);
+    UP(d_off, off, n * sizeof *off);
+    UP(d_len, len, n * sizeof *len);
+    OUT(d_status, n, 0);
+    OUT(d_l4, n * sizeof *d_l4, 0);
     CHECK(rns_tx_fill_dev(d_arena, bytes, d_off, d_len, n, d_status, st) == RNS_OK, "rns_tx_fill_dev");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(back, d_arena, bytes, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(status, d_status, n, hipMemcpyDeviceToHost));
+    DOWN(back, d_arena, bytes);
+    DOWN(status, d_status, n);
     for (uint32_t i = 0; i < n; ++i)
         CHECK(status[i] == want_st[i], "tx status %u: %02x != %02x", i, status[i], want_st[i]);
     uint64_t diff = 0;
@@ -525,14 +422,13 @@ static int test_tx_rx(hipStream_t st)
             s_ |= RNS_RX_ACCEPT;
         want_st[i] = s_;
     }
-    HIP_OK(hipMemcpy(d_arena, back, bytes, hipMemcpyHostToDevice));
+    UP(d_arena, back, bytes);
     CHECK(rns_rx_verify_dev(d_arena, bytes, d_off, d_len, n, dst, dst6, d_status, d_l4, st) == RNS_OK,
           "rns_rx_verify_dev");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(status, d_status, n, hipMemcpyDeviceToHost));
+    DOWN(status, d_status, n);
     for (uint32_t i = 0; i < n; ++i)
         CHECK(status[i] == want_st[i], "rx status %u (proto %u): %02x != %02x", i, proto[i], status[i], want_st[i]);
-    hipFree(d_arena); hipFree(d_off); hipFree(d_len); hipFree(d_status); hipFree(d_l4);
     free(off); free(len); free(proto); free(status); free(want_st); free(arena); free(ref); free(back);
     return 0;
 }
@@ -560,43 +456,30 @@ static int test_tx_rx_packed(hipStream_t st)
     uint8_t *arena = malloc(bytes), *ref = malloc(bytes), *back = malloc(bytes);
     fill_random(arena, bytes);
     for (uint32_t i = 0; i < n; ++i) {
-        uint8_t *h = arena + off[i];
-        h[0] = 0x45; h[1] = 0; h[2] = (uint8_t)(len16[i] >> 8); h[3] = (uint8_t)len16[i];
-        h[6] = 0x40; h[7] = 0; h[8] = 64; h[9] = proto[i];
-        memcpy(h + 12, src, 4);
-        memcpy(h + 16, dst, 4);
+        ipv4_fields(arena + off[i], len16[i], proto[i], src, dst);
     }
     memcpy(ref, arena, bytes);
     for (uint32_t i = 0; i < n; ++i) {
-        uint8_t *h = ref + off[i], *seg = h + 20;
-        const uint32_t seglen = len16[i] - 20u, field = proto[i] == 6 ? 16u : proto[i] == 17 ? 6u : 2u;
-        h[10] = h[11] = 0;
-        const uint32_t ipc = (uint32_t)oracle_compute_checksum(h, 20);
-        h[10] = (uint8_t)(ipc >> 8); h[11] = (uint8_t)ipc;
-        seg[field] = seg[field + 1] = 0;
-        const int32_t ph = proto[i] == 1 ? 0 : oracle_compute_pseudo_header_checksum(src, 4, dst, 4, seglen, proto[i]);
-        const uint32_t l4 = 0xffffu ^ (uint32_t)oracle_compute_ones_comp((uint16_t)ph, seg, seglen);
-        seg[field] = (uint8_t)(l4 >> 8); seg[field + 1] = (uint8_t)l4;
+        uint8_t *h = ref + off[i];
+        ipv4_checksum(h, 20);
+        l4_checksum(h + 20, len16[i] - 20u, proto[i] == 6 ? 16u : proto[i] == 17 ? 6u : 2u, src, dst, 4, proto[i]);
     }
-    uint8_t *d_arena, *d_status, *d_slots;
-    uint64_t *d_blk;
-    uint16_t *d_len16;
-    HIP_OK(hipMalloc((void **)&d_arena, bytes));
-    HIP_OK(hipMalloc((void **)&d_blk, ((n + 63) / 64) * sizeof *blk));
-    HIP_OK(hipMalloc((void **)&d_len16, n * sizeof *len16));
-    HIP_OK(hipMalloc((void **)&d_status, n));
-    HIP_OK(hipMalloc((void **)&d_slots, (uint64_t)n * 2048));
-    HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_blk, blk, ((n + 63) / 64) * sizeof *blk, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_len16, len16, n * sizeof *len16, hipMemcpyHostToDevice));
+    uint8_t *d_arena = NULL, *d_status = NULL, *d_slots = NULL;
+    uint64_t *d_blk = NULL;
+    uint16_t *d_len16 = NULL;
+    UP(d_arena, arena, bytes);
+    UP(d_blk, blk, ((n + 63) / 64) * sizeof *blk);
+    UP(d_len16, len16, n * sizeof *len16);
+    OUT(d_status, n, 0);
+    OUT(d_slots, (uint64_t)n * 2048, 0);
     const uint32_t hints[2] = {0, 1500};
     for (int h = 0; h < 2; ++h) {
-        HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
+        UP(d_arena, arena, bytes);
         CHECK(rns_tx_fill_packed_dev(d_arena, bytes, d_blk, d_len16, 4, n, d_status, hints[h], st) == RNS_OK,
               "rns_tx_fill_packed_dev");
         HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipMemcpy(back, d_arena, bytes, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(status, d_status, n, hipMemcpyDeviceToHost));
+        DOWN(back, d_arena, bytes);
+        DOWN(status, d_status, n);
         for (uint32_t i = 0; i < n; ++i)
             CHECK(status[i] == (RNS_TX_IP_FILLED | RNS_TX_L4_FILLED), "packed tx (hint %u) status %u: %02x", hints[h],
                   i, status[i]);
@@ -612,7 +495,7 @@ static int test_tx_rx_packed(hipStream_t st)
     CHECK(rns_rx_verify_packed_dev(d_arena, bytes, d_blk, d_len16, 4, n, dst, dst6, d_status, NULL, st) == RNS_OK,
           "rns_rx_verify_packed_dev");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(status, d_status, n, hipMemcpyDeviceToHost));
+    DOWN(status, d_status, n);
     for (uint32_t i = 0; i < n; ++i) {
         const uint8_t want = RNS_RX_IP_OK | RNS_RX_ACCEPT | (proto[i] == 17 ? RNS_RX_L4_UNCHECKED : RNS_RX_L4_OK);
         CHECK(status[i] == want, "packed rx status %u: %02x != %02x", i, status[i], want);
@@ -622,12 +505,11 @@ static int test_tx_rx_packed(hipStream_t st)
     CHECK(rns_rx_verify_strided_dev(d_slots, (uint64_t)n * 2048, 0, 2048, d_len16, n, dst, dst6, d_status, NULL, st) ==
               RNS_OK, "rns_rx_verify_strided_dev");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(status, d_status, n, hipMemcpyDeviceToHost));
+    DOWN(status, d_status, n);
     for (uint32_t i = 0; i < n; ++i) {
         const uint8_t want = RNS_RX_IP_OK | RNS_RX_ACCEPT | (proto[i] == 17 ? RNS_RX_L4_UNCHECKED : RNS_RX_L4_OK);
         CHECK(status[i] == want, "strided rx status %u: %02x != %02x", i, status[i], want);
     }
-    hipFree(d_arena); hipFree(d_blk); hipFree(d_len16); hipFree(d_status); hipFree(d_slots);
     free(len16); free(off); free(blk); free(proto); free(status); free(arena); free(ref); free(back);
     return 0;
 }
@@ -675,45 +557,33 @@ static int test_tx_chain(hipStream_t st)
     uint8_t *arena = malloc(bytes), *ref = malloc(bytes), *back = malloc(bytes);
     fill_random(arena, bytes);
     for (uint32_t i = 0; i < n; ++i) {
-        uint8_t *h = arena + off[first[i]];
-        const uint32_t tot = hl[i] + pl[i];
-        h[0] = 0x45; h[1] = 0; h[2] = (uint8_t)(tot >> 8); h[3] = (uint8_t)tot;
-        h[6] = 0x40; h[7] = 0; h[8] = 64; h[9] = proto[i];
-        memcpy(h + 12, src, 4);
-        memcpy(h + 16, dst, 4);                      /* both checksum fields keep their garbage */
+        ipv4_fields(arena + off[first[i]], hl[i] + pl[i], proto[i], src, dst);  /* both checksum fields keep their garbage */
     }
     memcpy(ref, arena, bytes);
     for (uint32_t i = 0; i < n; ++i) {
         uint8_t *h = ref + off[first[i]], *seg = h + 20;
         const uint32_t field = proto[i] == 6 ? 16u : proto[i] == 17 ? 6u : 2u;
-        h[10] = h[11] = 0;
-        const uint32_t ipc = (uint32_t)oracle_compute_checksum(h, 20);
-        h[10] = (uint8_t)(ipc >> 8); h[11] = (uint8_t)ipc;
-        seg[field] = seg[field + 1] = 0;
+        ipv4_checksum(h, 20);
+        put16(seg + field, 0);
         int32_t acc = proto[i] == 1 ? 0 : oracle_compute_pseudo_header_checksum(src, 4, dst, 4, hl[i] - 20u + pl[i], proto[i]);
         acc = oracle_compute_ones_comp((uint16_t)acc, seg, hl[i] - 20u);
         for (uint32_t f = first[i] + 1; f < first[i + 1]; ++f)
             acc = oracle_compute_ones_comp((uint16_t)acc, ref + off[f], len[f]);
-        const uint32_t l4 = 0xffffu ^ (uint32_t)acc;
-        seg[field] = (uint8_t)(l4 >> 8); seg[field + 1] = (uint8_t)l4;
+        put16(seg + field, 0xffffu ^ (uint32_t)acc);
     }
-    uint8_t *d_arena, *d_status;
-    uint64_t *d_off;
-    uint32_t *d_len, *d_first;
-    HIP_OK(hipMalloc((void **)&d_arena, bytes));
-    HIP_OK(hipMalloc((void **)&d_off, nf * sizeof *off));
-    HIP_OK(hipMalloc((void **)&d_len, nf * sizeof *len));
-    HIP_OK(hipMalloc((void **)&d_first, (n + 1) * sizeof *first));
-    HIP_OK(hipMalloc((void **)&d_status, n));
-    HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_off, off, nf * sizeof *off, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_len, len, nf * sizeof *len, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_first, first, (n + 1) * sizeof *first, hipMemcpyHostToDevice));
+    uint8_t *d_arena = NULL, *d_status = NULL;
+    uint64_t *d_off = NULL;
+    uint32_t *d_len = NULL, *d_first = NULL;
+    UP(d_arena, arena, bytes);
+    UP(d_off, off, nf * sizeof *off);
+    UP(d_len, len, nf * sizeof *len);
+    UP(d_first, first, (n + 1) * sizeof *first);
+    OUT(d_status, n, 0);
     CHECK(rns_tx_fill_chain_dev(d_arena, bytes, d_off, d_len, nf, d_first, n, d_status, st) == RNS_OK,
           "rns_tx_fill_chain_dev");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(back, d_arena, bytes, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(status, d_status, n, hipMemcpyDeviceToHost));
+    DOWN(back, d_arena, bytes);
+    DOWN(status, d_status, n);
     for (uint32_t i = 0; i < n; ++i)
         CHECK(status[i] == (RNS_TX_IP_FILLED | RNS_TX_L4_FILLED), "chain tx status %u: %02x", i, status[i]);
     uint64_t diff = 0;
@@ -722,7 +592,6 @@ static int test_tx_chain(hipStream_t st)
     CHECK(diff == 0, "chain tx: %llu arena bytes differ from the oracle's", (unsigned long long)diff);
     CHECK(rns_tx_fill_chain_dev(d_arena, bytes, d_off, d_len, nf, NULL, n, d_status, st) == RNS_E_INVALID,
           "NULL first");
-    hipFree(d_arena); hipFree(d_off); hipFree(d_len); hipFree(d_first); hipFree(d_status);
     free(first); free(hl); free(pl); free(proto); free(status); free(off); free(len); free(arena); free(ref);
     free(back);
     return 0;
@@ -747,12 +616,9 @@ int main(void)
     uint8_t *arena = NULL;
     if (rns_host_alloc(bytes, (void **)&arena) != RNS_OK) {  /* pinned, as the header recommends */
         fprintf(stderr, "rns_host_alloc failed\n");
-        return 2;
+        abi_no_device();
     }
-    for (uint64_t b = 0; b < bytes; b += 8) {
-        const uint64_t w = next_u64();
-        memcpy(arena + b, &w, bytes - b < 8 ? bytes - b : 8);
-    }
+    fill_random(arena, bytes);
     for (uint32_t i = 0; i < n; ++i)
         want[i] = (uint16_t)(0xffffu ^ (uint32_t)oracle_compute_ones_comp(seed[i], arena + off[i], len[i]));
 
@@ -768,31 +634,25 @@ int main(void)
     CHECK(rns_host_ctx_destroy(ctx) == RNS_OK, "rns_host_ctx_destroy");
 
     /* 2. device-resident batch: the caller owns the HBM buffers and the stream */
-    uint8_t *d_arena;
-    uint64_t *d_off;
-    uint32_t *d_len, *d_bad;
-    uint16_t *d_seed, *d_out;
+    uint8_t *d_arena = NULL;
+    uint64_t *d_off = NULL;
+    uint32_t *d_len = NULL, *d_bad = NULL;
+    uint16_t *d_seed = NULL, *d_out = NULL;
     hipStream_t st;
-    HIP_OK(hipMalloc((void **)&d_arena, bytes));
-    HIP_OK(hipMalloc((void **)&d_off, n * sizeof *off));
-    HIP_OK(hipMalloc((void **)&d_len, n * sizeof *len));
-    HIP_OK(hipMalloc((void **)&d_seed, n * sizeof *seed));
-    HIP_OK(hipMalloc((void **)&d_out, n * sizeof *got));
-    HIP_OK(hipMalloc((void **)&d_bad, sizeof *d_bad));
-    HIP_OK(hipStreamCreate(&st));
-    HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_off, off, n * sizeof *off, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_len, len, n * sizeof *len, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_seed, seed, n * sizeof *seed, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_bad, 0, sizeof *d_bad));
+    HIP_OK(abi_stream(&st));
+    UP(d_arena, arena, bytes);
+    UP(d_off, off, n * sizeof *off);
+    UP(d_len, len, n * sizeof *len);
+    UP(d_seed, seed, n * sizeof *seed);
+    OUT(d_bad, sizeof *d_bad, 0);
     const uint32_t hints[3] = {0u, 64u, 1000u};     /* auto, tiny-packet and mixed shapes */
     for (int h = 0; h < 3; ++h) {
-        HIP_OK(hipMemset(d_out, 0, n * sizeof *got));
+        OUT(d_out, n * sizeof *got, 0);
         CHECK(rns_csum_batch_dev(d_arena, bytes, d_off, d_len, d_seed, d_out, n, RNS_FLAG_COMPLEMENT, hints[h], d_bad,
                                  st) == RNS_OK,
               "rns_csum_batch_dev hint %u", hints[h]);
         HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipMemcpy(got, d_out, n * sizeof *got, hipMemcpyDeviceToHost));
+        DOWN(got, d_out, n * sizeof *got);
         for (uint32_t i = 0; i < n; ++i)
             CHECK(got[i] == want[i], "device batch (hint %u) packet %u: %04x != %04x", hints[h], i, got[i], want[i]);
     }
@@ -801,15 +661,14 @@ int main(void)
         uint32_t *off32 = malloc(n * sizeof *off32), *d_off32 = NULL;
         for (uint32_t i = 0; i < n; ++i)
             off32[i] = (uint32_t)off[i];
-        HIP_OK(hipMalloc((void **)&d_off32, n * sizeof *off32));
-        HIP_OK(hipMemcpy(d_off32, off32, n * sizeof *off32, hipMemcpyHostToDevice));
+        UP(d_off32, off32, n * sizeof *off32);
         for (int h = 0; h < 3; ++h) {
-            HIP_OK(hipMemset(d_out, 0, n * sizeof *got));
+            OUT(d_out, n * sizeof *got, 0);
             CHECK(rns_csum_batch_dev_off32(d_arena, bytes, d_off32, d_len, d_seed, d_out, n, RNS_FLAG_COMPLEMENT,
                                            hints[h], d_bad, st) == RNS_OK,
                   "rns_csum_batch_dev_off32 hint %u", hints[h]);
             HIP_OK(hipStreamSynchronize(st));
-            HIP_OK(hipMemcpy(got, d_out, n * sizeof *got, hipMemcpyDeviceToHost));
+            DOWN(got, d_out, n * sizeof *got);
             for (uint32_t i = 0; i < n; ++i)
                 CHECK(got[i] == want[i], "compact batch (hint %u) packet %u: %04x != %04x", hints[h], i, got[i],
                       want[i]);
@@ -817,11 +676,10 @@ int main(void)
         CHECK(rns_csum_batch_dev_off32(d_arena, bytes, NULL, d_len, d_seed, d_out, n, 0, 0, NULL, st) ==
                   RNS_E_INVALID,
               "NULL compact offsets");
-        hipFree(d_off32);
         free(off32);
     }
     uint32_t bad = 1;
-    HIP_OK(hipMemcpy(&bad, d_bad, sizeof bad, hipMemcpyDeviceToHost));
+    DOWN(&bad, d_bad, sizeof bad);
     CHECK(bad == 0, "d_bad = %u", bad);
 
     /* 2b. the packed entry bench.py times, the fragment-chain entry, transmit finalize and
@@ -836,23 +694,11 @@ int main(void)
     CHECK(rns_csum_batch_dev(d_arena, bytes, d_off, d_len, d_seed, d_out, 0, 0, 0, NULL, st) == RNS_OK, "n = 0");
     CHECK(rns_compute_ones_comp(0, arena, 0) < 0, "empty slice reports the reference's panic");
 
-    hipFree(d_arena);
-    hipFree(d_off);
-    hipFree(d_len);
-    hipFree(d_seed);
-    hipFree(d_out);
-    hipFree(d_bad);
-    hipStreamDestroy(st);
     rns_host_free(arena);
     free(off);
     free(len);
     free(seed);
     free(want);
     free(got);
-    if (failures) {
-        fprintf(stderr, "%d failures\n", failures);
-        return 1;
-    }
-    printf("all checks passed (%u packets)\n", n);
-    return 0;
+    return abi_finish("%u packets", n);
 }

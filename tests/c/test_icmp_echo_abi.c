@@ -11,42 +11,8 @@
  *
  * Prints "all checks passed" and exits 0 on success; exits 2 when no device memory can be had.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "rns_checksum.h"
-
-static uint64_t rng_state = 0xEC40F00Dull;
-static uint64_t next_u64(void)
-{
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-static int failures = 0;
-#define CHECK(cond, ...)                                                                           \
-    do {                                                                                           \
-        if (!(cond)) {                                                                             \
-            if (failures++ < 10) {                                                                 \
-                fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__);                               \
-                fprintf(stderr, __VA_ARGS__);                                                      \
-                fprintf(stderr, "\n");                                                             \
-            }                                                                                      \
-        }                                                                                          \
-    } while (0)
-#define HIP_OK(x)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_));              \
-            return 2;                                                                              \
-        }                                                                                          \
-    } while (0)
+#define ABI_TEST_SEED 0xEC40F00Dull
+#include "abi_test.h"
 
 enum { N = 200, LOG2 = 9, BUF = 1 << LOG2, MAXPAY = 1400, MAXT = 60 + 4 + MAXPAY, MAXFR = 1 + (MAXT + BUF - 1) / BUF,
        NRX = N * MAXFR, NTX = N * MAXFR, NBLK = (N + 63) / 64, KINDS = 7, ID_BASE = 0xFFF0, ID_ADD = 5 };
@@ -67,21 +33,17 @@ static uint32_t be_sum(uint32_t s, const uint8_t *b, uint32_t n)
     return s;
 }
 
-static void put16(uint8_t *p, uint32_t v) { p[0] = (uint8_t)(v >> 8); p[1] = (uint8_t)v; }
-
 /* An ICMP datagram of `pay` random payload bytes: IPv4 with IHL ihl (v6 == 0) or IPv6.  Its length. */
 static uint32_t make_icmp(uint8_t *d, int v6, uint32_t ihl, uint8_t type, uint32_t pay, int corrupt)
 {
     const uint32_t h = v6 ? 40 : 4 * ihl, T = h + 4 + pay;
     memset(d, 0, h + 4);
-    for (uint32_t b = 0; b < pay; ++b)
-        d[h + 4 + b] = (uint8_t)next_u64();
+    fill_random_bytes(d + h + 4, pay);
     d[h] = type;
     d[h + 1] = (uint8_t)next_u64();  /* the code is not echoed */
     uint32_t seed = 0;
     if (v6) {
-        d[0] = 0x60; put16(d + 4, 4 + pay); d[6] = 58; d[7] = 64;
-        memcpy(d + 8, R6, 16); memcpy(d + 24, L6, 16);
+        ipv6_header(d, 4 + pay, 58, R6, L6);
         seed = be_sum(be_sum(4 + pay + 58, R6, 16), L6, 16);
     } else {
         d[0] = (uint8_t)(0x40 | ihl); put16(d + 2, T); d[8] = 64; d[9] = 1;
@@ -103,8 +65,7 @@ static uint32_t make_reply(uint8_t *r, const uint8_t *d, uint32_t h, uint32_t T,
     memcpy(r + hl, d + h + 4, pay);
     uint32_t seed = 0;
     if (v6) {
-        r[0] = 0x60; put16(r + 4, 4 + pay); r[6] = 58; r[7] = 64;
-        memcpy(r + 8, L6, 16); memcpy(r + 24, R6, 16);
+        ipv6_header(r, 4 + pay, 58, L6, R6);
         r[40] = 129;
         seed = be_sum(be_sum(4 + pay + 58, R6, 16), L6, 16);
     } else {
@@ -131,8 +92,7 @@ int main(void)
         freel[j] = freel[r2];
         freel[r2] = t2;
     }
-    for (size_t b = 0; b < sizeof rx; ++b)
-        rx[b] = (uint8_t)next_u64();
+    fill_random_bytes(rx, sizeof rx);
     memset(tx, 0xA5, sizeof tx);
     uint32_t nf = 0, nreq = 0;
     for (uint32_t i = 0; i < N; ++i) {
@@ -180,32 +140,21 @@ int main(void)
     uint32_t *d_idx = NULL, *d_blk = NULL, *d_free = NULL, *d_tbf = NULL, *d_src = NULL, *d_count = NULL, *d_add = NULL;
     void *d_work = NULL;
     hipStream_t st;
-    if (hipMalloc((void **)&d_rx, sizeof rx) != hipSuccess) {
-        fprintf(stderr, "hipMalloc failed: no usable device\n");
-        return 2;
-    }
-    HIP_OK(hipMalloc((void **)&d_tx, sizeof tx));
-    HIP_OK(hipMalloc((void **)&d_status, N));
-    HIP_OK(hipMalloc((void **)&d_echo, N));
-    HIP_OK(hipMalloc((void **)&d_hl, N));
-    HIP_OK(hipMalloc((void **)&d_len, sizeof len16));
-    HIP_OK(hipMalloc((void **)&d_pl, sizeof pl16));
-    HIP_OK(hipMalloc((void **)&d_idx, sizeof idx));
-    HIP_OK(hipMalloc((void **)&d_blk, sizeof blk_first));
-    HIP_OK(hipMalloc((void **)&d_free, sizeof freel));
-    HIP_OK(hipMalloc((void **)&d_tbf, sizeof tbf));
-    HIP_OK(hipMalloc((void **)&d_src, sizeof src));
-    HIP_OK(hipMalloc((void **)&d_count, sizeof count));
-    HIP_OK(hipMalloc((void **)&d_add, 4));
-    HIP_OK(hipMalloc(&d_work, need));
-    HIP_OK(hipStreamCreate(&st));
     const uint32_t add = ID_ADD;
-    HIP_OK(hipMemcpy(d_rx, rx, sizeof rx, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_len, len16, sizeof len16, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_idx, idx, sizeof idx, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_blk, blk_first, sizeof blk_first, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_free, freel, sizeof freel, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_add, &add, 4, hipMemcpyHostToDevice));
+    UP(d_rx, rx, sizeof rx);
+    UP(d_len, len16, sizeof len16);
+    UP(d_idx, idx, sizeof idx);
+    UP(d_blk, blk_first, sizeof blk_first);
+    UP(d_free, freel, sizeof freel);
+    UP(d_add, &add, 4);
+    OUT(d_status, N, 0);
+    OUT(d_echo, N, 0);
+    OUT(d_hl, N, 0);
+    OUT(d_pl, sizeof pl16, 0);
+    OUT(d_tbf, sizeof tbf, 0);
+    OUT(d_src, sizeof src, 0);
+    OUT(d_work, need, 0);
+    HIP_OK(abi_stream(&st));
     for (int round = 0; round < 2; ++round) {
         /* round 1: a free list that ends inside the 21st reply: 20 replies, the other requests left to the host */
         uint32_t n_free = NTX, want_rep = nreq;
@@ -219,20 +168,20 @@ int main(void)
                 }
             n_free -= 1;
         }
-        HIP_OK(hipMemcpy(d_tx, tx, sizeof tx, hipMemcpyHostToDevice));
-        HIP_OK(hipMemset(d_count, 0x55, sizeof count));
+        UP(d_tx, tx, sizeof tx);
+        OUT(d_count, sizeof count, 0x55);
         CHECK(rns_rx_icmp_echo_pool_dev(d_rx, sizeof rx, LOG2, d_idx, nf, d_blk, d_len, N, L4, L6, d_tx, sizeof tx, d_free, n_free,
                                         N, ID_BASE, d_add, d_tbf, d_hl, d_pl, d_src, d_count, d_status, NULL, d_echo, d_work,
                                         need, st) == RNS_OK, "rns_rx_icmp_echo_pool_dev");
         HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipMemcpy(count, d_count, sizeof count, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(status, d_status, N, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(echo, d_echo, N, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(hl8, d_hl, N, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(pl16, d_pl, sizeof pl16, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(tbf, d_tbf, sizeof tbf, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(src, d_src, sizeof src, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(back, d_tx, sizeof tx, hipMemcpyDeviceToHost));
+        DOWN(count, d_count, sizeof count);
+        DOWN(status, d_status, N);
+        DOWN(echo, d_echo, N);
+        DOWN(hl8, d_hl, N);
+        DOWN(pl16, d_pl, sizeof pl16);
+        DOWN(tbf, d_tbf, sizeof tbf);
+        DOWN(src, d_src, sizeof src);
+        DOWN(back, d_tx, sizeof tx);
         CHECK(count[0] == want_rep, "round %d: %u replies, %u expected", round, count[0], want_rep);
         uint32_t r = 0, at = 0, v4 = 0;
         for (uint32_t i = 0; i < N; ++i) {
@@ -265,13 +214,5 @@ int main(void)
             for (uint32_t b = 0; b < BUF; b += 61)
                 CHECK(back[((size_t)freel[f] << LOG2) + b] == 0xA5, "round %d: free buffer %u written", round, f);
     }
-    hipStreamDestroy(st);
-    hipFree(d_rx); hipFree(d_tx); hipFree(d_status); hipFree(d_echo); hipFree(d_hl); hipFree(d_len); hipFree(d_pl); hipFree(d_idx);
-    hipFree(d_blk); hipFree(d_free); hipFree(d_tbf); hipFree(d_src); hipFree(d_count); hipFree(d_add); hipFree(d_work);
-    if (failures) {
-        fprintf(stderr, "%d checks failed\n", failures);
-        return 1;
-    }
-    printf("all checks passed\n");
-    return 0;
+    return abi_finish("%d datagrams, %u echo requests", N, nreq);
 }

@@ -11,55 +11,11 @@
  *
  * Prints "all checks passed" and exits 0 on success; exits 2 when no device memory can be had.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "rns_checksum.h"
-
-int32_t oracle_compute_ones_comp(uint16_t in_checksum, const uint8_t *slice, size_t len);
-int32_t oracle_compute_checksum(const uint8_t *slice, size_t len);
-int32_t oracle_compute_pseudo_header_checksum(const uint8_t *src, size_t src_len, const uint8_t *dst, size_t dst_len,
-                                              uint64_t length, uint8_t protocol);
-
-static uint64_t rng_state = 0xF10A5EEDull;
-static uint64_t next_u64(void)
-{
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-static int failures = 0;
-#define CHECK(cond, ...)                                                                           \
-    do {                                                                                           \
-        if (!(cond)) {                                                                             \
-            if (failures++ < 10) {                                                                 \
-                fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__);                               \
-                fprintf(stderr, __VA_ARGS__);                                                      \
-                fprintf(stderr, "\n");                                                             \
-            }                                                                                      \
-        }                                                                                          \
-    } while (0)
-#define HIP_OK(x)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_));              \
-            return 2;                                                                              \
-        }                                                                                          \
-    } while (0)
+#define ABI_TEST_SEED 0xF10A5EEDull
+#include "abi_test.h"
 
 enum { N = 300, NFLOW = 4, CAP = 4, STRIDE = 64, ACKCAP = 64, FILL = 0xEE };
 
-static int seq_gt(uint32_t a, uint32_t b)
-{
-    uint32_t d = a - b;
-    return d < 0x80000000u && d != 0;
-}
 static int seq_le(uint32_t a, uint32_t b) { return !seq_gt(a, b); }
 
 static rns_rx_tcp_meta meta[N];
@@ -158,9 +114,6 @@ static void update_ref(uint32_t f)
     ref_flow[f] = s;
     ref_res[f] = r;
 }
-
-static void put16(uint8_t *p, uint32_t v) { p[0] = (uint8_t)(v >> 8), p[1] = (uint8_t)v; }
-static void put32(uint8_t *p, uint32_t v) { put16(p, v >> 16), put16(p + 2, v & 0xffffu); }
 
 /* tcp_output (tcp.rs:938-976) and ip_output (ip.rs:140-177) for a pure ACK of flow f; returns the head length */
 static uint32_t ack_ref(uint32_t f, uint32_t ack_num, uint32_t window, uint32_t id, uint8_t *h)
@@ -279,56 +232,40 @@ int main(void)
     CHECK(rns_tx_ack_build_dev(fake, fake, N, fake, NFLOW, fake, STRIDE, fake, 0, fake, need, fake, ACKCAP, fake, fake, NULL,
                                NULL) == RNS_E_INVALID, "NULL d_n_acks");
 
-    rns_rx_tcp_meta *d_meta;
-    rns_tcp_flow *d_fin, *d_fout;
-    uint32_t *d_pin, *d_pout, *d_src, *d_n;
-    rns_rx_tcp_seg *d_seg;
-    rns_tcp_flow_res *d_res;
-    uint8_t *d_work, *d_tmpl, *d_hl, *d_out, *d_len;
-    if (hipMalloc((void **)&d_meta, sizeof meta) != hipSuccess) {
-        fprintf(stderr, "hipMalloc failed: no usable device\n");
-        return 2;
-    }
-    HIP_OK(hipMalloc((void **)&d_fin, sizeof flow_in));
-    HIP_OK(hipMalloc((void **)&d_fout, sizeof flow_out));
-    HIP_OK(hipMalloc((void **)&d_pin, sizeof pend_in));
-    HIP_OK(hipMalloc((void **)&d_pout, sizeof pend_out));
-    HIP_OK(hipMalloc((void **)&d_seg, sizeof seg));
-    HIP_OK(hipMalloc((void **)&d_res, sizeof res));
-    HIP_OK(hipMalloc((void **)&d_work, need));
-    HIP_OK(hipMalloc((void **)&d_tmpl, sizeof tmpl));
-    HIP_OK(hipMalloc((void **)&d_hl, sizeof head_len8));
-    HIP_OK(hipMalloc((void **)&d_out, sizeof out));
-    HIP_OK(hipMalloc((void **)&d_src, sizeof ack_src));
-    HIP_OK(hipMalloc((void **)&d_len, sizeof ack_len8));
-    HIP_OK(hipMalloc((void **)&d_n, sizeof n_acks));
-    HIP_OK(hipMemcpy(d_meta, meta, sizeof meta, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_fin, flow_in, sizeof flow_in, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_pin, pend_in, sizeof pend_in, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_tmpl, tmpl, sizeof tmpl, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_hl, head_len8, sizeof head_len8, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_fout, FILL, sizeof flow_out));
-    HIP_OK(hipMemset(d_pout, FILL, sizeof pend_out));
-    HIP_OK(hipMemset(d_seg, FILL, sizeof seg));
-    HIP_OK(hipMemset(d_res, FILL, sizeof res));
-    HIP_OK(hipMemset(d_out, FILL, sizeof out));
-    HIP_OK(hipMemset(d_src, FILL, sizeof ack_src));
-    HIP_OK(hipMemset(d_len, FILL, sizeof ack_len8));
-    HIP_OK(hipMemset(d_n, FILL, sizeof n_acks));
+    rns_rx_tcp_meta *d_meta = NULL;
+    rns_tcp_flow *d_fin = NULL, *d_fout = NULL;
+    uint32_t *d_pin = NULL, *d_pout = NULL, *d_src = NULL, *d_n = NULL;
+    rns_rx_tcp_seg *d_seg = NULL;
+    rns_tcp_flow_res *d_res = NULL;
+    uint8_t *d_work = NULL, *d_tmpl = NULL, *d_hl = NULL, *d_out = NULL, *d_len = NULL;
+    UP(d_meta, meta, sizeof meta);
+    UP(d_fin, flow_in, sizeof flow_in);
+    UP(d_pin, pend_in, sizeof pend_in);
+    UP(d_tmpl, tmpl, sizeof tmpl);
+    UP(d_hl, head_len8, sizeof head_len8);
+    OUT(d_work, need, FILL);
+    OUT(d_fout, sizeof flow_out, FILL);
+    OUT(d_pout, sizeof pend_out, FILL);
+    OUT(d_seg, sizeof seg, FILL);
+    OUT(d_res, sizeof res, FILL);
+    OUT(d_out, sizeof out, FILL);
+    OUT(d_src, sizeof ack_src, FILL);
+    OUT(d_len, sizeof ack_len8, FILL);
+    OUT(d_n, sizeof n_acks, FILL);
 
     CHECK(rns_rx_tcp_flow_update_dev(d_meta, N, NFLOW, d_fin, d_pin, CAP, d_fout, d_pout, d_seg, d_res, d_work, need, NULL) ==
               RNS_OK, "rns_rx_tcp_flow_update_dev");
     CHECK(rns_tx_ack_build_dev(d_meta, d_seg, N, d_fout, NFLOW, d_tmpl, STRIDE, d_hl, 0xFFF0, d_work, need, d_out, ACKCAP,
                                d_src, d_len, d_n, NULL) == RNS_OK, "rns_tx_ack_build_dev");
     HIP_OK(hipDeviceSynchronize());
-    HIP_OK(hipMemcpy(flow_out, d_fout, sizeof flow_out, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(pend_out, d_pout, sizeof pend_out, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(seg, d_seg, sizeof seg, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(res, d_res, sizeof res, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(out, d_out, sizeof out, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(ack_src, d_src, sizeof ack_src, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(ack_len8, d_len, sizeof ack_len8, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(n_acks, d_n, sizeof n_acks, hipMemcpyDeviceToHost));
+    DOWN(flow_out, d_fout, sizeof flow_out);
+    DOWN(pend_out, d_pout, sizeof pend_out);
+    DOWN(seg, d_seg, sizeof seg);
+    DOWN(res, d_res, sizeof res);
+    DOWN(out, d_out, sizeof out);
+    DOWN(ack_src, d_src, sizeof ack_src);
+    DOWN(ack_len8, d_len, sizeof ack_len8);
+    DOWN(n_acks, d_n, sizeof n_acks);
 
     for (uint32_t f = 0; f < NFLOW; ++f) {
         CHECK(memcmp(&flow_out[f], &ref_flow[f], sizeof flow_out[f]) == 0, "flow %u: rcv_nxt %u != %u, n_pend %u != %u", f,
@@ -359,12 +296,5 @@ int main(void)
     for (uint32_t b = 64 * k; b < sizeof out; ++b)
         CHECK(out[b] == FILL, "byte %u past the last ACK written", b);
 
-    hipFree(d_meta), hipFree(d_fin), hipFree(d_fout), hipFree(d_pin), hipFree(d_pout), hipFree(d_seg), hipFree(d_res);
-    hipFree(d_work), hipFree(d_tmpl), hipFree(d_hl), hipFree(d_out), hipFree(d_src), hipFree(d_len), hipFree(d_n);
-    if (failures) {
-        fprintf(stderr, "%d checks failed\n", failures);
-        return 1;
-    }
-    printf("all checks passed\n");
-    return 0;
+    return abi_finish("%d records of %d flows, %u ACKs", N, NFLOW, k);
 }

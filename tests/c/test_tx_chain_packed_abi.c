@@ -9,45 +9,8 @@
  *
  * Prints "all checks passed" and exits 0 on success; exits 2 when no device memory can be had.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "rns_checksum.h"
-
-void oracle_tx_chain_fill(uint8_t *arena, uint64_t arena_bytes, const uint64_t *frag_off, const uint32_t *frag_len,
-                          const uint32_t *first, uint32_t n_frags, size_t n, uint8_t *status);
-
-static uint64_t rng_state = 0xC0A7C4A1ull;
-static uint64_t next_u64(void)
-{
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-static int failures = 0;
-#define CHECK(cond, ...)                                                                           \
-    do {                                                                                           \
-        if (!(cond)) {                                                                             \
-            if (failures++ < 10) {                                                                 \
-                fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__);                               \
-                fprintf(stderr, __VA_ARGS__);                                                      \
-                fprintf(stderr, "\n");                                                             \
-            }                                                                                      \
-        }                                                                                          \
-    } while (0)
-#define HIP_OK(x)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_));              \
-            return 2;                                                                              \
-        }                                                                                          \
-    } while (0)
+#define ABI_TEST_SEED 0xC0A7C4A1ull
+#include "abi_test.h"
 
 int main(void)
 {
@@ -75,17 +38,9 @@ int main(void)
     CHECK(hblk[0] == 3 && pblk[0] == pay0 && hoff[64] == hblk[1] && poff[64] == pblk[1], "block offsets");
     const uint64_t bytes = pend + 16;
     uint8_t *arena = malloc(bytes), *ref = malloc(bytes), *back = malloc(bytes);
-    for (uint64_t b = 0; b < bytes; b += 8) {
-        const uint64_t w = next_u64();
-        memcpy(arena + b, &w, bytes - b < 8 ? bytes - b : 8);
-    }
+    fill_random(arena, bytes);
     for (uint32_t i = 0; i < N; ++i) {
-        uint8_t *h = arena + hoff[i];
-        const uint32_t tot = (uint32_t)hl8[i] + pl16[i];
-        h[0] = 0x45; h[1] = 0; h[2] = (uint8_t)(tot >> 8); h[3] = (uint8_t)tot;
-        h[6] = 0x40; h[7] = 0; h[8] = 64; h[9] = proto[i];
-        memcpy(h + 12, src, 4);
-        memcpy(h + 16, dst, 4);                      /* both checksum fields keep their garbage */
+        ipv4_fields(arena + hoff[i], (uint32_t)hl8[i] + pl16[i], proto[i], src, dst);  /* both checksum fields keep their garbage */
     }
     /* the oracle over the equivalent CSR chains */
     static uint64_t off[2 * N];
@@ -108,27 +63,18 @@ int main(void)
     uint16_t *d_pl16 = NULL;
     uint64_t *d_hblk = NULL, *d_pblk = NULL;
     hipStream_t st;
-    if (hipMalloc((void **)&d_arena, bytes) != hipSuccess) {
-        fprintf(stderr, "hipMalloc failed: no usable device\n");
-        return 2;
-    }
-    HIP_OK(hipMalloc((void **)&d_status, N));
-    HIP_OK(hipMalloc((void **)&d_hl8, N));
-    HIP_OK(hipMalloc((void **)&d_pl16, N * sizeof *pl16));
-    HIP_OK(hipMalloc((void **)&d_hblk, NB * sizeof *hblk));
-    HIP_OK(hipMalloc((void **)&d_pblk, NB * sizeof *pblk));
-    HIP_OK(hipStreamCreate(&st));
-    HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_hl8, hl8, N, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_pl16, pl16, N * sizeof *pl16, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_hblk, hblk, NB * sizeof *hblk, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_pblk, pblk, NB * sizeof *pblk, hipMemcpyHostToDevice));
-    HIP_OK(hipMemset(d_status, 0x55, N));
+    UP(d_arena, arena, bytes);
+    UP(d_hl8, hl8, N);
+    UP(d_pl16, pl16, N * sizeof *pl16);
+    UP(d_hblk, hblk, NB * sizeof *hblk);
+    UP(d_pblk, pblk, NB * sizeof *pblk);
+    OUT(d_status, N, 0x55);
+    HIP_OK(abi_stream(&st));
     CHECK(rns_tx_fill_chain_packed_dev(d_arena, bytes, d_hblk, d_hl8, d_pblk, d_pl16, 4, N, d_status, st) == RNS_OK,
           "rns_tx_fill_chain_packed_dev");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(back, d_arena, bytes, hipMemcpyDeviceToHost));
-    HIP_OK(hipMemcpy(status, d_status, N, hipMemcpyDeviceToHost));
+    DOWN(back, d_arena, bytes);
+    DOWN(status, d_status, N);
     for (uint32_t i = 0; i < N; ++i) {
         CHECK(ref_status[i] == (RNS_TX_IP_FILLED | RNS_TX_L4_FILLED), "oracle status %u: %02x", i, ref_status[i]);
         CHECK(status[i] == ref_status[i], "status %u: %02x != %02x", i, status[i], ref_status[i]);
@@ -138,11 +84,11 @@ int main(void)
         diff += back[b] != ref[b];
     CHECK(diff == 0, "%llu arena bytes differ from the oracle's", (unsigned long long)diff);
     /* without a status array, and the argument checks with a device present */
-    HIP_OK(hipMemcpy(d_arena, arena, bytes, hipMemcpyHostToDevice));
+    UP(d_arena, arena, bytes);
     CHECK(rns_tx_fill_chain_packed_dev(d_arena, bytes, d_hblk, d_hl8, d_pblk, d_pl16, 4, N, NULL, st) == RNS_OK,
           "no status array");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(back, d_arena, bytes, hipMemcpyDeviceToHost));
+    DOWN(back, d_arena, bytes);
     CHECK(memcmp(back, ref, bytes) == 0, "without a status array: arena differs");
     CHECK(rns_tx_fill_chain_packed_dev(d_arena, bytes, d_hblk, NULL, d_pblk, d_pl16, 4, N, d_status, st) == RNS_E_INVALID,
           "NULL head lengths");
@@ -150,13 +96,6 @@ int main(void)
           "align 3");
     CHECK(rns_tx_fill_chain_packed_dev(d_arena, bytes, d_hblk, d_hl8, d_pblk, d_pl16, 13, N, d_status, st) == RNS_E_INVALID,
           "align 13");
-    hipStreamDestroy(st);
-    hipFree(d_arena); hipFree(d_status); hipFree(d_hl8); hipFree(d_pl16); hipFree(d_hblk); hipFree(d_pblk);
     free(arena); free(ref); free(back);
-    if (failures) {
-        fprintf(stderr, "%d checks failed\n", failures);
-        return 1;
-    }
-    printf("all checks passed\n");
-    return 0;
+    return abi_finish("%d chains", N);
 }

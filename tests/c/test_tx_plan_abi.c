@@ -12,74 +12,11 @@
  *
  * Prints "all checks passed" and exits 0 on success; exits 2 when no device memory can be had.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "rns_checksum.h"
-
-void oracle_tx_chain_fill(uint8_t *arena, uint64_t arena_bytes, const uint64_t *frag_off, const uint32_t *frag_len,
-                          const uint32_t *first, uint32_t n_frags, size_t n, uint8_t *status);
-
-static uint64_t rng_state = 0x91A45EEDull;
-static uint64_t next_u64(void)
-{
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-static int failures = 0;
-#define CHECK(cond, ...)                                                                           \
-    do {                                                                                           \
-        if (!(cond)) {                                                                             \
-            if (failures++ < 10) {                                                                 \
-                fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__);                               \
-                fprintf(stderr, __VA_ARGS__);                                                      \
-                fprintf(stderr, "\n");                                                             \
-            }                                                                                      \
-        }                                                                                          \
-    } while (0)
-#define HIP_OK(x)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_));              \
-            return 2;                                                                              \
-        }                                                                                          \
-    } while (0)
+#define ABI_TEST_SEED 0x91A45EEDull
+#include "abi_test.h"
 
 enum { NFL = 40, E = 2 * NFL, STRIDE = 64, SEGCAP = 1000, NBLK = (SEGCAP + 63) / 64, SQ = 20000, DATA = NFL * (SQ + 1) + 64,
        ARENA = DATA + SEGCAP * 60 + 64, FILL = 0xEE, IDBASE = 0xFFF0, IDADD = 7 };
-
-static int seq_gt(uint32_t a, uint32_t b) /* util.rs:155-158 */
-{
-    uint32_t d = a - b;
-    return d < 0x80000000u && d != 0;
-}
-
-static void put32(uint8_t *p, uint32_t v) { p[0] = (uint8_t)(v >> 24); p[1] = (uint8_t)(v >> 16); p[2] = (uint8_t)(v >> 8); p[3] = (uint8_t)v; }
-
-/* The head of segment j of an entry: its row but for the lengths, id + j, seq + j * mss; both checksums zero. */
-static void make_head(uint8_t *h, const uint8_t *t, uint32_t hl, uint32_t j, uint32_t mss, uint32_t seglen)
-{
-    memcpy(h, t, hl);
-    uint32_t iphdr = 40;
-    if (hl == 40) {
-        const uint32_t len = hl + seglen, id = (((uint32_t)t[4] << 8 | t[5]) + j) & 0xffff;
-        iphdr = 20;
-        h[2] = (uint8_t)(len >> 8); h[3] = (uint8_t)len; h[4] = (uint8_t)(id >> 8); h[5] = (uint8_t)id; h[10] = h[11] = 0;
-    } else {
-        const uint32_t len = 20 + seglen;
-        h[4] = (uint8_t)(len >> 8); h[5] = (uint8_t)len;
-    }
-    const uint8_t *ts = t + iphdr + 4;
-    put32(h + iphdr + 4, ((uint32_t)ts[0] << 24 | (uint32_t)ts[1] << 16 | (uint32_t)ts[2] << 8 | ts[3]) + j * mss);
-    h[iphdr + 16] = h[iphdr + 17] = 0;
-}
 
 int main(void)
 {
@@ -93,8 +30,7 @@ int main(void)
         want[ARENA], back[ARENA], status[SEGCAP], w_status[SEGCAP];
     const uint64_t head_first = DATA;
 
-    for (size_t b = 0; b < ARENA; ++b)
-        arena[b] = (uint8_t)next_u64();
+    fill_random_bytes(arena, ARENA);
     for (uint32_t f = 0; f < NFL; ++f) {
         rns_tcp_flow *s = &flow[f];
         const uint32_t inflight = f % 4 == 1 ? 0 : (uint32_t)(next_u64() % 4000), acked = (uint32_t)(next_u64() % 500);
@@ -113,8 +49,7 @@ int main(void)
         mss[f] = (uint16_t)(f % 6 == 2 ? 100 + f : 1460);
         rexmit[f] = f % 3 == 0;
         uint8_t *t = tmpl + f * STRIDE;
-        for (uint32_t b = 0; b < STRIDE; ++b)
-            t[b] = (uint8_t)next_u64();
+        fill_random_bytes(t, STRIDE);
         if (f & 1) {
             hl8[f] = 60; t[0] = 0x60; t[6] = 6; t[7] = 64; t[52] = 0x50;
         } else {
@@ -178,12 +113,9 @@ int main(void)
             row[ip + 12] = 0x50;
             row[ip + 13] = 0x18;
             const uint32_t window = (0xffffu - (s->rq_len & 0xffffu)) & 0xffffu;  /* tcp.rs:403 */
-            row[ip + 14] = (uint8_t)(window >> 8);
-            row[ip + 15] = (uint8_t)window;
-            if (hl == 40) {
-                row[4] = (uint8_t)(next_packet_id >> 8);
-                row[5] = (uint8_t)next_packet_id;
-            }
+            put16(row + ip + 14, window);
+            if (hl == 40)
+                put16(row + 4, next_packet_id);
             for (uint32_t j = 0; j < npiece[k]; ++j, ++n_seg) {
                 const uint32_t seglen = nbytes[k] - j * mss[f] < mss[f] ? nbytes[k] - j * mss[f] : mss[f];
                 if (n_seg % 64 == 0)
@@ -193,7 +125,7 @@ int main(void)
                 frag_len[2 * n_seg] = hl;
                 frag_off[2 * n_seg + 1] = w_pay_off[e] + (uint64_t)j * mss[f];
                 frag_len[2 * n_seg + 1] = seglen;
-                make_head(want + frag_off[2 * n_seg], row, hl, j, mss[f], seglen);
+                make_segment_head(want + frag_off[2 * n_seg], row, hl, j, mss[f], seglen);
                 if (hl == 40) {  /* NEXT_PACKET_ID.fetch_add(1), ip_output_v4 only */
                     next_packet_id = (next_packet_id + 1) & 0xffff;
                     n_v4 += 1;
@@ -227,24 +159,13 @@ int main(void)
     CHECK(rns_tx_tcp_plan_work(NFL, NULL) == RNS_E_INVALID && rns_tx_tcp_plan_work((1u << 30) + 1, &need2) == RNS_E_INVALID,
           "the workspace helper's checks");
 
-    int dev_count = 0;
-    if (hipGetDeviceCount(&dev_count) != hipSuccess || dev_count == 0) {
-        fprintf(stderr, "no HIP device\n");
-        return 2;
-    }
-    rns_tcp_flow *d_flow, *d_flow_out;
-    rns_tx_plan_res *d_res;
-    uint64_t *d_sq_off, *d_pay_off, *d_head_off;
-    uint32_t *d_sq_seq, *d_sq_len, *d_pay_len, *d_seg_first, *d_blk_flow, *d_n, *d_add;
-    uint16_t *d_mss, *d_mss_out;
-    uint8_t *d_rexmit, *d_hl8, *d_tmpl, *d_tmpl_out, *d_hl8_out, *d_arena, *d_status;
-    void *d_work;
-#define UP(d, h, bytes)                                                      \
-    HIP_OK(hipMalloc((void **)&(d), (bytes)));                               \
-    HIP_OK(hipMemcpy((d), (h), (bytes), hipMemcpyHostToDevice))
-#define OUT(d, bytes)                                                        \
-    HIP_OK(hipMalloc((void **)&(d), (bytes)));                               \
-    HIP_OK(hipMemset((d), FILL, (bytes)))
+    rns_tcp_flow *d_flow = NULL, *d_flow_out = NULL;
+    rns_tx_plan_res *d_res = NULL;
+    uint64_t *d_sq_off = NULL, *d_pay_off = NULL, *d_head_off = NULL;
+    uint32_t *d_sq_seq = NULL, *d_sq_len = NULL, *d_pay_len = NULL, *d_seg_first = NULL, *d_blk_flow = NULL, *d_n = NULL, *d_add = NULL;
+    uint16_t *d_mss = NULL, *d_mss_out = NULL;
+    uint8_t *d_rexmit = NULL, *d_hl8 = NULL, *d_tmpl = NULL, *d_tmpl_out = NULL, *d_hl8_out = NULL, *d_arena = NULL, *d_status = NULL;
+    void *d_work = NULL;
     const uint32_t add[1] = {IDADD + 0x30000u};  /* mod 2^16 */
     UP(d_flow, flow, sizeof flow);
     UP(d_sq_off, sq_off, sizeof sq_off);
@@ -256,19 +177,19 @@ int main(void)
     UP(d_tmpl, tmpl, sizeof tmpl);
     UP(d_add, add, sizeof add);
     UP(d_arena, arena, ARENA);
-    OUT(d_flow_out, sizeof flow_out);
-    OUT(d_res, sizeof res);
-    OUT(d_pay_off, sizeof pay_off);
-    OUT(d_head_off, sizeof head_off);
-    OUT(d_pay_len, sizeof pay_len);
-    OUT(d_seg_first, sizeof seg_first);
-    OUT(d_blk_flow, sizeof blk_flow);
-    OUT(d_n, sizeof n_out);
-    OUT(d_mss_out, sizeof mss_out);
-    OUT(d_tmpl_out, sizeof tmpl_out);
-    OUT(d_hl8_out, sizeof hl8_out);
-    OUT(d_status, sizeof status);
-    OUT(d_work, need);
+    OUT(d_flow_out, sizeof flow_out, FILL);
+    OUT(d_res, sizeof res, FILL);
+    OUT(d_pay_off, sizeof pay_off, FILL);
+    OUT(d_head_off, sizeof head_off, FILL);
+    OUT(d_pay_len, sizeof pay_len, FILL);
+    OUT(d_seg_first, sizeof seg_first, FILL);
+    OUT(d_blk_flow, sizeof blk_flow, FILL);
+    OUT(d_n, sizeof n_out, FILL);
+    OUT(d_mss_out, sizeof mss_out, FILL);
+    OUT(d_tmpl_out, sizeof tmpl_out, FILL);
+    OUT(d_hl8_out, sizeof hl8_out, FILL);
+    OUT(d_status, sizeof status, FILL);
+    OUT(d_work, need, FILL);
 
     CHECK(rns_tx_tcp_plan_dev(d_flow, d_flow_out, NFL, d_sq_off, d_sq_seq, d_sq_len, d_mss, d_rexmit, d_tmpl, 0, d_hl8, IDBASE, d_add,
                               head_first, SEGCAP, d_tmpl_out, d_hl8_out, d_pay_off, d_pay_len, d_mss_out, d_head_off, d_seg_first,
@@ -277,7 +198,7 @@ int main(void)
                               d_add, head_first, SEGCAP, d_tmpl_out, d_hl8_out, d_pay_off, d_pay_len, d_mss_out, d_head_off,
                               d_seg_first, d_blk_flow, d_n, d_res, d_work, need - 1, NULL) == RNS_E_INVALID, "a short workspace");
     hipStream_t st;
-    HIP_OK(hipStreamCreate(&st));
+    HIP_OK(abi_stream(&st));
     /* plan, then segment with n_seg = seg_cap: one stream, nothing read in between */
     int rc = rns_tx_tcp_plan_dev(d_flow, d_flow_out, NFL, d_sq_off, d_sq_seq, d_sq_len, d_mss, d_rexmit, d_tmpl, STRIDE, d_hl8, IDBASE,
                                  d_add, head_first, SEGCAP, d_tmpl_out, d_hl8_out, d_pay_off, d_pay_len, d_mss_out, d_head_off,
@@ -287,7 +208,6 @@ int main(void)
                             d_blk_flow, E, SEGCAP, d_status, st);
     CHECK(rc == RNS_OK, "rns_tx_segment_dev: %d", rc);
     HIP_OK(hipStreamSynchronize(st));
-#define DOWN(h, d, bytes) HIP_OK(hipMemcpy((h), (d), (bytes), hipMemcpyDeviceToHost))
     DOWN(flow_out, d_flow_out, sizeof flow_out);
     DOWN(res, d_res, sizeof res);
     DOWN(pay_off, d_pay_off, sizeof pay_off);
@@ -322,10 +242,5 @@ int main(void)
     for (size_t b = 0; b < ARENA; ++b)
         CHECK(back[b] == want[b], "arena byte %zu: %02x != %02x", b, back[b], want[b]);
 
-    if (failures) {
-        fprintf(stderr, "%d checks failed\n", failures);
-        return 1;
-    }
-    printf("all checks passed (%u segments of %u flows, %u retransmits, %u flows waiting)\n", n_seg, NFL, n_rex, n_wait);
-    return 0;
+    return abi_finish("%u segments of %u flows, %u retransmits, %u flows waiting", n_seg, NFL, n_rex, n_wait);
 }

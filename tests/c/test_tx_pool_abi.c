@@ -11,45 +11,8 @@
  *
  * Prints "all checks passed" and exits 0 on success; exits 2 when no device memory can be had.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "rns_checksum.h"
-
-void oracle_tx_chain_fill(uint8_t *arena, uint64_t arena_bytes, const uint64_t *frag_off, const uint32_t *frag_len,
-                          const uint32_t *first, uint32_t n_frags, size_t n, uint8_t *status);
-
-static uint64_t rng_state = 0x7001F00Dull;
-static uint64_t next_u64(void)
-{
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-static int failures = 0;
-#define CHECK(cond, ...)                                                                           \
-    do {                                                                                           \
-        if (!(cond)) {                                                                             \
-            if (failures++ < 10) {                                                                 \
-                fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__);                               \
-                fprintf(stderr, __VA_ARGS__);                                                      \
-                fprintf(stderr, "\n");                                                             \
-            }                                                                                      \
-        }                                                                                          \
-    } while (0)
-#define HIP_OK(x)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_));              \
-            return 2;                                                                              \
-        }                                                                                          \
-    } while (0)
+#define ABI_TEST_SEED 0x7001F00Dull
+#include "abi_test.h"
 
 enum { N = 300, LOG2 = 9, BUF = 1 << LOG2, MAXPAY = 2000, MAXFR = 1 + (MAXPAY + BUF - 1) / BUF, NBUF = N * MAXFR,
        NBLK = (N + 63) / 64, KINDS = 7, EMPTY_HEAD = 131, OUTSIDE = 201 };
@@ -60,13 +23,11 @@ static uint32_t make_head(uint8_t *h, int k, uint32_t pay)
 {
     static const uint32_t hlen[KINDS] = {40, 60, 28, 28, 40, 41, 40};
     const uint32_t hl = hlen[k];
-    for (uint32_t b = 0; b < hl; ++b)
-        h[b] = (uint8_t)next_u64();
+    fill_random_bytes(h, hl);
     if (k == 1) {  /* IPv6, TCP */
-        h[0] = 0x60; h[4] = (uint8_t)((pay + 20) >> 8); h[5] = (uint8_t)(pay + 20); h[6] = 6; h[7] = 64;
+        h[0] = 0x60; put16(h + 4, pay + 20); h[6] = 6; h[7] = 64;
     } else {       /* IPv4: TCP, UDP (2), ICMP (3), TCP with a payload byte in the head (5), version 7 (6) */
-        const uint32_t len = hl + pay;
-        h[0] = k == 6 ? 0x75 : 0x45; h[2] = (uint8_t)(len >> 8); h[3] = (uint8_t)len; h[6] = 0x40; h[7] = 0; h[8] = 64;
+        h[0] = k == 6 ? 0x75 : 0x45; put16(h + 2, hl + pay); h[6] = 0x40; h[7] = 0; h[8] = 64;
         h[9] = k == 2 ? 17 : k == 3 ? 1 : 6;
     }
     return hl;
@@ -78,13 +39,7 @@ int main(void)
     static uint16_t pl16[N];
     static uint32_t idx[NBUF], blk_first[NBLK], first[N + 1], frag_len[NBUF], order[NBUF];
     static uint64_t frag_off[NBUF];
-    for (uint32_t j = 0; j < NBUF; ++j)
-        order[j] = j;
-    for (uint32_t j = NBUF - 1; j > 0; --j) {  /* a pool whose buffers have been in use: any order */
-        const uint32_t r = (uint32_t)(next_u64() % (j + 1)), t = order[j];
-        order[j] = order[r];
-        order[r] = t;
-    }
+    shuffled_order(order, NBUF);
     for (uint32_t i = 0; i < N; ++i) {
         const uint32_t edge[] = {0, 1, 2, BUF - 1, BUF, BUF + 1, 2 * BUF, 2 * BUF + 1, MAXPAY};
         pl16[i] = (uint16_t)(i % KINDS == 4 ? 0 : i < 9 ? edge[i] : next_u64() % (MAXPAY + 1));
@@ -103,8 +58,7 @@ int main(void)
         CHECK((i & 63) || blk_first[i >> 6] == first[i], "blk_first[%u]", i >> 6);
     }
 
-    for (size_t b = 0; b < sizeof pool; ++b)
-        pool[b] = (uint8_t)next_u64();
+    fill_random_bytes(pool, sizeof pool);
     for (uint32_t i = 0; i < N; ++i) {
         const uint32_t pay = pl16[i];
         uint32_t hl = make_head(head, (int)(i % KINDS), pay);
@@ -147,19 +101,10 @@ int main(void)
     uint16_t *d_pl = NULL;
     uint32_t *d_idx = NULL, *d_blk = NULL;
     hipStream_t st;
-    if (hipMalloc((void **)&d_pool, sizeof pool) != hipSuccess) {
-        fprintf(stderr, "hipMalloc failed: no usable device\n");
-        return 2;
-    }
-    HIP_OK(hipMalloc((void **)&d_status, N));
-    HIP_OK(hipMalloc((void **)&d_hl, N));
-    HIP_OK(hipMalloc((void **)&d_pl, N * sizeof *pl16));
-    HIP_OK(hipMalloc((void **)&d_idx, NBUF * sizeof *idx));
-    HIP_OK(hipMalloc((void **)&d_blk, NBLK * sizeof *blk_first));
-    HIP_OK(hipStreamCreate(&st));
-    HIP_OK(hipMemcpy(d_hl, hl8, N, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_pl, pl16, N * sizeof *pl16, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_blk, blk_first, NBLK * sizeof *blk_first, hipMemcpyHostToDevice));
+    UP(d_hl, hl8, N);
+    UP(d_pl, pl16, N * sizeof *pl16);
+    UP(d_blk, blk_first, NBLK * sizeof *blk_first);
+    HIP_OK(abi_stream(&st));
     for (int round = 0; round < 2; ++round) {
         if (round == 1) {  /* one index outside the pool: that datagram alone is rejected, untouched */
             const uint32_t f = first[OUTSIDE] + 1;
@@ -170,32 +115,25 @@ int main(void)
             oracle_tx_chain_fill(want, sizeof pool, frag_off, frag_len, first, nf, N, want_st);
             CHECK(want_st[OUTSIDE] == RNS_TX_MALFORMED, "the oracle rejects the index outside the pool");
         }
-        HIP_OK(hipMemcpy(d_pool, pool, sizeof pool, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(d_idx, idx, NBUF * sizeof *idx, hipMemcpyHostToDevice));
-        HIP_OK(hipMemset(d_status, 0x55, N));
+        UP(d_pool, pool, sizeof pool);
+        UP(d_idx, idx, NBUF * sizeof *idx);
+        OUT(d_status, N, 0x55);
         CHECK(rns_tx_fill_pool_dev(d_pool, sizeof pool, LOG2, d_idx, nf, d_blk, d_hl, d_pl, N, d_status, st) == RNS_OK,
               "rns_tx_fill_pool_dev");
         HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipMemcpy(status, d_status, N, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(back, d_pool, sizeof pool, hipMemcpyDeviceToHost));
+        DOWN(status, d_status, N);
+        DOWN(back, d_pool, sizeof pool);
         for (uint32_t i = 0; i < N; ++i)
             CHECK(status[i] == want_st[i], "round %d status %u: %02x != %02x", round, i, status[i], want_st[i]);
         for (size_t b = 0; b < sizeof pool; ++b)
             CHECK(back[b] == want[b], "round %d pool byte %zu: %02x != %02x", round, b, back[b], want[b]);
     }
     /* without the status array: the same bytes */
-    HIP_OK(hipMemcpy(d_pool, pool, sizeof pool, hipMemcpyHostToDevice));
+    UP(d_pool, pool, sizeof pool);
     CHECK(rns_tx_fill_pool_dev(d_pool, sizeof pool, LOG2, d_idx, nf, d_blk, d_hl, d_pl, N, NULL, st) == RNS_OK,
           "no status array");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(back, d_pool, sizeof pool, hipMemcpyDeviceToHost));
+    DOWN(back, d_pool, sizeof pool);
     CHECK(memcmp(back, want, sizeof pool) == 0, "without the status array: the pool differs");
-    hipStreamDestroy(st);
-    hipFree(d_pool); hipFree(d_status); hipFree(d_hl); hipFree(d_pl); hipFree(d_idx); hipFree(d_blk);
-    if (failures) {
-        fprintf(stderr, "%d checks failed\n", failures);
-        return 1;
-    }
-    printf("all checks passed\n");
-    return 0;
+    return abi_finish("%d datagrams in %u pool buffers", N, nf);
 }

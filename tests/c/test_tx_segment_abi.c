@@ -11,45 +11,8 @@
  *
  * Prints "all checks passed" and exits 0 on success; exits 2 when no device memory can be had.
  */
-#include <hip/hip_runtime_api.h>
-#include <stdint.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "rns_checksum.h"
-
-void oracle_tx_chain_fill(uint8_t *arena, uint64_t arena_bytes, const uint64_t *frag_off, const uint32_t *frag_len,
-                          const uint32_t *first, uint32_t n_frags, size_t n, uint8_t *status);
-
-static uint64_t rng_state = 0x5E67F00Dull;
-static uint64_t next_u64(void)
-{
-    uint64_t z = (rng_state += 0x9E3779B97F4A7C15ull);
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-static int failures = 0;
-#define CHECK(cond, ...)                                                                           \
-    do {                                                                                           \
-        if (!(cond)) {                                                                             \
-            if (failures++ < 10) {                                                                 \
-                fprintf(stderr, "FAIL %s:%d: ", __FILE__, __LINE__);                               \
-                fprintf(stderr, __VA_ARGS__);                                                      \
-                fprintf(stderr, "\n");                                                             \
-            }                                                                                      \
-        }                                                                                          \
-    } while (0)
-#define HIP_OK(x)                                                                                  \
-    do {                                                                                           \
-        hipError_t e_ = (x);                                                                       \
-        if (e_ != hipSuccess) {                                                                    \
-            fprintf(stderr, "%s:%d %s\n", __FILE__, __LINE__, hipGetErrorString(e_));              \
-            return 2;                                                                              \
-        }                                                                                          \
-    } while (0)
+#define ABI_TEST_SEED 0x5E67F00Dull
+#include "abi_test.h"
 
 enum { NFL = 60, STRIDE = 72, MAXSEG = 4096, PAY_BYTES = 1 << 20, ARENA = PAY_BYTES + MAXSEG * STRIDE, BAD_FLOW = 30 };
 
@@ -58,37 +21,16 @@ enum { NFL = 60, STRIDE = 72, MAXSEG = 4096, PAY_BYTES = 1 << 20, ARENA = PAY_BY
 static uint32_t make_template(uint8_t *t, int k, uint32_t seq, uint16_t id)
 {
     const uint32_t iphdr = (k & 1) ? 40 : 20, doff = k >= 2 ? 8 : 5, hl = iphdr + 4 * doff;
-    for (uint32_t b = 0; b < hl; ++b)
-        t[b] = (uint8_t)next_u64();
+    fill_random_bytes(t, hl);
     if (k & 1) {
         t[0] = 0x60; t[6] = 6; t[7] = 64;
     } else {
-        t[0] = 0x45; t[4] = (uint8_t)(id >> 8); t[5] = (uint8_t)id; t[6] = 0x40; t[7] = 0; t[8] = 64; t[9] = 6;
+        t[0] = 0x45; put16(t + 4, id); t[6] = 0x40; t[7] = 0; t[8] = 64; t[9] = 6;
     }
     uint8_t *tcp = t + iphdr;
-    tcp[4] = (uint8_t)(seq >> 24); tcp[5] = (uint8_t)(seq >> 16); tcp[6] = (uint8_t)(seq >> 8); tcp[7] = (uint8_t)seq;
+    put32(tcp + 4, seq);
     tcp[12] = (uint8_t)(doff << 4); tcp[13] = 0x18;  /* ACK | PSH */
     return hl;
-}
-
-/* The head of segment j: the template but for the lengths, id + j, seq + j * mss; both checksums zero. */
-static void make_head(uint8_t *h, const uint8_t *t, uint32_t hl, uint32_t j, uint32_t mss, uint32_t seglen)
-{
-    memcpy(h, t, hl);
-    uint32_t iphdr = 40;
-    if ((t[0] >> 4) == 4) {
-        const uint32_t len = hl + seglen, id = (((uint32_t)t[4] << 8 | t[5]) + j) & 0xffff;
-        iphdr = 20;
-        h[2] = (uint8_t)(len >> 8); h[3] = (uint8_t)len; h[4] = (uint8_t)(id >> 8); h[5] = (uint8_t)id; h[10] = h[11] = 0;
-    } else {
-        const uint32_t len = hl - 40 + seglen;
-        h[4] = (uint8_t)(len >> 8); h[5] = (uint8_t)len;
-    }
-    const uint8_t *ts = t + iphdr + 4;
-    const uint32_t seq = ((uint32_t)ts[0] << 24 | (uint32_t)ts[1] << 16 | (uint32_t)ts[2] << 8 | ts[3]) + j * mss;
-    uint8_t *tcp = h + iphdr;
-    tcp[4] = (uint8_t)(seq >> 24); tcp[5] = (uint8_t)(seq >> 16); tcp[6] = (uint8_t)(seq >> 8); tcp[7] = (uint8_t)seq;
-    tcp[16] = tcp[17] = 0;
 }
 
 int main(void)
@@ -97,8 +39,7 @@ int main(void)
     static uint16_t mss[NFL];
     static uint32_t pay_len[NFL], seg_first[NFL + 1], blk_flow[(MAXSEG + 63) / 64], frag_len[2 * MAXSEG], first[MAXSEG + 1];
     static uint64_t pay_off[NFL], head_off[NFL], frag_off[2 * MAXSEG];
-    for (size_t b = 0; b < sizeof arena; ++b)
-        arena[b] = (uint8_t)next_u64();
+    fill_random_bytes(arena, sizeof arena);
     uint64_t at = 64;
     for (uint32_t f = 0; f < NFL; ++f) {
         static const uint16_t ms[] = {1460, 537, 1, 1459, 16};
@@ -151,27 +92,14 @@ int main(void)
     uint32_t *d_pl = NULL, *d_sf = NULL, *d_bf = NULL;
     uint64_t *d_po = NULL, *d_ho = NULL;
     hipStream_t st;
-    if (hipMalloc((void **)&d_arena, ARENA) != hipSuccess) {
-        fprintf(stderr, "hipMalloc failed: no usable device\n");
-        return 2;
-    }
-    HIP_OK(hipMalloc((void **)&d_tmpl, sizeof tmpl));
-    HIP_OK(hipMalloc((void **)&d_hl, NFL));
-    HIP_OK(hipMalloc((void **)&d_status, MAXSEG));
-    HIP_OK(hipMalloc((void **)&d_mss, sizeof mss));
-    HIP_OK(hipMalloc((void **)&d_pl, sizeof pay_len));
-    HIP_OK(hipMalloc((void **)&d_sf, sizeof seg_first));
-    HIP_OK(hipMalloc((void **)&d_bf, sizeof blk_flow));
-    HIP_OK(hipMalloc((void **)&d_po, sizeof pay_off));
-    HIP_OK(hipMalloc((void **)&d_ho, sizeof head_off));
-    HIP_OK(hipStreamCreate(&st));
-    HIP_OK(hipMemcpy(d_hl, hl8, NFL, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_mss, mss, sizeof mss, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_pl, pay_len, sizeof pay_len, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_sf, seg_first, sizeof seg_first, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_bf, blk_flow, sizeof blk_flow, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_po, pay_off, sizeof pay_off, hipMemcpyHostToDevice));
-    HIP_OK(hipMemcpy(d_ho, head_off, sizeof head_off, hipMemcpyHostToDevice));
+    UP(d_hl, hl8, NFL);
+    UP(d_mss, mss, sizeof mss);
+    UP(d_pl, pay_len, sizeof pay_len);
+    UP(d_sf, seg_first, sizeof seg_first);
+    UP(d_bf, blk_flow, sizeof blk_flow);
+    UP(d_po, pay_off, sizeof pay_off);
+    UP(d_ho, head_off, sizeof head_off);
+    HIP_OK(abi_stream(&st));
     for (int round = 0; round < 2; ++round) {
         if (round == 1)  /* one template with a bad version: that send alone is rejected, its head range untouched */
             tmpl[BAD_FLOW * STRIDE] = 0x75;
@@ -189,7 +117,7 @@ int main(void)
                 const uint32_t j = s - seg_first[f];
                 CHECK(first[s] == 2 * s && frag_off[2 * s] == head_off[f] + (uint64_t)j * hl8[f] && frag_len[2 * s] == hl8[f] &&
                           frag_off[2 * s + 1] == pay_off[f] + (uint64_t)j * mss[f], "chain of segment %u", s);
-                make_head(want + frag_off[2 * s], tmpl + f * STRIDE, hl8[f], j, mss[f], frag_len[2 * s + 1]);
+                make_segment_head(want + frag_off[2 * s], tmpl + f * STRIDE, hl8[f], j, mss[f], frag_len[2 * s + 1]);
                 c_first[nch] = 2 * nch;
                 c_off[2 * nch] = frag_off[2 * s]; c_len[2 * nch] = frag_len[2 * s];
                 c_off[2 * nch + 1] = frag_off[2 * s + 1]; c_len[2 * nch + 1] = frag_len[2 * s + 1];
@@ -204,14 +132,14 @@ int main(void)
         }
         CHECK(round == 0 ? nch == n_seg : nch < n_seg, "round %d: %u chains", round, nch);
 
-        HIP_OK(hipMemcpy(d_arena, arena, ARENA, hipMemcpyHostToDevice));
-        HIP_OK(hipMemcpy(d_tmpl, tmpl, sizeof tmpl, hipMemcpyHostToDevice));
-        HIP_OK(hipMemset(d_status, 0x55, MAXSEG));
+        UP(d_arena, arena, ARENA);
+        UP(d_tmpl, tmpl, sizeof tmpl);
+        OUT(d_status, MAXSEG, 0x55);
         CHECK(rns_tx_segment_dev(d_arena, ARENA, d_tmpl, STRIDE, d_hl, d_po, d_pl, d_mss, d_ho, d_sf, d_bf, NFL, n_seg, d_status,
                                  st) == RNS_OK, "rns_tx_segment_dev");
         HIP_OK(hipStreamSynchronize(st));
-        HIP_OK(hipMemcpy(status, d_status, MAXSEG, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(back, d_arena, ARENA, hipMemcpyDeviceToHost));
+        DOWN(status, d_status, MAXSEG);
+        DOWN(back, d_arena, ARENA);
         for (uint32_t i = 0; i < n_seg; ++i)
             CHECK(status[i] == want_st[i], "round %d status %u: %02x != %02x", round, i, status[i], want_st[i]);
         for (uint32_t i = n_seg; i < MAXSEG; ++i)
@@ -220,19 +148,11 @@ int main(void)
             CHECK(back[b] == want[b], "round %d arena byte %zu: %02x != %02x", round, b, back[b], want[b]);
     }
     /* without the status array: the same bytes */
-    HIP_OK(hipMemcpy(d_arena, arena, ARENA, hipMemcpyHostToDevice));
+    UP(d_arena, arena, ARENA);
     CHECK(rns_tx_segment_dev(d_arena, ARENA, d_tmpl, STRIDE, d_hl, d_po, d_pl, d_mss, d_ho, d_sf, d_bf, NFL, n_seg, NULL, st) ==
               RNS_OK, "no status array");
     HIP_OK(hipStreamSynchronize(st));
-    HIP_OK(hipMemcpy(back, d_arena, ARENA, hipMemcpyDeviceToHost));
+    DOWN(back, d_arena, ARENA);
     CHECK(memcmp(back, want, ARENA) == 0, "without the status array: the arena differs");
-    hipStreamDestroy(st);
-    hipFree(d_arena); hipFree(d_tmpl); hipFree(d_hl); hipFree(d_status); hipFree(d_mss); hipFree(d_pl); hipFree(d_sf);
-    hipFree(d_bf); hipFree(d_po); hipFree(d_ho);
-    if (failures) {
-        fprintf(stderr, "%d checks failed\n", failures);
-        return 1;
-    }
-    printf("all checks passed\n");
-    return 0;
+    return abi_finish("%u segments of %d sends", n_seg, NFL);
 }

@@ -7,6 +7,7 @@ import subprocess
 
 import pytest
 
+from abi_helper import assert_header_compiles
 from conftest import ROOT
 from rustnetworkstack_amd import _lib
 
@@ -45,9 +46,7 @@ def test_library_contains_gfx950_code_object():
 
 
 def test_header_compiles_as_c():
-    src = '#include "rns_checksum.h"\nint main(void){ return rns_abi_version() == RNS_ABI_VERSION ? 0 : 1; }\n'
-    subprocess.run(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-",
-                    "-fsyntax-only"], input=src, text=True, check=True)
+    assert_header_compiles("int main(void){ return rns_abi_version() == RNS_ABI_VERSION ? 0 : 1; }\n", std="c99")
 
 
 @pytest.mark.skipif(_lib.load().rns_device_count() > 0, reason="checks the GPU-less behaviour")

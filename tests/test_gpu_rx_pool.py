@@ -15,6 +15,7 @@ from rustnetworkstack_amd.batch import recv_batch_pool, rx_pool_layout, rx_verif
 from rustnetworkstack_amd.pipeline import RxPoolPipeline
 from rustnetworkstack_amd.workloads import LOCAL4, LOCAL6, RxChainBatch
 from rx_chain_helper import make_datagrams, netbuffers, rx_verify_chain_ref
+from rx_place_helper import lay_pool
 from test_rx_oracle import L4, L6, R4, R6, ipv4, ipv6, tcp_seg
 
 pytestmark = pytest.mark.gpu
@@ -31,23 +32,6 @@ def gpu_present():
 
 def dev(a, view):
     return torch.from_numpy(np.ascontiguousarray(a).view(view)).to(DEV)
-
-
-def lay_pool(pkts, buf, shuffled=False, seed=1, spare=3):
-    """The datagrams in a pool of buf-byte buffers as recv_packet leaves them: (pool uint8, buf_idx
-    uint32, blk_first uint32, len16 uint16); buffers in order or a seeded permutation, `spare`
-    unused ones among them, the unused bytes random."""
-    len16 = np.array([len(p) for p in pkts], dtype=np.uint16)
-    blk_first, first, nf = rx_pool_layout(len16, buf)
-    nbuf = nf + spare
-    order = np.random.default_rng(seed).permutation(nbuf) if shuffled else np.arange(nbuf)
-    idx = order[:nf].astype(np.uint32)
-    pool = np.frombuffer(O.splitmix64_bytes(seed ^ 0x9001, nbuf * buf).tobytes(), dtype=np.uint8).copy()
-    rows = pool.reshape(nbuf, buf)
-    for i, p in enumerate(pkts):
-        for j, f in enumerate(netbuffers(p, buf)):
-            rows[idx[first[i] + j], :len(f)] = np.frombuffer(f, dtype=np.uint8)
-    return pool, idx, blk_first, len16
 
 
 def expand(idx, blk_first, len16, buf, n_frags=None):

@@ -6,9 +6,9 @@ import numpy as np
 import pytest
 import torch
 
+from abi_helper import FAKE
 from rustnetworkstack_amd import _lib, batch, icmp
 
-FAKE = ctypes.c_void_p(4096)
 PTRS = ("rx", "idx", "blk", "len16", "ip4", "ip6", "tx", "free", "add", "tbf", "thl", "tpl", "src", "count", "status", "l4",
         "echo", "work")
 OPTIONAL = ("add", "src", "l4")

@@ -6,10 +6,10 @@ import ctypes
 import numpy as np
 import pytest
 
+from abi_helper import FAKE
 from rustnetworkstack_amd import _lib
 from rustnetworkstack_amd.workloads import make_layout, rx_chain_layout
 
-FAKE = ctypes.c_void_p(4096)
 L4 = bytes([10, 0, 0, 2])
 L6 = bytes(range(16))
 

@@ -2,17 +2,12 @@
 GPU: the symbols, the constants and record sizes, the argument checks (all before the device is
 touched), the GPU-less error, the workspace helper and the CPU-tensor refusal."""
 import ctypes
-import os
-import re
 
 import pytest
 
-from conftest import ROOT
+from abi_helper import BIG, FAKE, ODD, assert_header_compiles, assert_header_defines
 from rustnetworkstack_amd import _lib, flow
 
-FAKE = ctypes.c_void_p(4096)
-ODD = ctypes.c_void_p(4096 + 2)
-BIG = 1 << 40
 UPD = ("meta", "flow_in", "pend_in", "flow_out", "pend_out", "seg", "res", "work")
 ACKP = ("meta", "seg", "flow", "tmpl", "hl8", "work", "out", "src", "len8", "nacks")
 
@@ -42,18 +37,11 @@ def test_symbols_constants_and_sizes():
         assert len(getattr(lib, name).argtypes) == argc
     assert lib.rns_abi_version() == 1  # additive: the ABI version stays
     assert (flow.FLOW_DTYPE.itemsize, flow.SEG_DTYPE.itemsize, flow.RES_DTYPE.itemsize) == (40, 8, 24)
-    text = open(os.path.join(ROOT, "include", "rns_checksum.h")).read()
-    for name in ("RNS_TCP_ESTABLISHED", "RNS_FLOW_MAX_SEGS", "RNS_SEG_CONSUMED", "RNS_SEG_ACK", "RNS_SEG_TIMER", "RNS_EV_WND",
-                 "RNS_STOP_NONE", "RNS_STOP_MANY", "RNS_STOP_STATE", "RNS_STOP_FLAGS", "RNS_STOP_OPTIONS",
-                 "RNS_STOP_OUTSIDE", "RNS_STOP_PEND"):
-        m = re.search(rf"#define {name}\s+(\d+)u", text)
-        assert m and int(m.group(1)) == getattr(_lib, name), name
-    src = ('#include "rns_checksum.h"\n'
-           "_Static_assert(sizeof(rns_tcp_flow) == 40 && sizeof(rns_rx_tcp_seg) == 8 && sizeof(rns_tcp_flow_res) == 24, \"\");\n"
-           "int main(void){ return 0; }\n")
-    import subprocess
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-",
-                    "-fsyntax-only"], input=src, text=True, check=True)
+    assert_header_defines(("RNS_TCP_ESTABLISHED", "RNS_FLOW_MAX_SEGS", "RNS_SEG_CONSUMED", "RNS_SEG_ACK", "RNS_SEG_TIMER",
+                           "RNS_EV_WND", "RNS_STOP_NONE", "RNS_STOP_MANY", "RNS_STOP_STATE", "RNS_STOP_FLAGS", "RNS_STOP_OPTIONS",
+                           "RNS_STOP_OUTSIDE", "RNS_STOP_PEND"))
+    assert_header_compiles("_Static_assert(sizeof(rns_tcp_flow) == 40 && sizeof(rns_rx_tcp_seg) == 8 && "
+                           "sizeof(rns_tcp_flow_res) == 24, \"\");\nint main(void){ return 0; }\n")
 
 
 def test_update_argument_checks_come_before_the_device():

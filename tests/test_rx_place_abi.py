@@ -7,9 +7,9 @@ import ctypes
 import numpy as np
 import pytest
 
+from abi_helper import FAKE
 from rustnetworkstack_amd import _lib, batch, place
 
-FAKE = ctypes.c_void_p(4096)
 PTRS = ("pool", "idx", "blk", "len16", "ip4", "ip6", "tbl", "nseq", "woff", "wlen", "stream", "status", "meta")
 IP4, IP6 = bytes(4), bytes(16)
 

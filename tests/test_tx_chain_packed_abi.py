@@ -6,11 +6,11 @@ import ctypes
 import numpy as np
 import pytest
 
+from abi_helper import FAKE
 from rustnetworkstack_amd import _lib
 from rustnetworkstack_amd.batch import tx_chain_packed_layout
 from rustnetworkstack_amd.pipeline import chain_compact_form, compact_desc_bytes
 
-FAKE = ctypes.c_void_p(4096)
 
 
 def call(lib, arena=FAKE, hblk=FAKE, hl=FAKE, pblk=FAKE, pl=FAKE, align=4, n=1):

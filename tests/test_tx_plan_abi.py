@@ -2,17 +2,12 @@
 every argument check (all before the device is touched), the GPU-less error, the workspace helper and
 the CPU-tensor refusal."""
 import ctypes
-import os
-import re
-import subprocess
 
 import pytest
 
-from conftest import ROOT
+from abi_helper import BIG, FAKE, assert_header_compiles, assert_header_defines
 from rustnetworkstack_amd import _lib, batch, send
 
-FAKE = ctypes.c_void_p(4096)
-BIG = 1 << 40
 # name -> required alignment (0: bytes); the optional ones are not in REQUIRED
 ALIGN = {"flow_in": 4, "flow_out": 4, "sq_off": 8, "sq_seq": 4, "sq_len": 4, "mss": 2, "rexmit": 0, "tmpl": 0, "hl8": 0,
          "id_add": 4, "tmpl_out": 0, "hl8_out": 0, "pay_off": 8, "pay_len": 4, "mss_out": 2, "head_off": 8, "seg_first": 4,
@@ -43,15 +38,8 @@ def test_symbols_constants_and_sizes():
     assert send.RES_DTYPE.itemsize == 16 and batch.PLAN_RES_DTYPE is send.RES_DTYPE
     assert batch.tx_tcp_plan is send.tx_tcp_plan and batch.plan_host is send.plan_host
     assert batch.tx_tcp_send is send.tx_tcp_send and batch.tx_plan_work is send.tx_plan_work
-    text = open(os.path.join(ROOT, "include", "rns_checksum.h")).read()
-    for name in ("RNS_PLAN_NONE", "RNS_PLAN_WINDOW", "RNS_PLAN_STATE", "RNS_PLAN_BAD", "RNS_PLAN_TMPL", "RNS_PLAN_CAP"):
-        m = re.search(rf"#define {name}\s+(\d+)u", text)
-        assert m and int(m.group(1)) == getattr(_lib, name), name
-    src = ('#include "rns_checksum.h"\n'
-           "_Static_assert(sizeof(rns_tx_plan_res) == 16, \"\");\n"
-           "int main(void){ return 0; }\n")
-    subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-x", "c", "-",
-                    "-fsyntax-only"], input=src, text=True, check=True)
+    assert_header_defines(("RNS_PLAN_NONE", "RNS_PLAN_WINDOW", "RNS_PLAN_STATE", "RNS_PLAN_BAD", "RNS_PLAN_TMPL", "RNS_PLAN_CAP"))
+    assert_header_compiles("_Static_assert(sizeof(rns_tx_plan_res) == 16, \"\");\nint main(void){ return 0; }\n")
 
 
 def test_argument_checks_come_before_the_device():

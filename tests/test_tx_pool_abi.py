@@ -6,9 +6,9 @@ import ctypes
 import numpy as np
 import pytest
 
+from abi_helper import FAKE
 from rustnetworkstack_amd import _lib, batch
 
-FAKE = ctypes.c_void_p(4096)
 
 
 def call(lib, pool=FAKE, log2=9, idx=FAKE, n_frags=1, blk=FAKE, hl=FAKE, pl=FAKE, n=1, status=None):

@@ -6,10 +6,10 @@ import ctypes
 import numpy as np
 import pytest
 
+from abi_helper import FAKE
 from rustnetworkstack_amd import _lib, batch
 from tx_segment_helper import Flow, chains, data_bytes, lay, template
 
-FAKE = ctypes.c_void_p(4096)
 ARGS = ("arena", "tmpl", "hl", "po", "pl", "mss", "ho", "sf", "bf")
 
 

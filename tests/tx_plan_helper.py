@@ -8,6 +8,7 @@ import numpy as np
 
 from oracle import oracle as O
 from rx_flow_helper import ESTABLISHED, FLOW, template_ok
+from rx_place_helper import seq_gt
 from tx_segment_helper import head
 
 RES = np.dtype([("new_bytes", "<u4"), ("new_segs", "<u4"), ("rexmit_bytes", "<u4"), ("why", "u1"), ("pad", "u1", (3,))])
@@ -18,11 +19,6 @@ FLAG_ACK, FLAG_PSH = 0x10, 0x08
 M32 = 0xFFFFFFFF
 FILL = 0xEE
 KEYS = ("tmpl", "head_len8", "pay_off", "pay_len", "mss", "head_off", "seg_first", "blk_flow", "n", "res", "flows_out")
-
-
-def seq_gt(val1, val2):                                   # util.rs:155-158
-    diff = (val1 - val2) & M32
-    return diff < 0x80000000 and diff != 0
 
 
 class Socket:
