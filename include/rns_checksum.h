@@ -527,6 +527,95 @@ int rns_rx_icmp_echo_pool_dev(const uint8_t *d_rx_pool, uint64_t rx_pool_bytes, 
  * RNS_E_INVALID for a NULL bytes or n_pkts > RNS_CHAIN_MAX_PACKETS. */
 int rns_rx_icmp_echo_work(uint32_t n_pkts, uint64_t *bytes);
 
+/* UDP receive demux over pool buffers: udp_input (udp.rs:126-148) on the device — the UDP twin of
+ * rns_rx_tcp_place_pool_dev.  For a receive batch in the pool form above, every accepted UDP datagram
+ * whose destination port has a socket becomes one entry of that socket's receive_queue: a 32-byte record
+ * (source address, source port, length) and its payload, copied to a 16-byte-aligned place in d_data.  A
+ * socket's entries are contiguous, in arrival order, so the bytes successive udp_recv calls (udp.rs:75-98)
+ * hand out lie in order on the device, and the host reads one dword per socket and 32 B per delivered
+ * datagram instead of touching every datagram.
+ * The form is defined by what it expands to:
+ *   Status: d_status[i] and d_l4_sum[i] are exactly what rns_rx_verify_pool_dev gives for the same pool
+ *     and descriptors.
+ *   Decode: with T = d_len16[i] and h the IP header length as the verify parses it (IHL * 4, or 40),
+ *     datagram i is a UDP datagram (RNS_UDP_DGRAM) iff its status has RNS_RX_ACCEPT, its protocol (IPv4
+ *     byte 9, IPv6 byte 6) is 17 and T - h >= 8.  sport and dport are the header's big-endian fields and
+ *     the payload is bytes [h + 8, T) of the datagram: byte o at offset o & (B - 1) of buffer
+ *     d_buf_idx[first_i + (o >> buf_log2)], B = 2^buf_log2.  The UDP length field and the UDP checksum are
+ *     not looked at: the reference reads neither.  Everything else has d_udp[i] == 0.  (For T - h < 8 the
+ *     reference panics in header[2..4] / trim_head(8): parity is unpinned there.)
+ *   Lookup: s = d_port_tbl[dport]; RNS_UDP_SOCK is set iff s < n_socks.  Anything else takes the "No
+ *     socket listening" path: dropped, no record.  With n_socks == 0 every UDP datagram is RNS_UDP_DGRAM
+ *     without a socket and d_port_tbl is not read.  Sockets past RNS_UDP_MAX_SOCKS stay on the host and
+ *     show as unbound here.
+ *   Queues: socket s's entries are the datagrams with RNS_UDP_SOCK and socket s in ascending i, the order
+ *     push_back would have met them, and the queues are laid out socket-major: position(i) = (entries of
+ *     sockets < s) + (entries of s before i).  off16 follows the same order, each payload taking
+ *     ceil(len / 16) units of 16 bytes: every payload starts 16-byte aligned, and a zero-length datagram
+ *     is an entry with no units (the reference queues it, and udp_recv returns 0 for it).
+ *     d_q_first[s] = the position of s's first entry, d_q_first[n_socks] = all entries, and d_count =
+ *     {entries, units}, both counted before any cut.  (The units are counted in 32 bits, which the bound on
+ *     n_frags below makes exact unless blocks of d_blk_first share entries of d_buf_idx; such a batch is
+ *     outside the domain — still nothing outside the arrays is read or written.)
+ *   Cut: entry i is RNS_UDP_QUEUED iff position < rec_cap and 16 * (off16 + units) <= data_bytes.
+ *     Otherwise it is RNS_UDP_NOROOM: no record is written, no byte copied, d_pos[i] = 0xffffffff, and the
+ *     host queues it.  With rec_cap >= n_pkts and data_bytes >= n_frags << buf_log2 nothing is ever cut.
+ *   Bytes: a queued entry's record goes to d_rec[position] (flags = d_udp[i]) and its payload to
+ *     d_data[16 * off16 ..).  At most the bytes from the payload's end to the next 16-byte boundary of its
+ *     own range may also be written, with unspecified values.  No other byte of d_data or d_rec is written;
+ *     d_pos[i] is the position of a queued entry and 0xffffffff for every other datagram.  The pool and
+ *     every input stay as they were.  The same inputs give the same bytes on every run.
+ * Whatever the descriptors and the table hold, nothing outside the pool, the table's 65536 entries and the
+ * arrays is read, and nothing outside d_data[0 .. data_bytes), d_rec[0 .. rec_cap) and the per-datagram
+ * and per-socket outputs is written.
+ * The launches after the verify: one that classifies and counts per (socket, tile of 512 datagrams), the
+ * three of a prefix sum over those counts, and one that ranks, writes the records and copies each payload
+ * once.  No atomic decides an output.
+ * n_pkts == 0 is RNS_OK with d_count zeroed and d_q_first[0 .. n_socks] zero.  n_socks >
+ * RNS_UDP_MAX_SOCKS, buf_log2 outside 7..15 (60 + 8 header bytes must lie in the first buffer), a NULL
+ * d_pool / d_blk_first / d_len16 / d_status / d_udp / d_q_first / d_count / d_work / local address, a NULL
+ * d_buf_idx with n_frags > 0, a NULL d_port_tbl with n_socks > 0, a NULL d_data with data_bytes > 0, a NULL
+ * d_rec with rec_cap > 0, a d_pool, d_data, d_rec or d_work that is not 16-byte aligned, work_bytes below
+ * rns_rx_udp_demux_work's answer, n_pkts > RNS_CHAIN_MAX_PACKETS, or (uint64_t)n_frags << buf_log2 >= 2^36
+ * (so that the unit counts fit 32 bits) is RNS_E_INVALID, all before the device is touched. */
+#define RNS_UDP_MAX_SOCKS 1024u
+#define RNS_UDP_NO_SOCK   0xffffu
+#define RNS_UDP_DGRAM   0x01u  /* decoded as UDP: udp_input would be called on it */
+#define RNS_UDP_SOCK    0x02u  /* its destination port has a socket */
+#define RNS_UDP_QUEUED  0x04u  /* its record is written and its payload copied */
+#define RNS_UDP_NOROOM  0x08u  /* it has a socket, but rec_cap or data_bytes does not take it: the host queues it */
+typedef struct rns_udp_rec {          /* 32 bytes: one receive_queue entry */
+    uint8_t  ip[16];                  /* source address: family 4 in ip[0..4], rest zero */
+    uint32_t src;                     /* the datagram's index in the batch */
+    uint32_t off16;                   /* payload start in d_data, in units of 16 bytes */
+    uint16_t sport, len;              /* host byte order; len = payload bytes (may be 0) */
+    uint8_t  family, flags, pad[2];   /* 4 / 6; flags = d_udp[src]; pad zero */
+} rns_udp_rec;
+int rns_rx_udp_demux_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2,
+                              const uint32_t *d_buf_idx, uint32_t n_frags,
+                              const uint32_t *d_blk_first,   /* (n_pkts + 63) / 64 entries */
+                              const uint16_t *d_len16, uint32_t n_pkts,
+                              const uint8_t *local_ipv4, const uint8_t *local_ipv6,
+                              const uint16_t *d_port_tbl /* 65536 entries: rns_rx_udp_port_table_build's */,
+                              uint32_t n_socks,
+                              uint8_t *d_data, uint64_t data_bytes,
+                              rns_udp_rec *d_rec, uint32_t rec_cap,
+                              uint32_t *d_q_first /* n_socks + 1 */, uint32_t *d_count /* 2: records, 16-byte units */,
+                              uint8_t *d_status, uint16_t *d_l4_sum /* optional */, uint8_t *d_udp /* n_pkts */,
+                              uint32_t *d_pos /* optional, n_pkts: record position or 0xffffffff */,
+                              void *d_work, uint64_t work_bytes, void *stream);
+
+/* The demux's workspace in bytes for n_pkts datagrams and n_socks sockets (CPU only): non-zero, monotone
+ * in both, at most 64 MiB for 2^20 datagrams and 1024 sockets.  RNS_E_INVALID for a NULL bytes, n_pkts >
+ * RNS_CHAIN_MAX_PACKETS or n_socks > RNS_UDP_MAX_SOCKS. */
+int rns_rx_udp_demux_work(uint32_t n_pkts, uint32_t n_socks, uint64_t *bytes);
+
+/* Host helper for the demux's port table (CPU only), PORT_MAP as an array: all 65536 entries of tbl are
+ * set to RNS_UDP_NO_SOCK, then tbl[ports[s]] = s (ports in host byte order).  Copy the table to the device
+ * as it is.  RNS_E_INVALID for a duplicate port (udp_open's "Port already in use"; the table's contents are
+ * then unspecified), n_socks > RNS_UDP_MAX_SOCKS, a NULL tbl, or a NULL ports with n_socks > 0. */
+int rns_rx_udp_port_table_build(const uint16_t *ports, uint32_t n_socks, uint16_t *tbl /* 65536 */);
+
 /* TCP flow update: the rest of tcp_input for an Established socket (tcp.rs:642-740) on the device,
  * over the placement's d_meta as it is — the advance of receive_next_seq and the reassembler's
  * next_sequence, the delayed-ACK count and its immediate ACKs, the ACK-field check that trims the

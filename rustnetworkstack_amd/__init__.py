@@ -20,16 +20,19 @@
 * ``icmp``      — ICMP echo responder: every accepted echo request of a receive batch becomes a finished
                   reply in a transmit pool on the device, buffers drawn from a free list; the same on
                   the host for what the device leaves (also ``batch.*``);
+* ``udp``       — UDP receive demux: every accepted UDP datagram to a bound port becomes a record and a
+                  payload in its socket's queue on the device, the queues contiguous and in arrival order;
+                  the same on the host for what the device leaves (also ``batch.*``);
 * ``workloads`` — the synthetic packet batches BASELINE.json's configs name.
 """
 from . import _lib, util  # noqa: F401
 from ._lib import ChecksumError, ChecksumLibraryMissing  # noqa: F401
 
-__all__ = ["util", "batch", "pool", "segment", "place", "flow", "send", "icmp", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
+__all__ = ["util", "batch", "pool", "segment", "place", "flow", "send", "icmp", "udp", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
 
 
 def __getattr__(name):
-    if name in ("batch", "pool", "segment", "place", "flow", "send", "icmp", "workloads"):
+    if name in ("batch", "pool", "segment", "place", "flow", "send", "icmp", "udp", "workloads"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -159,7 +159,7 @@ def _call(name: str, dev: torch.device, *args) -> None:
 
 
 def _ptr(t: torch.Tensor | None):
-    """A tensor's address; None (a null pointer) for no tensor and for an empty one (place, flow, send, icmp)."""
+    """A tensor's address; None (a null pointer) for no tensor and for an empty one (place, flow, send, icmp, udp)."""
     return t.data_ptr() if t is not None and t.numel() else None
 
 
@@ -858,6 +858,9 @@ _FLOW_API = ("FLOW_DTYPE", "RES_DTYPE", "SEG_DTYPE", "flow_update_host", "flow_u
 _SEND_API = ("PLAN_RES_DTYPE", "plan_host", "tx_plan_work", "tx_tcp_plan", "tx_tcp_send")
 # and the ICMP echo responder (icmp.py): batch.rx_icmp_echo_pool, batch.echo_host, batch.echo_respond, batch.echo_work.
 _ICMP_API = ("echo_host", "echo_respond", "echo_work", "rx_icmp_echo_pool")
+# and the UDP receive demux (udp.py): batch.rx_udp_demux_pool, batch.demux_host, batch.drain, batch.udp_demux,
+# batch.port_table, batch.demux_work.
+_UDP_API = ("demux_host", "demux_work", "drain", "port_table", "rx_udp_demux_pool", "udp_demux")
 
 
 def __getattr__(name):
@@ -879,4 +882,7 @@ def __getattr__(name):
     if name in _ICMP_API:
         from . import icmp
         return getattr(icmp, name)
+    if name in _UDP_API:
+        from . import udp
+        return getattr(udp, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -525,6 +525,53 @@ int rns_rx_icmp_echo_pool_dev(const uint8_t *d_rx_pool, uint64_t rx_pool_bytes, 
                           static_cast<hipStream_t>(stream));
 }
 
+int rns_rx_udp_demux_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2, const uint32_t *d_buf_idx,
+                              uint32_t n_frags, const uint32_t *d_blk_first, const uint16_t *d_len16, uint32_t n_pkts,
+                              const uint8_t *local_ipv4, const uint8_t *local_ipv6, const uint16_t *d_port_tbl,
+                              uint32_t n_socks, uint8_t *d_data, uint64_t data_bytes, rns_udp_rec *d_rec, uint32_t rec_cap,
+                              uint32_t *d_q_first, uint32_t *d_count, uint8_t *d_status, uint16_t *d_l4_sum, uint8_t *d_udp,
+                              uint32_t *d_pos, void *d_work, uint64_t work_bytes, void *stream)
+{
+    static_assert(sizeof(rns_udp_rec) == 32, "rns_k_udp.hpp: a record is two 16-byte stores");
+    if (n_socks > RNS_UDP_MAX_SOCKS || !d_q_first || !d_count || misaligned(d_q_first, 3) || misaligned(d_count, 3))
+        return RNS_E_INVALID;
+    if (n_pkts == 0) {  // no datagram: the counts and the empty queues alone
+        RNS_TRY(check_device());
+        RNS_TRY(hip_status(hipMemsetAsync(d_count, 0, 8, static_cast<hipStream_t>(stream))));
+        return hip_status(hipMemsetAsync(d_q_first, 0, 4ull * (n_socks + 1), static_cast<hipStream_t>(stream)));
+    }
+    // every rejection of the verify's and this entry's own, before the device is touched
+    if (buf_log2 < kUdpMinLog2 || buf_log2 > kPoolMaxLog2 || n_pkts > RNS_CHAIN_MAX_PACKETS || !d_pool || !d_blk_first ||
+        !d_len16 || (n_frags && !d_buf_idx) || !rx_valid(d_status, local_ipv4, local_ipv6) || !d_udp || !d_work ||
+        (n_socks && !d_port_tbl) || (data_bytes && !d_data) || (rec_cap && !d_rec) || misaligned(d_pool, 15) ||
+        misaligned(d_data, 15) || misaligned(d_rec, 15) || misaligned(d_work, 15) || misaligned(d_port_tbl, 1) ||
+        misaligned(d_pos, 3) || work_bytes < udp_work_bytes(n_pkts, n_socks) ||
+        (static_cast<uint64_t>(n_frags) << buf_log2) >= (1ull << 36))
+        return RNS_E_INVALID;
+    // the verify as it is: its kernel, its status and L4 sum
+    RNS_TRY(rns_rx_verify_pool_dev(d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
+                                   local_ipv4, local_ipv6, d_status, d_l4_sum, stream));
+    UdpArgs a{};
+    set_pool_rx(a.rx, d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, d_status);
+    a.port_tbl = d_port_tbl;
+    a.data = d_data;
+    a.data_bytes = data_bytes;
+    a.rec_out = reinterpret_cast<uint4 *>(d_rec);
+    a.q_first = d_q_first;
+    a.count = d_count;
+    a.udp = d_udp;
+    a.pos = d_pos;
+    a.n_socks = n_socks;
+    a.n_tiles = static_cast<uint32_t>(udp_tiles(n_pkts));
+    a.rec_cap = rec_cap;
+    const uint64_t m = static_cast<uint64_t>(n_socks) * a.n_tiles;
+    a.part = static_cast<uint2 *>(d_work);
+    a.mat = a.part + scan_blocks(m) + 1;
+    a.rec = reinterpret_cast<uint32_t *>(a.mat + m);
+    return launch_rx_udp(a, chain_nt_from_arena(pool_bytes, n_frags, static_cast<double>(n_frags) / n_pkts),
+                         static_cast<hipStream_t>(stream));
+}
+
 int rns_rx_tcp_flow_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,
                                const rns_tcp_flow *d_flow_in, const uint32_t *d_pend_in, uint32_t pend_cap,
                                rns_tcp_flow *d_flow_out, uint32_t *d_pend_out, rns_rx_tcp_seg *d_seg,

@@ -1,6 +1,6 @@
 // What every translation unit sees of the entry points that are sequences of launches: their kernel
 // arguments, constants and workspace sizes.  Their kernels are no templates, so each family's header is
-// included by the one translation unit that launches it (k_flow.hip, k_plan.hip, k_echo.hip).
+// included by the one translation unit that launches it (k_flow.hip, k_plan.hip, k_echo.hip, k_udp.hip).
 // (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
 #pragma once
 
@@ -109,5 +109,38 @@ struct EchoArgs {
 
 // The workspace, 8-byte aligned: the two arrays of block sums, then the datagrams' dwords.
 inline uint64_t echo_work_bytes(uint64_t n_pkts) { return 16ull * (scan_blocks(n_pkts) + 1) + 4ull * n_pkts; }
+
+// --- the UDP receive demux (rns_k_udp.hpp) ---
+constexpr uint32_t kUdpMinLog2 = 7;  // 60 + 8 header bytes lie inside the first buffer
+// A tile is the datagrams of one workgroup: kUdpSteps 64-datagram blocks per wave.  Two keep the grid of
+// 2^20 datagrams at 8 workgroups per CU and the counts matrix of 1024 sockets at 16 MiB.
+constexpr uint32_t kUdpSteps = 2, kUdpWaves = kScanBlock / 64, kUdpTile = kScanBlock * kUdpSteps;
+// the workspace's dword per datagram: socket | payload bytes << 16
+constexpr uint32_t kUdpNoSock = RNS_UDP_NO_SOCK, kUdpNotDgram = 0xfffeu;  // both >= RNS_UDP_MAX_SOCKS
+static_assert(kUdpNotDgram >= RNS_UDP_MAX_SOCKS && kUdpNoSock >= RNS_UDP_MAX_SOCKS, "no socket index");
+
+struct UdpArgs {
+    PlaceArgs rx;  // the receive pool form (pool, pool_bytes, buf_idx, blk_first, len16, status, n, n_frags, blog)
+    const uint16_t *port_tbl;  // 65536 entries
+    uint8_t *data;             // 16-byte aligned
+    uint64_t data_bytes;
+    uint4 *rec_out;            // two per record
+    uint32_t *q_first, *count;
+    uint8_t *udp;
+    uint32_t *pos;             // optional
+    uint32_t *rec;             // workspace: a dword per datagram
+    uint2 *mat;                // workspace: (entries, units) of socket s in tile t at s * n_tiles + t
+    uint2 *part;               // workspace: the scan's block sums over the matrix, blocks + 1
+    uint32_t n_socks, n_tiles, rec_cap;
+};
+
+inline uint64_t udp_tiles(uint64_t n_pkts) { return (n_pkts + kUdpTile - 1) / kUdpTile; }
+// The workspace, 8-byte aligned pieces: the block sums of the M = n_socks * tiles matrix entries, the
+// matrix itself (8 B per entry), then the datagrams' dwords.  2^20 datagrams and 1024 sockets: 20 MiB.
+inline uint64_t udp_work_bytes(uint64_t n_pkts, uint64_t n_socks)
+{
+    const uint64_t m = n_socks * udp_tiles(n_pkts);
+    return 8ull * (scan_blocks(m) + 1) + 8ull * m + 4ull * n_pkts;
+}
 
 }  // namespace rns

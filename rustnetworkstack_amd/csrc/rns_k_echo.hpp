@@ -48,32 +48,11 @@ constexpr int kEchoPd = 7;
 constexpr uint32_t kEchoRecReq = 1u, kEchoRecV4 = 2u;
 constexpr int kEchoRecBufShift = 2, kEchoRecIhlShift = 12;  // payload buffers (<= 256), ip_hdr / 4 (<= 15)
 
-// A datagram's place in the pool form, as the verify and the placement compute it (whole wave).
-struct EchoLane {
-    uint64_t p, gi;
-    uint32_t T, nf;
-    bool live;
-};
-
-__device__ __forceinline__ EchoLane echo_lane(const PlaceArgs &a, uint32_t blk, uint32_t lane)
-{
-    EchoLane e;
-    e.p = static_cast<uint64_t>(blk) * 64 + lane;
-    e.live = e.p < a.n;
-    const uint32_t bmask = (1u << a.blog) - 1u;
-    e.T = e.live ? a.len16[e.p] : 0u;
-    e.nf = (e.T + bmask) >> a.blog;
-    const uint32_t inc = wave_incl_scan(e.nf);
-    const uint32_t first = static_cast<uint64_t>(blk) * 64 < a.n ? a.blk_first[blk] : 0u;  // wave-uniform
-    e.gi = static_cast<uint64_t>(first) + (inc - e.nf);
-    return e;
-}
-
 __global__ __launch_bounds__(kScanBlock) void echo_classify_kernel(const EchoArgs a)
 {
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t blk = blockIdx.x * kEchoWaves + (threadIdx.x >> 6);
-    const EchoLane e = echo_lane(a.rx, blk, lane);
+    const PoolLane e = pool_lane(a.rx, blk, lane);
     const uint32_t stv = e.live ? a.rx.status[e.p] : 0u;
     // accepted: the verify has found every fragment inside d_buf_idx and the pool; checked again for the
     // bytes read here and in the build, so that nothing depends on what d_status held before the call
@@ -176,7 +155,7 @@ __global__ __launch_bounds__(kScanBlock) void echo_build_kernel(const EchoArgs a
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     uint32_t(&pd)[kEchoPd][64] = pds[wv];
     const uint32_t blk = blockIdx.x * kEchoWaves + wv;
-    const EchoLane e = echo_lane(a.rx, blk, lane);
+    const PoolLane e = pool_lane(a.rx, blk, lane);
     const uint32_t rec = e.live ? a.rec[e.p] : 0u;
     const bool req = (rec & kEchoRecReq) != 0, v4 = (rec & kEchoRecV4) != 0;
     const uint32_t pbufs = (rec >> kEchoRecBufShift) & 0x3ffu, ip_hdr = ((rec >> kEchoRecIhlShift) & 0xfu) * 4u;

@@ -219,6 +219,28 @@ __device__ __forceinline__ void place_emit(const PlaceChunk &ck, const uint4 y)
     }
 }
 
+// A datagram's place in the pool form, as the verify and the placement compute it (whole wave).
+// (Shared by the echo responder and the UDP demux, rns_k_echo.hpp and rns_k_udp.hpp.)
+struct PoolLane {
+    uint64_t p, gi;
+    uint32_t T, nf;
+    bool live;
+};
+
+__device__ __forceinline__ PoolLane pool_lane(const PlaceArgs &a, uint32_t blk, uint32_t lane)
+{
+    PoolLane e;
+    e.p = static_cast<uint64_t>(blk) * 64 + lane;
+    e.live = e.p < a.n;
+    const uint32_t bmask = (1u << a.blog) - 1u;
+    e.T = e.live ? a.len16[e.p] : 0u;
+    e.nf = (e.T + bmask) >> a.blog;
+    const uint32_t inc = wave_incl_scan(e.nf);
+    const uint32_t first = static_cast<uint64_t>(blk) * 64 < a.n ? a.blk_first[blk] : 0u;  // wave-uniform
+    e.gi = static_cast<uint64_t>(first) + (inc - e.nf);
+    return e;
+}
+
 __device__ __forceinline__ uint32_t be32(uint32_t v) { return __builtin_bswap32(v); }
 
 template <bool NT>

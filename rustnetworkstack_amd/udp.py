@@ -1,0 +1,249 @@
+"""UDP receive demux: udp_input's socket queues built on the device.
+
+udp_input (udp.rs:126-148) reads a datagram's ports, looks the destination port up in PORT_MAP and
+pushes (source address, source port, payload) onto that socket's receive_queue; udp_recv
+(udp.rs:75-98) pops the queue front first.  ``rx_udp_demux_pool`` does the first half for a batch held
+in the pool form (``pool.rx_verify_pool``'s layout): every accepted UDP datagram to a bound port becomes
+a 32-byte record and a payload copied to a 16-byte-aligned place, the records and the payloads of a
+socket contiguous and in arrival order (rns_rx_udp_demux_pool_dev).  ``demux_host`` is the same function
+in numpy over a host pool — the host's path for the entries the device leaves (``RNS_UDP_NOROOM``) and
+what the GPU tests compare with — ``drain`` the list repeated udp_recv calls would return, and
+``udp_demux`` one receive -> device -> drain step.  The functions are re-exported by ``batch``, whose
+argument checks they use.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import _lib
+from .batch import (_I32, _U8, _U16, _call, _descriptors, _local_addrs, _nonnull, _per_packet, _require_cuda, _status,
+                    _work_bytes)
+from .icmp import _new, _verify_host
+from .pool import _buf_log2, recv_batch_pool
+
+REC = np.dtype([("ip", "u1", 16), ("src", "<u4"), ("off16", "<u4"), ("sport", "<u2"), ("len", "<u2"), ("family", "u1"),
+                ("flags", "u1"), ("pad", "u1", 2)])  # rns_udp_rec
+assert REC.itemsize == 32
+NO_POS = 0xFFFFFFFF
+
+
+class UdpDemux(NamedTuple):
+    """What a demux call leaves: torch tensors from ``rx_udp_demux_pool``, numpy arrays from ``demux_host``."""
+    status: object   # uint8 [n]: rx_verify_pool's
+    l4_sum: object   # uint16 [n] or None
+    udp: object      # uint8 [n]: RNS_UDP_* bits
+    pos: object      # uint32 [n]: the record's position, 0xffffffff if none
+    rec: object      # the records (REC on the host; uint8 [rec_cap * 32] on the device)
+    q_first: object  # uint32 [n_socks + 1]
+    count: object    # uint32 [2]: entries, 16-byte units
+    data: object     # uint8: the payloads
+
+
+def port_table(ports) -> np.ndarray:
+    """PORT_MAP as the demux's table (rns_rx_udp_port_table_build): uint16 [65536], ``ports[s]`` -> s, every
+    other entry RNS_UDP_NO_SOCK.  A duplicate port (udp_open's "Port already in use") or more than
+    RNS_UDP_MAX_SOCKS ports raise."""
+    p = np.ascontiguousarray(np.asarray(ports, dtype=np.int64).reshape(-1))
+    if p.size and (int(p.min()) < 0 or int(p.max()) > 0xFFFF):
+        raise ValueError("ports are u16")
+    p16 = p.astype(np.uint16)
+    tbl = np.empty(65536, dtype=np.uint16)
+    _lib.check(_lib.load().rns_rx_udp_port_table_build(p16.ctypes.data if p16.size else None, int(p16.size), tbl.ctypes.data),
+               "rns_rx_udp_port_table_build")
+    return tbl
+
+
+def demux_work(n_pkts: int, n_socks: int) -> int:
+    """Bytes of workspace ``rx_udp_demux_pool`` needs (rns_rx_udp_demux_work)."""
+    return _work_bytes("rns_rx_udp_demux_work", int(n_pkts), int(n_socks))
+
+
+def rx_udp_demux_pool(rx_pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: torch.Tensor, len16: torch.Tensor,
+                      local_ipv4: bytes, local_ipv6: bytes, port_tbl: torch.Tensor | None, n_socks: int, *,
+                      buf_bytes: int = 512, rec_cap: int | None = None, data: torch.Tensor | None = None,
+                      rec: torch.Tensor | None = None, status: torch.Tensor | None = None,
+                      l4_sum: torch.Tensor | None = None, udp: torch.Tensor | None = None, pos: torch.Tensor | None = None,
+                      q_first: torch.Tensor | None = None, count: torch.Tensor | None = None,
+                      work: torch.Tensor | None = None) -> UdpDemux:
+    """UDP receive demux over pool buffers (rns_rx_udp_demux_pool_dev).  ``rx_pool`` / ``buf_idx`` /
+    ``blk_first`` / ``len16`` as for ``rx_verify_pool`` (``buf_bytes`` a power of two in 128..32768);
+    ``port_tbl`` = ``port_table(ports)`` on the device as int16 / uint16 [65536] (None with ``n_socks`` 0).
+    Every accepted UDP datagram whose destination port maps to a socket s < ``n_socks`` becomes entry
+    ``pos[i]`` of the socket-major queues: ``rec`` (uint8, 32 bytes per record, ``REC``) and its payload at
+    ``data[16 * off16:]``; socket s owns records ``q_first[s]:q_first[s + 1]``.  ``rec_cap`` (default: one
+    per datagram) and ``data`` (default: one byte per pool-buffer byte in use, so nothing is cut) bound what
+    is written; entries past them get RNS_UDP_NOROOM.  Nothing is synchronised here.  Returns a
+    ``UdpDemux`` of device tensors (``udp`` uint8 [n], ``pos`` / ``q_first`` / ``count`` int32)."""
+    dev = _descriptors(rx_pool, ("buf_idx", buf_idx, _I32), ("blk_first", blk_first, _I32), ("len16", len16, _U16))
+    log2 = _buf_log2(buf_bytes, 128)
+    n, nf, n_socks = len16.numel(), buf_idx.numel(), int(n_socks)
+    if blk_first.numel() < (n + 63) // 64:
+        raise ValueError("blk_first needs one entry per 64 datagrams")
+    if n > _lib.RNS_CHAIN_MAX_PACKETS or (nf << log2) >= 2 ** 36:
+        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} datagrams and 2^36 bytes of buffers per demux call")
+    if not 0 <= n_socks <= _lib.RNS_UDP_MAX_SOCKS:
+        raise ValueError(f"n_socks must be at most {_lib.RNS_UDP_MAX_SOCKS}")
+    if rx_pool.data_ptr() & 15:
+        raise ValueError("the pool must start 16-byte aligned")
+    if n_socks:
+        _require_cuda(port_tbl, "port_tbl", _U16)
+        if port_tbl.numel() != 65536 or port_tbl.device != dev:
+            raise ValueError(f"port_tbl must have 65536 entries on {dev}")
+    cap = n if rec_cap is None else int(rec_cap)
+    if not 0 <= cap <= _lib.RNS_CHAIN_MAX_PACKETS:
+        raise ValueError("rec_cap must be a datagram count")
+    ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
+    if data is None:
+        data = torch.empty(max(nf << log2, 16), dtype=torch.uint8, device=dev)
+    rec = _new(rec, "rec", 32 * cap, torch.uint8, dev)
+    for name, t in (("data", data), ("rec", rec)):
+        _require_cuda(t, name, _U8)
+        if t.device != dev or t.data_ptr() & 15:
+            raise ValueError(f"{name} must be 16-byte aligned on {dev}")
+    status = _status(status, n, dev)
+    udp = _new(udp, "udp", n, torch.uint8, dev)
+    pos = _new(pos, "pos", n, torch.int32, dev)
+    q_first = _new(q_first, "q_first", n_socks + 1, torch.int32, dev)
+    count = _new(count, "count", 2, torch.int32, dev)
+    need = demux_work(n, n_socks)
+    if work is None:
+        work = torch.empty(-(-max(need, 16) // 8), dtype=torch.int64, device=dev)
+    _require_cuda(work, "work", (torch.int64,))
+    if work.numel() * 8 < need or work.device != dev or work.data_ptr() & 15:
+        raise ValueError(f"work needs {need} bytes (demux_work), 16-byte aligned, on {dev}")
+    ptr = _nonnull(dev)
+    _call("rns_rx_udp_demux_pool_dev", dev, rx_pool.data_ptr(), rx_pool.numel(), log2, buf_idx.data_ptr(), nf,
+          ptr(blk_first), ptr(len16), n, ip4, ip6, port_tbl.data_ptr() if n_socks else None, n_socks,
+          data.data_ptr(), data.numel(), rec.data_ptr(), cap, q_first.data_ptr(), count.data_ptr(), ptr(status),
+          _per_packet(l4_sum, "l4_sum", n, dev), ptr(udp), ptr(pos), work.data_ptr(), work.numel() * 8)
+    return UdpDemux(status, l4_sum, udp, pos, rec, q_first, count, data)
+
+
+# ---------------------------------------------------------------------------
+# the same on the host
+# ---------------------------------------------------------------------------
+def demux_host(rx_pool: np.ndarray, buf_idx, blk_first, len16, local_ipv4: bytes, local_ipv6: bytes, port_tbl, n_socks: int,
+               *, buf_bytes: int = 512, rec_cap: int | None = None, data: np.ndarray | None = None,
+               rec: np.ndarray | None = None) -> UdpDemux:
+    """``rx_udp_demux_pool`` in numpy over a host pool (uint8 array): the same decode, lookup, queue order,
+    cut, records and payload bytes — the host's path for the entries the device leaves with
+    RNS_UDP_NOROOM, and what the GPU tests compare with.  ``data`` (uint8) and ``rec`` (``REC``) are written
+    in place where given (``rec_cap`` defaults to ``len(rec)``, else to one per datagram); the bytes after a
+    payload's end up to the next 16-byte boundary stay as they were.  Returns a ``UdpDemux`` of numpy
+    arrays."""
+    B = int(buf_bytes)
+    log2 = _buf_log2(B, 128)
+    ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
+    buf_idx = np.asarray(buf_idx, dtype=np.uint32).astype(np.int64)
+    blk_first = np.asarray(blk_first, dtype=np.uint32).astype(np.int64)
+    len16 = np.asarray(len16, dtype=np.uint16).astype(np.int64)
+    n, n_frags, n_socks = len(len16), len(buf_idx), int(n_socks)
+    if not 0 <= n_socks <= _lib.RNS_UDP_MAX_SOCKS:
+        raise ValueError(f"n_socks must be at most {_lib.RNS_UDP_MAX_SOCKS}")
+    tbl = np.asarray(port_tbl, dtype=np.uint16) if n_socks else None
+    cap = (n if rec is None else len(rec)) if rec_cap is None else int(rec_cap)
+    if data is None:
+        data = np.zeros(max(n_frags << log2, 16), dtype=np.uint8)
+    if rec is None:
+        rec = np.zeros(cap, dtype=REC)
+    status, l4_sum, udp = np.zeros(n, np.uint8), np.zeros(n, np.uint16), np.zeros(n, np.uint8)
+    pos = np.full(n, NO_POS, dtype=np.uint32)
+    nfr = -(-len16 // B)
+    entries = []  # (socket, datagram, source address, source port, family, payload)
+    for i in range(n):
+        T, nf = int(len16[i]), int(nfr[i])
+        gi = int(blk_first[i // 64]) + int(nfr[64 * (i // 64):i].sum())
+        d, ok = b"", nf != 0 and gi + nf <= n_frags
+        if ok:
+            frags = []
+            for j in range(nf):
+                at, ln = int(buf_idx[gi + j]) << log2, min(B, T - j * B)
+                ok = ok and at + ln <= rx_pool.size
+                frags.append(rx_pool[at:at + ln].tobytes())
+            d = b"".join(frags)
+        if not ok:
+            status[i] = _lib.RNS_RX_MALFORMED
+            continue
+        st, l4, h, v6 = _verify_host(d, min(T, B), ip4, ip6)
+        status[i], l4_sum[i] = st, l4
+        if not (st & _lib.RNS_RX_ACCEPT) or (d[6] if v6 else d[9]) != 17 or T - h < 8:
+            continue
+        udp[i] = _lib.RNS_UDP_DGRAM
+        dport = (d[h + 2] << 8) | d[h + 3]
+        s = int(tbl[dport]) if n_socks else _lib.RNS_UDP_NO_SOCK
+        if s >= n_socks:
+            continue  # "No socket listening"
+        udp[i] |= _lib.RNS_UDP_SOCK
+        entries.append((s, i, d[8:24] if v6 else d[12:16] + bytes(12), (d[h] << 8) | d[h + 1], 6 if v6 else 4, d[h + 8:]))
+    # socket-major, arrival order within a socket: a stable sort by socket
+    entries.sort(key=lambda e: e[0])
+    q_first = np.zeros(n_socks + 1, dtype=np.uint32)
+    off = 0
+    for k, (s, i, ip, sport, fam, pay) in enumerate(entries):
+        q_first[s + 1:] += 1
+        units = -(-len(pay) // 16)
+        if k < cap and 16 * (off + units) <= data.size:
+            udp[i] |= _lib.RNS_UDP_QUEUED
+            pos[i] = k
+            rec[k] = (np.frombuffer(ip, dtype=np.uint8), i, off, sport, len(pay), fam, udp[i], (0, 0))
+            data[16 * off:16 * off + len(pay)] = np.frombuffer(pay, dtype=np.uint8)
+        else:
+            udp[i] |= _lib.RNS_UDP_NOROOM
+        off += units
+    return UdpDemux(status, l4_sum, udp, pos, rec, q_first, np.array([len(entries), off], dtype=np.uint32), data)
+
+
+def _np(t, dtype):
+    if isinstance(t, torch.Tensor):
+        t = t.cpu().numpy()
+    return np.ascontiguousarray(t).reshape(-1).view(dtype)
+
+
+def drain(result: UdpDemux, s: int):
+    """What repeated udp_recv calls on socket ``s`` would return after the batch, front first: a list of
+    ``(source address bytes (4 or 16), source port, payload bytes)``.  Entries the cut left out
+    (RNS_UDP_NOROOM: no record) end the list: they are the host's to queue, behind these."""
+    q = _np(result.q_first, np.uint32)
+    cnt = _np(result.count, np.uint32)
+    rec, data = _np(result.rec, np.uint8), _np(result.data, np.uint8)
+    pos = np.sort(_np(result.pos, np.uint32))
+    out = []
+    for k in range(int(q[s]), int(q[s + 1])):
+        if k * 32 + 32 > rec.size or k >= int(cnt[0]) or pos[np.searchsorted(pos, k) % pos.size] != k:
+            break  # cut: its record was not written
+        r = rec[32 * k:32 * k + 32].view(REC)[0]
+        at = 16 * int(r["off16"])
+        out.append((r["ip"][:4 if r["family"] == 4 else 16].tobytes(), int(r["sport"]), data[at:at + int(r["len"])].tobytes()))
+    return out
+
+
+def udp_demux(fd: int, pool: np.ndarray, free: np.ndarray, ports, local_ipv4: bytes, local_ipv6: bytes, *,
+              buf_bytes: int = 512, mru: int = 2048, max_pkts: int | None = None, device: str = "cuda:0",
+              timeout_ms: int = 0):
+    """One receive -> device -> drain step: ``recv_batch_pool`` from ``fd`` into the host ``pool``, the used
+    buffers to the device, ``rx_udp_demux_pool`` over the table of ``ports``, the result read back.  Returns
+    ``(datagrams received, UdpDemux of numpy arrays)``; ``drain(result, s)`` is then socket s's queue."""
+    B = int(buf_bytes)
+    ports = list(ports)
+    n, len16, blk_first, nf = recv_batch_pool(fd, pool, free, B, mru, max_pkts, timeout_ms)
+    if n == 0:
+        z = np.zeros(0, np.uint8)
+        return 0, UdpDemux(z, np.zeros(0, np.uint16), z, np.zeros(0, np.uint32), np.zeros(0, REC),
+                           np.zeros(len(ports) + 1, np.uint32), np.zeros(2, np.uint32), z)
+    dev = torch.device(device)
+    rows = pool.reshape(-1, B)
+    used = torch.from_numpy(free[:nf].astype(np.int64))
+    d_rx = torch.zeros(rows.shape, dtype=torch.uint8, device=dev)
+    d_rx[used.to(dev)] = torch.from_numpy(rows[free[:nf]]).to(dev)  # the received buffers only
+    to_dev = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).to(dev)  # noqa: E731
+    r = rx_udp_demux_pool(d_rx.reshape(-1), to_dev(free[:nf].astype(np.uint32), np.int32),
+                          to_dev(blk_first.astype(np.uint32), np.int32), to_dev(len16, np.int16), local_ipv4, local_ipv6,
+                          to_dev(port_table(ports), np.int16) if ports else None, len(ports), buf_bytes=B)
+    cnt = _np(r.count, np.uint32)  # the one synchronisation the host needs first: 8 bytes
+    nrec, nunits = int(cnt[0]), int(cnt[1])
+    return n, UdpDemux(_np(r.status, np.uint8), None, _np(r.udp, np.uint8)[:n], _np(r.pos, np.uint32)[:n],
+                       _np(r.rec[:32 * nrec], np.uint8).view(REC), _np(r.q_first, np.uint32), cnt,
+                       _np(r.data[:16 * nunits], np.uint8))

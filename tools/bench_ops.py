@@ -72,6 +72,14 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              alone, (c) the pool verify and then rns_tx_fill_pool_dev over prebuilt replies of the same
              shapes — the floor that copies nothing; the replies of (a) are compared with echo_host on a
              sample before timing.  Timed once per run, whatever --configs names
+* rx_udp   — rns_rx_udp_demux_pool_dev: 2^20 UDP datagrams of 1500 bytes over 1024 sockets, 2^20 of 64 bytes
+             to one socket, and 2^23 IMIX-sized ones (workloads.imix_lengths) over 16 sockets, IPv4 in 512-byte
+             buffers, the sockets interleaved.  Timed in alternating rounds: (a) the demux, (b) the pool verify
+             alone, (c) rns_rx_tcp_place_pool_dev over RxPlaceBatch's TCP segments of the same datagram sizes
+             (1500: 1460 payload bytes against the demux's 1472; none for the 64-byte shape) — the nearest
+             existing copy; the queues of (a) are checked on the device before timing: d_q_first against the
+             sockets' counts, and every record and payload of a sample.  Timed once per run, whatever
+             --configs names
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -165,6 +173,8 @@ def main():
     ap.add_argument("--place-flows", type=int, default=1024, help="rx_place: flows (a divisor of the datagram count)")
     ap.add_argument("--echo-shapes", default="ping84,ping1500,imix", help="rx_echo: the shapes to time")
     ap.add_argument("--echo-n", type=int, default=0, help="rx_echo: datagrams per shape (0 = 2^20 pings, 2^23 imix)")
+    ap.add_argument("--udp-shapes", default="udp1500:1024,udp64:1,imix:16", help="rx_udp: shape:sockets to time")
+    ap.add_argument("--udp-n", type=int, default=0, help="rx_udp: datagrams per shape (0 = 2^20, 2^23 imix)")
     ap.add_argument("--tx-modes", default="plain,runs,txpacked", help="chain_fill: hint flags to time")
     args = ap.parse_args()
     ops = set(args.ops.split(","))
@@ -219,6 +229,10 @@ def main():
         if "rx_echo" in ops and cfg == args.configs.split(",")[0]:
             for shape in args.echo_shapes.split(","):
                 r.update(bench_rx_echo(shape, dev, args))
+        if "rx_udp" in ops and cfg == args.configs.split(",")[0]:
+            for spec in args.udp_shapes.split(","):
+                shape, socks = spec.split(":")
+                r.update(bench_rx_udp(shape, int(socks), dev, args))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -1039,6 +1053,117 @@ def bench_rx_echo(shape, dev, args, B=512):
     del pool, tx
     torch.cuda.empty_cache()
     return {f"rx_echo_{shape}": row}
+
+
+def _udp_batch(shape, n, n_socks, dev, B=512):
+    """n UDP datagrams from 192.168.1.1 to L4 in a pool of B-byte buffers, built on the device: all of one
+    length (udp1500, udp64) or IMIX lengths; datagram i goes to socket (7919 i) mod n_socks, whose port is
+    1024 + 3 s, and lies in consecutive buffers from i * stride on, zeros after its end.  (pool, buf_idx,
+    blk_first, len16 as device tensors; the lengths, the sockets and the ports as numpy.)"""
+    from rustnetworkstack_amd.batch import rx_pool_layout
+    from rustnetworkstack_amd.workloads import DATA_SEED, imix_lengths
+    i = np.arange(n)
+    T = imix_lengths(n, DATA_SEED).astype(np.int64) if shape == "imix" else np.full(n, int(shape[3:]), dtype=np.int64)
+    sock = (i * 7919) % n_socks
+    ports = 1024 + 3 * np.arange(n_socks)
+    stride = int(-(-int(T.max()) // B))
+    W = stride * B
+    blk, first, nf = rx_pool_layout(T, B)
+    nfr = -(-T // B)
+    idx = (np.repeat(i * stride, nfr) + (np.arange(nf) - np.repeat(first[:-1].astype(np.int64), nfr))).astype(np.uint32)
+    pool = torch.zeros(n * W, dtype=torch.uint8, device=dev)
+    rows = pool.view(n, W)
+    Tt = torch.from_numpy(T).to(dev)
+    col = torch.arange(W, device=dev)
+    for lo in range(0, n, 1 << 18):  # the payloads: random bytes inside the datagram, zeros after it
+        hi = min(n, lo + (1 << 18))
+        rnd = torch.randint(0, 256, (hi - lo, W), dtype=torch.uint8, device=dev)
+        rows[lo:hi] = rnd * (col[None, :] < Tt[lo:hi, None]).to(torch.uint8)
+        del rnd
+    dport = torch.from_numpy(ports[sock]).to(dev)
+    hdr = torch.zeros((n, 28), dtype=torch.uint8, device=dev)
+    hdr[:, 0], hdr[:, 8], hdr[:, 9] = 0x45, 64, 17
+    hdr[:, 2], hdr[:, 3] = (Tt >> 8).to(torch.uint8), (Tt & 255).to(torch.uint8)
+    hdr[:, 12:16] = torch.tensor([192, 168, 1, 1], dtype=torch.uint8, device=dev)
+    hdr[:, 16:20] = torch.tensor(list(L4), dtype=torch.uint8, device=dev)
+    ck = 0xFFFF ^ _be_words(hdr[:, :20])
+    hdr[:, 10], hdr[:, 11] = (ck >> 8).to(torch.uint8), (ck & 255).to(torch.uint8)
+    hdr[:, 20], hdr[:, 21] = 0x9C, 0x40  # source port 40000
+    hdr[:, 22], hdr[:, 23] = (dport >> 8).to(torch.uint8), (dport & 255).to(torch.uint8)
+    hdr[:, 24], hdr[:, 25] = ((Tt - 20) >> 8).to(torch.uint8), ((Tt - 20) & 255).to(torch.uint8)
+    rows[:, :28] = hdr
+    dv = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).to(dev)  # noqa: E731
+    return pool, dv(idx, np.int32), dv(blk, np.int32), dv(T.astype(np.uint16), np.int16), T, sock, ports, nf
+
+
+def bench_rx_udp(shape, n_socks, dev, args, B=512):
+    """rns_rx_udp_demux_pool_dev against the pool verify alone and against the TCP placement of RxPlaceBatch's
+    segments of the same datagram sizes, in alternating rounds."""
+    from rustnetworkstack_amd.batch import demux_work, port_table, rx_tcp_place_pool, rx_udp_demux_pool, rx_verify_pool
+    from rustnetworkstack_amd.workloads import LOCAL4, LOCAL6
+    n = args.udp_n or (1 << 23 if shape == "imix" else 1 << 20)
+    pool, idx, blk, len16, T, sock, ports, nf = _udp_batch(shape, n, n_socks, dev, B)
+    pay = T - 28
+    units = -(-pay // 16)
+    tbl = torch.from_numpy(port_table(ports).view(np.int16)).to(dev)
+    keep = dict(status=torch.empty(n, dtype=torch.uint8, device=dev), udp=torch.empty(n, dtype=torch.uint8, device=dev),
+                pos=torch.empty(n, dtype=torch.int32, device=dev), rec=torch.empty(32 * n, dtype=torch.uint8, device=dev),
+                data=torch.empty(16 * int(units.sum()) + 16, dtype=torch.uint8, device=dev),
+                q_first=torch.empty(n_socks + 1, dtype=torch.int32, device=dev), count=torch.empty(2, dtype=torch.int32, device=dev),
+                work=torch.empty((demux_work(n, n_socks) + 15) // 8, dtype=torch.int64, device=dev))
+
+    def demux():
+        rx_udp_demux_pool(pool, idx, blk, len16, L4, L6, tbl, n_socks, buf_bytes=B, **keep)
+
+    demux()
+    torch.cuda.synchronize()
+    cnt = keep["count"].cpu().numpy().view(np.uint32)
+    assert cnt.tolist() == [n, int(units.sum())], cnt
+    assert int((keep["udp"] == 7).sum().item()) == n
+    qf = np.concatenate([[0], np.cumsum(np.bincount(sock, minlength=n_socks))])
+    assert np.array_equal(keep["q_first"].cpu().numpy().view(np.uint32), qf)
+    # a sample against the pool: the record's fields and the payload, byte for byte
+    W = pool.numel() // n
+    posh = keep["pos"].cpu().numpy().view(np.uint32)
+    for i in np.random.default_rng(16).choice(n, 256, replace=False).tolist():
+        k = int(posh[i])
+        r = keep["rec"][32 * k:32 * k + 32].cpu().numpy()
+        src, off16, sport, ln = (int(r[16:20].view(np.uint32)[0]), int(r[20:24].view(np.uint32)[0]), int(r[24:26].view(np.uint16)[0]),
+                                 int(r[26:28].view(np.uint16)[0]))
+        assert qf[sock[i]] <= k < qf[sock[i] + 1] and (src, sport, ln, r[28], r[29]) == (i, 40000, int(pay[i]), 4, 7)
+        assert bytes(r[:16]) == bytes([192, 168, 1, 1]) + bytes(12)
+        assert torch.equal(keep["data"][16 * off16:16 * off16 + ln], pool[i * W + 28:i * W + 28 + ln])
+    st2 = torch.empty(n, dtype=torch.uint8, device=dev)
+
+    def verify():
+        rx_verify_pool(pool, idx, blk, len16, L4, L6, buf_bytes=B, status=st2)
+
+    verify()
+    torch.cuda.synchronize()
+    assert torch.equal(st2, keep["status"])
+    fns, names, rb = [demux, verify], ["demux", "verify"], None
+    if shape != "udp64":
+        rb = RxPlaceBatch("bulk" if shape == "udp1500" else "imix", dev, n, 1024, False)
+        fns.append(lambda: rx_tcp_place_pool(rb.pool, rb.d_buf_idx, rb.d_blk_first, rb.d_len16, LOCAL4, LOCAL6, rb.d_table,
+                                             rb.d_next_seq, rb.d_win_off, rb.d_win_len, rb.stream, status=rb.status,
+                                             l4_sum=rb.l4_sum, meta=rb.meta))
+        names.append("place")
+    rs = timed_rounds(fns, args.steps, args.rounds)
+    med = [r[len(r) // 2] for r in rs]
+    rx_bytes, pay_bytes = int(T.sum()), int(pay.sum())
+    row = {"datagrams": n, "sockets": n_socks, "fragments": nf, "rx_bytes": rx_bytes, "payload_bytes": pay_bytes,
+           "work_bytes": demux_work(n, n_socks), "demux_us": round(med[0] * 1e3, 1), "verify_us": round(med[1] * 1e3, 1),
+           "demux_over_verify": round(med[0] / med[1], 3),
+           "added_us_per_copied_GB": round((med[0] - med[1]) * 1e3 / max(pay_bytes / 1e9, 1e-9), 1),
+           "demux_GBps_rx_plus_copied": round((rx_bytes + 2 * pay_bytes) / med[0] / 1e6, 1),
+           "rounds_us": {k: [round(x * 1e3, 1) for x in r] for k, r in zip(names, rs)}}
+    if rb is not None:
+        row.update({"place_us": round(med[2] * 1e3, 1), "place_payload_bytes": rb.pay_total,
+                    "demux_over_place": round(med[0] / med[2], 3),
+                    "place_added_us_per_copied_GB": round((med[2] - med[1]) * 1e3 / max(rb.pay_total / 1e9, 1e-9), 1)})
+    del pool, keep, rb
+    torch.cuda.empty_cache()
+    return {f"rx_udp_{shape}_{n_socks}": row}
 
 
 def bench_chain_netbuf(lay, dev, args, shuffled=False, runs=False):
