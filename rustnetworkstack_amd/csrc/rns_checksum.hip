@@ -222,19 +222,27 @@ dim3 stash_grid(uint64_t n, uint64_t arena_bytes, bool tiny_cap)
 
 bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
-// The pool-receive part of PlaceArgs: the placement's and the echo responder's view of a verified batch.
-void set_pool_rx(PlaceArgs &p, const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2, const uint32_t *d_buf_idx,
-                 uint32_t n_frags, const uint32_t *d_blk_first, const uint16_t *d_len16, uint32_t n_pkts, uint8_t *d_status)
+// The pool receive form's arguments, as the verify and its consumers take them (buffers of 2^min_log2 bytes or more).
+bool pool_rx_valid(const uint8_t *d_pool, uint32_t buf_log2, uint32_t min_log2, const uint32_t *d_buf_idx, uint32_t n_frags,
+                   const uint32_t *d_blk_first, const uint16_t *d_len16, uint32_t n_pkts, const uint8_t *local_ipv4,
+                   const uint8_t *local_ipv6, const uint8_t *d_status)
 {
-    p.pool = d_pool;
-    p.pool_bytes = pool_bytes;
-    p.buf_idx = d_buf_idx;
-    p.blk_first = d_blk_first;
-    p.len16 = d_len16;
-    p.status = d_status;
-    p.n = n_pkts;
-    p.n_frags = n_frags;
-    p.blog = buf_log2;
+    return d_pool && buf_log2 >= min_log2 && buf_log2 <= kPoolMaxLog2 && d_blk_first && d_len16 && (!n_frags || d_buf_idx) &&
+           n_pkts <= RNS_CHAIN_MAX_PACKETS && !misaligned(d_pool, 15) && rx_valid(d_status, local_ipv4, local_ipv6);
+}
+
+// A consumer's first step: the verify as it is (its kernel, its status and L4 sum), then the view of the
+// verified batch and the load form for the consumer's kernels, picked as the verify picks its own.
+int pool_rx_verify(PoolRx &rx, bool &nt, const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2,
+                   const uint32_t *d_buf_idx, uint32_t n_frags, const uint32_t *d_blk_first, const uint16_t *d_len16,
+                   uint32_t n_pkts, const uint8_t *local_ipv4, const uint8_t *local_ipv6, uint8_t *d_status, uint16_t *d_l4_sum,
+                   void *stream)
+{
+    RNS_TRY(rns_rx_verify_pool_dev(d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, local_ipv4,
+                                   local_ipv6, d_status, d_l4_sum, stream));
+    rx = PoolRx{d_pool, pool_bytes, d_buf_idx, d_blk_first, d_len16, d_status, n_pkts, n_frags, buf_log2};
+    nt = chain_nt_from_arena(pool_bytes, n_frags, static_cast<double>(n_frags) / n_pkts);
+    return RNS_OK;
 }
 
 }  // namespace
@@ -424,9 +432,8 @@ int rns_rx_verify_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t 
                            void *stream)
 {
     return entry(n_pkts,
-                 buf_log2 >= kPoolMinLog2 && buf_log2 <= kPoolMaxLog2 && d_blk_first && d_len16 &&
-                     (!n_frags || d_buf_idx) && n_pkts <= RNS_CHAIN_MAX_PACKETS &&
-                     (reinterpret_cast<uintptr_t>(d_pool) & 15) == 0 && rx_valid(d_status, local_ipv4, local_ipv6),
+                 pool_rx_valid(d_pool, buf_log2, kPoolMinLog2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, local_ipv4,
+                               local_ipv6, d_status),
                  d_pool, pool_bytes, RNS_FLAG_COMPLEMENT, stream, [&](CsumArgs &a, hipStream_t st) {
                      // the compact descriptors in CsumArgs: off32 = buffer indices, first = d_blk_first,
                      // len16 = datagram lengths, align_mask = buffer bytes - 1 (rns_k_pool_rx.hpp)
@@ -453,25 +460,20 @@ int rns_rx_tcp_place_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
     if (n_pkts == 0)
         return RNS_OK;
     const uint64_t slots = flow_slots(n_flows);
-    if (buf_log2 < kPlaceMinLog2 || !d_meta || misaligned(d_meta, 3) || !d_next_seq || !d_win_off || !d_win_len ||
-        !d_stream || (n_flows && (!d_tbl || misaligned(d_tbl, 3) || tbl_bytes < slots * kFlowSlotBytes)))
+    // every rejection of the verify's and this entry's own, before the device is touched
+    if (!pool_rx_valid(d_pool, buf_log2, kPlaceMinLog2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, local_ipv4,
+                       local_ipv6, d_status) ||
+        !d_meta || misaligned(d_meta, 3) || !d_next_seq || !d_win_off || !d_win_len || !d_stream ||
+        (n_flows && (!d_tbl || misaligned(d_tbl, 3) || tbl_bytes < slots * kFlowSlotBytes)))
         return RNS_E_INVALID;
-    // the verify as it is: its rejections, its kernel, its status and L4 sum
-    RNS_TRY(rns_rx_verify_pool_dev(d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
-                                   local_ipv4, local_ipv6, d_status, d_l4_sum, stream));
-    PlaceArgs p{};
-    set_pool_rx(p, d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, d_status);
-    p.tbl = reinterpret_cast<const uint32_t *>(d_tbl);
-    p.next_seq = d_next_seq;
-    p.win_off = d_win_off;
-    p.win_len = d_win_len;
-    p.stream = d_stream;
-    p.stream_bytes = stream_bytes;
-    p.meta = reinterpret_cast<uint32_t *>(d_meta);
-    p.n_flows = n_flows;
-    p.slots = static_cast<uint32_t>(slots);
-    return launch_rx_place(p, chain_nt_from_arena(pool_bytes, n_frags, static_cast<double>(n_frags) / n_pkts),
-                           static_cast<hipStream_t>(stream));
+    PoolRx rx;
+    bool nt;
+    RNS_TRY(pool_rx_verify(rx, nt, d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
+                           local_ipv4, local_ipv6, d_status, d_l4_sum, stream));
+    const PlaceArgs p{rx.pool, rx.pool_bytes, rx.buf_idx, rx.blk_first, rx.len16, rx.status,  // the view, flat
+                      reinterpret_cast<const uint32_t *>(d_tbl), d_next_seq, d_win_off, d_win_len, d_stream, stream_bytes,
+                      reinterpret_cast<uint32_t *>(d_meta), rx.n, rx.n_frags, n_flows, static_cast<uint32_t>(slots), rx.blog};
+    return launch_rx_place(p, nt, static_cast<hipStream_t>(stream));
 }
 
 int rns_rx_icmp_echo_pool_dev(const uint8_t *d_rx_pool, uint64_t rx_pool_bytes, uint32_t buf_log2,
@@ -490,19 +492,18 @@ int rns_rx_icmp_echo_pool_dev(const uint8_t *d_rx_pool, uint64_t rx_pool_bytes, 
         return hip_status(hipMemsetAsync(d_count, 0, 12, static_cast<hipStream_t>(stream)));
     }
     // every rejection of the verify's and this entry's own, before the device is touched
-    if (buf_log2 < kEchoMinLog2 || buf_log2 > kPoolMaxLog2 || n_pkts > RNS_CHAIN_MAX_PACKETS || !d_rx_pool || !d_blk_first ||
-        !d_len16 || (n_frags && !d_buf_idx) || !rx_valid(d_status, local_ipv4, local_ipv6) || !d_tx_pool || !d_count ||
-        !d_echo || !d_work || (n_free && !d_free) ||
-        (reply_cap && (!d_tx_blk_first || !d_tx_head_len8 || !d_tx_pay_len16)) || misaligned(d_rx_pool, 15) ||
-        misaligned(d_tx_pool, 15) || misaligned(d_free, 3) || misaligned(d_ip_id_add, 3) || misaligned(d_tx_blk_first, 3) ||
+    if (!pool_rx_valid(d_rx_pool, buf_log2, kEchoMinLog2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, local_ipv4,
+                       local_ipv6, d_status) ||
+        !d_tx_pool || !d_count || !d_echo || !d_work || (n_free && !d_free) ||
+        (reply_cap && (!d_tx_blk_first || !d_tx_head_len8 || !d_tx_pay_len16)) || misaligned(d_tx_pool, 15) ||
+        misaligned(d_free, 3) || misaligned(d_ip_id_add, 3) || misaligned(d_tx_blk_first, 3) ||
         misaligned(d_tx_pay_len16, 1) || misaligned(d_tx_src, 3) || misaligned(d_count, 3) || misaligned(d_work, 7) ||
         work_bytes < echo_work_bytes(n_pkts))
         return RNS_E_INVALID;
-    // the verify as it is: its kernel, its status and L4 sum
-    RNS_TRY(rns_rx_verify_pool_dev(d_rx_pool, rx_pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
-                                   local_ipv4, local_ipv6, d_status, d_l4_sum, stream));
     EchoArgs a{};
-    set_pool_rx(a.rx, d_rx_pool, rx_pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, d_status);
+    bool nt;
+    RNS_TRY(pool_rx_verify(a.rx, nt, d_rx_pool, rx_pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
+                           local_ipv4, local_ipv6, d_status, d_l4_sum, stream));
     a.tx_pool = d_tx_pool;
     a.tx_bufs = tx_pool_bytes >> buf_log2;
     a.free = d_free;
@@ -521,8 +522,7 @@ int rns_rx_icmp_echo_pool_dev(const uint8_t *d_rx_pool, uint64_t rx_pool_bytes, 
     a.n_free = n_free;
     a.reply_cap = reply_cap;
     a.ip_id_base = ip_id_base;
-    return launch_rx_echo(a, chain_nt_from_arena(rx_pool_bytes, n_frags, static_cast<double>(n_frags) / n_pkts),
-                          static_cast<hipStream_t>(stream));
+    return launch_rx_echo(a, nt, static_cast<hipStream_t>(stream));
 }
 
 int rns_rx_udp_demux_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2, const uint32_t *d_buf_idx,
@@ -541,18 +541,17 @@ int rns_rx_udp_demux_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
         return hip_status(hipMemsetAsync(d_q_first, 0, 4ull * (n_socks + 1), static_cast<hipStream_t>(stream)));
     }
     // every rejection of the verify's and this entry's own, before the device is touched
-    if (buf_log2 < kUdpMinLog2 || buf_log2 > kPoolMaxLog2 || n_pkts > RNS_CHAIN_MAX_PACKETS || !d_pool || !d_blk_first ||
-        !d_len16 || (n_frags && !d_buf_idx) || !rx_valid(d_status, local_ipv4, local_ipv6) || !d_udp || !d_work ||
-        (n_socks && !d_port_tbl) || (data_bytes && !d_data) || (rec_cap && !d_rec) || misaligned(d_pool, 15) ||
+    if (!pool_rx_valid(d_pool, buf_log2, kUdpMinLog2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, local_ipv4, local_ipv6,
+                       d_status) ||
+        !d_udp || !d_work || (n_socks && !d_port_tbl) || (data_bytes && !d_data) || (rec_cap && !d_rec) ||
         misaligned(d_data, 15) || misaligned(d_rec, 15) || misaligned(d_work, 15) || misaligned(d_port_tbl, 1) ||
         misaligned(d_pos, 3) || work_bytes < udp_work_bytes(n_pkts, n_socks) ||
         (static_cast<uint64_t>(n_frags) << buf_log2) >= (1ull << 36))
         return RNS_E_INVALID;
-    // the verify as it is: its kernel, its status and L4 sum
-    RNS_TRY(rns_rx_verify_pool_dev(d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
-                                   local_ipv4, local_ipv6, d_status, d_l4_sum, stream));
     UdpArgs a{};
-    set_pool_rx(a.rx, d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, d_status);
+    bool nt;
+    RNS_TRY(pool_rx_verify(a.rx, nt, d_pool, pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, local_ipv4,
+                           local_ipv6, d_status, d_l4_sum, stream));
     a.port_tbl = d_port_tbl;
     a.data = d_data;
     a.data_bytes = data_bytes;
@@ -568,8 +567,7 @@ int rns_rx_udp_demux_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
     a.part = static_cast<uint2 *>(d_work);
     a.mat = a.part + scan_blocks(m) + 1;
     a.rec = reinterpret_cast<uint32_t *>(a.mat + m);
-    return launch_rx_udp(a, chain_nt_from_arena(pool_bytes, n_frags, static_cast<double>(n_frags) / n_pkts),
-                         static_cast<hipStream_t>(stream));
+    return launch_rx_udp(a, nt, static_cast<hipStream_t>(stream));
 }
 
 int rns_rx_tcp_flow_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,

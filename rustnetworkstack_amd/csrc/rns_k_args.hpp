@@ -88,7 +88,7 @@ inline uint64_t plan_work_bytes(uint64_t n_flows) { return 8ull * (scan_blocks(2
 constexpr uint32_t kEchoMinLog2 = 8;  // the transmit pool form's: a head fits its buffer
 
 struct EchoArgs {
-    PlaceArgs rx;  // the receive pool form (pool, pool_bytes, buf_idx, blk_first, len16, status, n, n_frags, blog)
+    PoolRx rx;
     uint8_t *tx_pool;
     uint64_t tx_bufs;  // whole buffers of the transmit pool
     const uint32_t *free;
@@ -120,7 +120,7 @@ constexpr uint32_t kUdpNoSock = RNS_UDP_NO_SOCK, kUdpNotDgram = 0xfffeu;  // bot
 static_assert(kUdpNotDgram >= RNS_UDP_MAX_SOCKS && kUdpNoSock >= RNS_UDP_MAX_SOCKS, "no socket index");
 
 struct UdpArgs {
-    PlaceArgs rx;  // the receive pool form (pool, pool_bytes, buf_idx, blk_first, len16, status, n, n_frags, blog)
+    PoolRx rx;
     const uint16_t *port_tbl;  // 65536 entries
     uint8_t *data;             // 16-byte aligned
     uint64_t data_bytes;

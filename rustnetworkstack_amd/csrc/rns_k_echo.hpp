@@ -24,9 +24,8 @@ namespace rns {
 //   3. echo_build_kernel     the same decomposition: scans its workgroup again, applies reply_cap
 //                            and the free list's length (both counts are monotone: the answered
 //                            requests are a prefix), then each wave walks the destination 16-byte
-//                            chunks of all its replies concatenated — the placement's walk
-//                            (place_owner / place_load / place_second / place_join), with the
-//                            destination in the reply's payload buffers, which start 16-byte aligned:
+//                            chunks of all its replies concatenated (pool_walk, rns_k_pool_view.hpp),
+//                            the destination in the reply's payload buffers, which start 16-byte aligned:
 //                            every chunk is one whole aligned store, a payload's last chunk with
 //                            zeros after its bytes (the reply's own buffer).  The chunks' little-endian
 //                            word sums are reduced per datagram across the lanes (a range of the wave's
@@ -39,10 +38,9 @@ namespace rns {
 // counts) or, when all are, the last request — into the zeroed d_count: no atomics.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kEchoWaves = kScanBlock / 64;
-constexpr int kEchoPd = 7;
-// Per answered request in the wave's LDS table: [0] the wave's destination chunks before it, [1] [2] its
-// first fragment's place in d_buf_idx, [3] ip_hdr + 4, [4] pay_len, [5] its first payload buffer's place
-// in d_free, [6] the little-endian word sum of its payload.
+// The wave's LDS table: pool_walk's rows, then an answered request's first payload buffer's place in d_free
+// and the little-endian word sum of its payload.
+constexpr int kEchoPd = kPdRows + 2, kEchoPdFree = kPdRows, kEchoPdSum = kPdRows + 1;
 
 // the workspace's dword per datagram
 constexpr uint32_t kEchoRecReq = 1u, kEchoRecV4 = 2u;
@@ -54,8 +52,7 @@ __global__ __launch_bounds__(kScanBlock) void echo_classify_kernel(const EchoArg
     const uint32_t blk = blockIdx.x * kEchoWaves + (threadIdx.x >> 6);
     const PoolLane e = pool_lane(a.rx, blk, lane);
     const uint32_t stv = e.live ? a.rx.status[e.p] : 0u;
-    // accepted: the verify has found every fragment inside d_buf_idx and the pool; checked again for the
-    // bytes read here and in the build, so that nothing depends on what d_status held before the call
+    // the first buffer's checks (rns_k_pool_view.hpp says why each read is safe), as this kernel's own lines
     bool ok = e.live && (stv & RNS_RX_ACCEPT) && e.nf != 0 && e.gi + e.nf <= a.rx.n_frags;
     uint32_t rec = 0;
     if (ok) {
@@ -65,11 +62,10 @@ __global__ __launch_bounds__(kScanBlock) void echo_classify_kernel(const EchoArg
         if (ok) {
             const uint32_t *h = reinterpret_cast<const uint32_t *>(a.rx.pool + s0);
             const uint32_t w0 = h[0];
-            const bool v6 = ((w0 >> 4) & 0xfu) == 6u;  // accepted: version 4 or 6
+            const bool v6 = ((w0 >> 4) & 0xfu) == 6u;
             const uint32_t ip_hdr = v6 ? 40u : (w0 & 0xfu) * 4u;
-            // accepted: T >= 16 (IPv4) or 40 (IPv6), so the protocol is the datagram's; the ICMP header's
-            // dword lies in the first buffer (ip_hdr + 4 <= 64 <= B) and inside the datagram
             const uint32_t proto = v6 ? (h[1] >> 16) & 0xffu : (h[2] >> 8) & 0xffu;
+            // the ICMP header's dword lies in the first buffer (ip_hdr + 4 <= 64 <= B) and inside the datagram
             if (ip_hdr + 4u <= e.T && proto == (v6 ? 58u : 1u) && (h[ip_hdr >> 2] & 0xffu) == (v6 ? 128u : 8u)) {
                 const uint32_t pay = e.T - ip_hdr - 4u;
                 rec = kEchoRecReq | (v6 ? 0u : kEchoRecV4) | (((pay + (1u << a.rx.blog) - 1u) >> a.rx.blog) << kEchoRecBufShift) |
@@ -89,43 +85,12 @@ __global__ __launch_bounds__(kScanBlock) void echo_classify_kernel(const EchoArg
     }
 }
 
-// Chunk v of the wave's concatenated destination chunks, its first load issued: place_fetch with the
-// destination in the reply's payload buffers (chunk c of a payload lies in buffer c >> (blog - 4)).
-template <bool NT>
-__device__ __forceinline__ PlaceChunk echo_fetch(const EchoArgs &a, const uint32_t (&pd)[kEchoPd][64], uint32_t v, uint32_t W,
-                                                 uint32_t &c)
-{
-    PlaceChunk ck{};
-    ck.j = ~0u;
-    c = 0;
-    if (v >= W)
-        return ck;
-    const uint32_t j = place_owner(pd, v);
-    c = v - pd[0][j];
-    const uint32_t skip = pd[3][j], plen = pd[4][j];
-    const uint64_t gi = (static_cast<uint64_t>(pd[2][j]) << 32) | pd[1][j];
-    const uint32_t o0 = skip + 16u * c;  // < skip + plen = T <= 65535
-    const uint32_t s = o0 & ~15u;
-    ck.sh = o0 & 15u;
-    ck.x = place_load<NT>(a.rx, gi, s);
-    ck.s2 = (ck.sh && s + 16u < skip + plen) ? s + 16u : 0u;
-    ck.gi = gi;
-    ck.j = j;
-    // the reply's buffers were found inside the transmit pool before its chunks were counted
-    const uint32_t bi = a.free[pd[5][j] + (c >> (a.rx.blog - 4u))];
-    ck.dc = a.tx_pool + (static_cast<uint64_t>(bi) << a.rx.blog) + ((16u * c) & ((1u << a.rx.blog) - 1u));
-    ck.lo = 0u;
-    ck.hi = min(16u, plen - 16u * c);  // >= 1: c is below the payload's chunk count
-    return ck;
-}
-
 // Stores the chunk whole (zeros after a payload's last byte) and adds its little-endian word sum to its
 // datagram's in LDS.  A datagram's chunks are consecutive lanes, so its sum over this step is a range of
 // the wave's prefix sum (DPP, no LDS round trip), as the rows kernels take a packet's: the datagram's last
 // lane of the step subtracts the prefix before its first lane — lane - min(c, lane), c the chunk's index in
 // its payload — and adds the range.  (Called by the whole wave.)
-__device__ __forceinline__ void echo_emit(const PlaceChunk &ck, const uint4 y, uint32_t c, uint32_t (&pd)[kEchoPd][64],
-                                          uint32_t lane)
+__device__ __forceinline__ void echo_emit(const PlaceChunk &ck, const uint4 y, uint32_t (&pd)[kEchoPd][64], uint32_t lane)
 {
     uint32_t sum = 0;
     if (ck.hi != 0) {
@@ -140,11 +105,11 @@ __device__ __forceinline__ void echo_emit(const PlaceChunk &ck, const uint4 y, u
         sum = sad4(make_uint4(o[0], o[1], o[2], o[3]), 0u);  // <= 8 * 0xffff
     }
     const uint32_t S = wave_incl_scan(sum);  // <= 64 * 8 * 0xffff
-    const uint32_t a = lane - min(c, lane);
+    const uint32_t a = lane - min(ck.c, lane);
     const uint32_t before = static_cast<uint32_t>(__shfl(static_cast<int>(S), static_cast<int>(max(a, 1u)) - 1, 64));
     const uint32_t jn = static_cast<uint32_t>(__shfl_down(static_cast<int>(ck.j), 1, 64));
     if (ck.hi != 0 && (lane == 63u || jn != ck.j))
-        pd[6][ck.j] += S - (a ? before : 0u);  // one lane per datagram; a payload's sum stays below 4096 * 8 * 0xffff < 2^32
+        pd[kEchoPdSum][ck.j] += S - (a ? before : 0u);  // one lane per datagram; a payload's sum stays below 4096 * 8 * 0xffff < 2^32
     wave_lds_fence();
 }
 
@@ -196,23 +161,21 @@ __global__ __launch_bounds__(kScanBlock) void echo_build_kernel(const EchoArgs a
     const uint32_t nck = copy ? (pay + 15u) >> 4 : 0u;
     const uint32_t cinc = wave_incl_scan(nck);
     const uint32_t W = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cinc), 63));
-    pd[6][lane] = 0u;
+    pd[kEchoPdSum][lane] = 0u;
     if (W != 0) {
-        pd[0][lane] = cinc - nck;
-        pd[1][lane] = static_cast<uint32_t>(e.gi);
-        pd[2][lane] = static_cast<uint32_t>(e.gi >> 32);
-        pd[3][lane] = ip_hdr + 4u;
-        pd[4][lane] = pay;
-        pd[5][lane] = fi + 1u;
+        pool_rows(pd, lane, cinc - nck, e.gi, ip_hdr + 4u, pay);
+        pd[kEchoPdFree][lane] = fi + 1u;
         wave_lds_fence();
-        for (uint32_t vb = 0; vb < W; vb += 128u) {
-            uint32_t i0, i1;  // the chunks' indices in their payloads
-            const PlaceChunk c0 = echo_fetch<NT>(a, pd, vb + lane, W, i0);
-            const PlaceChunk c1 = echo_fetch<NT>(a, pd, vb + 64u + lane, W, i1);
-            const uint4 y0 = place_second<NT>(a.rx, c0, lane), y1 = place_second<NT>(a.rx, c1, lane);
-            echo_emit(c0, y0, i0, pd, lane);
-            echo_emit(c1, y1, i1, pd, lane);
-        }
+        pool_walk<NT>(
+            a.rx, pd, W, lane,
+            [](uint32_t) { return 0u; },
+            [&](uint32_t j, uint32_t c) {
+                // chunk c of a payload lies in buffer c >> (blog - 4); the reply's buffers were found inside the
+                // transmit pool before its chunks were counted
+                const uint32_t bi = a.free[pd[kEchoPdFree][j] + (c >> (a.rx.blog - 4u))];
+                return a.tx_pool + (static_cast<uint64_t>(bi) << a.rx.blog) + ((16u * c) & ((1u << a.rx.blog) - 1u));
+            },
+            [&](const PlaceChunk &ck, const uint4 y) { echo_emit(ck, y, pd, lane); });
     }
     wave_lds_fence();
     if (!built)
@@ -227,9 +190,9 @@ __global__ __launch_bounds__(kScanBlock) void echo_build_kernel(const EchoArgs a
     if (bad)
         return;
     const uint32_t B = 1u << a.rx.blog;
-    const uint32_t *h = reinterpret_cast<const uint32_t *>(a.rx.pool + (static_cast<uint64_t>(a.rx.buf_idx[e.gi]) << a.rx.blog));
+    const uint32_t *h = pool_first(a.rx, e);  // a request: the classify found it inside the pool
     uint8_t *const hb = a.tx_pool + (static_cast<uint64_t>(a.free[fi]) << a.rx.blog) + B;
-    const uint32_t pay_be = bswap16_u32(fold16(pd[6][lane]));  // the payload's big-endian word sum, folded (RFC 1071 2(B))
+    const uint32_t pay_be = bswap16_u32(fold16(pd[kEchoPdSum][lane]));  // the payload's big-endian word sum, folded (RFC 1071 2(B))
     if (v4) {
         // ip_output_v4: 45 00 len | id 0000 | 40 01 csum | local | requester; then 00 00 csum (icmp_output)
         const uint32_t total = (24u + pay) & 0xffffu;

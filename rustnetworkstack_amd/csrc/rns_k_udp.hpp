@@ -30,14 +30,13 @@ namespace rns {
 //                           (entries, units) from LDS — it starts as the matrix prefix — and leave it
 //                           advanced for the next step and wave.  The cut, the record as two 16-byte
 //                           stores, d_udp, d_pos; then each wave walks the destination 16-byte chunks of all
-//                           its queued payloads concatenated, the placement's walk (place_owner /
-//                           place_load / place_second / place_join).  Destinations are 16-byte aligned, so
+//                           its queued payloads concatenated (pool_walk, rns_k_pool_view.hpp).
+//                           Destinations are 16-byte aligned, so
 //                           every chunk is one whole aligned store, a payload's last chunk with unspecified
 //                           bytes after its end (its own range's slack).
 // ---------------------------------------------------------------------------
-constexpr int kUdpPd = 6;
-// Per queued datagram in the wave's LDS table: [0] the wave's destination chunks before it, [1] [2] its
-// first fragment's place in d_buf_idx, [3] ip_hdr + 8, [4] payload bytes, [5] off16.
+// The wave's LDS table: pool_walk's rows, then a queued datagram's off16.
+constexpr int kUdpPd = kPdRows + 1;
 
 // The 64-datagram block of wave wv's step k in tile `tile`: a wave's blocks are consecutive, so batch order
 // is the waves in order, each one's steps in order.
@@ -57,8 +56,7 @@ __global__ __launch_bounds__(kScanBlock) void udp_classify_kernel(const UdpArgs 
     for (uint32_t k = 0; k < kUdpSteps; ++k) {
         const PoolLane e = pool_lane(a.rx, udp_block(blockIdx.x, wv, k), lane);
         const uint32_t stv = e.live ? a.rx.status[e.p] : 0u;
-        // accepted: the verify has found every fragment inside d_buf_idx and the pool; checked again for the
-        // bytes read here and in the scatter, so that nothing depends on what d_status held before the call
+        // the first buffer's checks (rns_k_pool_view.hpp says why each read is safe), as this kernel's own lines
         bool ok = e.live && (stv & RNS_RX_ACCEPT) && e.nf != 0 && e.gi + e.nf <= a.rx.n_frags;
         uint32_t rec = kUdpNotDgram;
         if (ok) {
@@ -68,11 +66,10 @@ __global__ __launch_bounds__(kScanBlock) void udp_classify_kernel(const UdpArgs 
             if (ok) {
                 const uint32_t *h = reinterpret_cast<const uint32_t *>(a.rx.pool + s0);
                 const uint32_t w0 = h[0];
-                const bool v6 = ((w0 >> 4) & 0xfu) == 6u;  // accepted: version 4 or 6
+                const bool v6 = ((w0 >> 4) & 0xfu) == 6u;
                 const uint32_t ip_hdr = v6 ? 40u : (w0 & 0xfu) * 4u;
-                // accepted: T >= 16 (IPv4) or 40 (IPv6), so the protocol is the datagram's; the ports' dword lies
-                // in the first buffer (ip_hdr + 8 <= 68 <= B) and inside the datagram
                 const uint32_t proto = v6 ? (h[1] >> 16) & 0xffu : (h[2] >> 8) & 0xffu;
+                // the ports' dword lies in the first buffer (ip_hdr + 8 <= 68 <= B) and inside the datagram
                 if (proto == 17u && ip_hdr + 8u <= e.T) {
                     const uint32_t t0 = h[ip_hdr >> 2];
                     const uint32_t dport = ((t0 >> 8) & 0xff00u) | (t0 >> 24);
@@ -144,41 +141,6 @@ __device__ __forceinline__ UdpRank udp_wave_rank(bool has, uint32_t sock, uint32
     return r;
 }
 
-// Chunk v of the wave's concatenated destination chunks, its first load issued: place_fetch with the
-// destination at the payload's 16-byte-aligned place in d_data.
-template <bool NT>
-__device__ __forceinline__ PlaceChunk udp_fetch(const UdpArgs &a, const uint32_t (&pd)[kUdpPd][64], uint32_t v, uint32_t W)
-{
-    PlaceChunk ck{};
-    ck.j = ~0u;
-    if (v >= W)
-        return ck;
-    const uint32_t j = place_owner(pd, v);
-    const uint32_t c = v - pd[0][j], skip = pd[3][j], plen = pd[4][j];
-    const uint64_t gi = (static_cast<uint64_t>(pd[2][j]) << 32) | pd[1][j];
-    const uint32_t o0 = skip + 16u * c;  // < skip + plen = T <= 65535
-    const uint32_t s = o0 & ~15u;
-    ck.sh = o0 & 15u;
-    ck.x = place_load<NT>(a.rx, gi, s);
-    ck.s2 = (ck.sh && s + 16u < skip + plen) ? s + 16u : 0u;
-    ck.gi = gi;
-    ck.j = j;
-    ck.dc = a.data + 16ull * (static_cast<uint64_t>(pd[5][j]) + c);  // the cut found the whole range inside d_data
-    ck.lo = 0u;
-    ck.hi = min(16u, plen - 16u * c);  // >= 1: c is below the payload's chunk count
-    return ck;
-}
-
-// The chunk as one aligned store: whole also where the payload ends inside it (the slack of its own range).
-__device__ __forceinline__ void udp_emit(const PlaceChunk &ck, const uint4 y)
-{
-    if (ck.hi == 0)
-        return;
-    uint32_t o[4];
-    place_join(ck, y, o);
-    *reinterpret_cast<uint4 *>(ck.dc) = make_uint4(o[0], o[1], o[2], o[3]);
-}
-
 template <bool NT>
 __global__ __launch_bounds__(kScanBlock) void udp_scatter_kernel(const UdpArgs a)
 {
@@ -235,13 +197,11 @@ __global__ __launch_bounds__(kScanBlock) void udp_scatter_kernel(const UdpArgs a
         uint32_t ip_hdr = 0;
         if (queued) {
             // the record: the classify found these header dwords inside the first buffer and the pool
-            const uint32_t *h =
-                reinterpret_cast<const uint32_t *>(a.rx.pool + (static_cast<uint64_t>(a.rx.buf_idx[e[k].gi]) << a.rx.blog));
-            const uint32_t w0 = h[0];
-            const bool v6 = ((w0 >> 4) & 0xfu) == 6u;
-            ip_hdr = v6 ? 40u : (w0 & 0xfu) * 4u;
-            const uint32_t t0 = h[ip_hdr >> 2];
-            const uint32_t sport = ((t0 & 0xffu) << 8) | ((t0 >> 8) & 0xffu);
+            const uint32_t *h = pool_first(a.rx, e[k]);
+            const IpHead ip = ip_head(h);
+            const bool v6 = ip.v6;
+            ip_hdr = ip.ip_hdr;
+            const uint32_t sport = l4_sport(h[ip_hdr >> 2]);
             uint4 *const r = a.rec_out + 2ull * pos[k];
             r[0] = v6 ? make_uint4(h[2], h[3], h[4], h[5]) : make_uint4(h[3], 0u, 0u, 0u);
             r[1] = make_uint4(static_cast<uint32_t>(e[k].p), off[k], sport | (plen << 16), (v6 ? 6u : 4u) | (flags << 8));
@@ -251,20 +211,15 @@ __global__ __launch_bounds__(kScanBlock) void udp_scatter_kernel(const UdpArgs a
         const uint32_t cinc = wave_incl_scan(nck);
         const uint32_t W = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cinc), 63));
         if (W != 0) {
-            pd[0][lane] = cinc - nck;
-            pd[1][lane] = static_cast<uint32_t>(e[k].gi);
-            pd[2][lane] = static_cast<uint32_t>(e[k].gi >> 32);
-            pd[3][lane] = ip_hdr + 8u;
-            pd[4][lane] = plen;
-            pd[5][lane] = off[k];
+            pool_rows(pd, lane, cinc - nck, e[k].gi, ip_hdr + 8u, plen);
+            pd[kPdRows][lane] = off[k];
             wave_lds_fence();
-            for (uint32_t vb = 0; vb < W; vb += 128u) {
-                const PlaceChunk c0 = udp_fetch<NT>(a, pd, vb + lane, W);
-                const PlaceChunk c1 = udp_fetch<NT>(a, pd, vb + 64u + lane, W);
-                const uint4 y0 = place_second<NT>(a.rx, c0, lane), y1 = place_second<NT>(a.rx, c1, lane);
-                udp_emit(c0, y0);
-                udp_emit(c1, y1);
-            }
+            // the cut found the whole range inside d_data: every chunk one aligned store (the range's own slack)
+            pool_walk<NT>(
+                a.rx, pd, W, lane,
+                [](uint32_t) { return 0u; },
+                [&](uint32_t j, uint32_t c) { return a.data + 16ull * (static_cast<uint64_t>(pd[kPdRows][j]) + c); },
+                [](const PlaceChunk &ck, const uint4 y) { place_emit_whole(ck, y); });
             wave_lds_fence();  // the next step writes the table again
         }
     }

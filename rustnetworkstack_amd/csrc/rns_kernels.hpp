@@ -43,6 +43,7 @@
 #include "rns_k_txrows.hpp"
 #include "rns_k_pool_tx.hpp"
 #include "rns_k_segment.hpp"
+#include "rns_k_pool_view.hpp"
 #include "rns_k_pool_place.hpp"
 #include "rns_k_scan.hpp"
 #include "rns_k_args.hpp"

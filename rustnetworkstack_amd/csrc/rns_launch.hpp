@@ -4,6 +4,7 @@
 //   k_segment.hip, k_place.hip                            TCP segmentation offload, receive placement
 //   k_flow.hip, k_plan.hip, k_echo.hip, k_udp.hip         the sequences of launches; each includes its own
 //                                                         kernels header (rns_k_flow / plan / echo / udp.hpp)
+//   (k_place, k_echo and k_udp, the pool verify's consumers, share rns_k_pool_view.hpp: view, decode, walk)
 //   k_scan.hip                                            the scan's middle launch, which those four share
 // rns_checksum.hip holds the device entry points of the C ABI, rns_pipeline.hip the host-resident
 // pipeline and the multi-GPU contexts.

@@ -16,24 +16,13 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import (_I32, _U8, _U16, _call, _descriptors, _local_addrs, _nonnull, _per_packet, _require_cuda, _status,
-                    _work_bytes, _workspace)
-from .pool import _buf_log2, recv_batch_pool, send_batch_pool
+from .batch import _I32, _U8, _call, _local_addrs, _nonnull, _per_packet, _require_cuda, _status, _work_bytes, _workspace
+from .pool import (_be_sum, _buf_log2, _fold, _host_datagrams, _new, _pool_batch, recv_batch_pool, send_batch_pool)
 
 
 def echo_work(n_pkts: int) -> int:
     """Bytes of workspace ``rx_icmp_echo_pool`` needs for ``n_pkts`` datagrams (rns_rx_icmp_echo_work)."""
     return _work_bytes("rns_rx_icmp_echo_work", int(n_pkts))
-
-
-def _new(t: torch.Tensor | None, name: str, n: int, dtype, dev) -> torch.Tensor:
-    """An output tensor of at least n entries: the caller's, or a new one."""
-    if t is None:
-        return torch.empty(max(n, 1), dtype=dtype, device=dev)
-    _require_cuda(t, name, (dtype,) if dtype not in _U16 else _U16)
-    if t.numel() < n or t.device != dev:
-        raise ValueError(f"{name} needs at least {n} entries on {dev}")
-    return t
 
 
 def rx_icmp_echo_pool(rx_pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: torch.Tensor, len16: torch.Tensor,
@@ -57,14 +46,9 @@ def rx_icmp_echo_pool(rx_pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: t
     int32 on the device: nothing is synchronised here, the counts stay on the device until the caller
     reads them.  Returns ``(status, l4_sum, echo, tx_blk_first, tx_head_len8, tx_pay_len16, tx_src,
     count)``; status and l4_sum are ``rx_verify_pool``'s."""
-    dev = _descriptors(rx_pool, ("buf_idx", buf_idx, _I32), ("blk_first", blk_first, _I32), ("len16", len16, _U16),
-                       ("tx_pool", tx_pool, _U8), ("free", free, _I32))
-    log2 = _buf_log2(buf_bytes, 256)
-    n, nf, n_free = len16.numel(), buf_idx.numel(), free.numel()
-    if blk_first.numel() < (n + 63) // 64:
-        raise ValueError("blk_first needs one entry per 64 datagrams")
-    if n > _lib.RNS_CHAIN_MAX_PACKETS or nf >= 2 ** 32 or n_free >= 2 ** 32:
-        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} datagrams and 2^32-1 buffers per pool call")
+    dev, log2, n, nf = _pool_batch(rx_pool, buf_idx, blk_first, len16, buf_bytes, 256, ("tx_pool", tx_pool, _U8),
+                                   ("free", free, _I32), more_bufs=free.numel())
+    n_free = free.numel()
     if rx_pool.data_ptr() & 15 or tx_pool.data_ptr() & 15:
         raise ValueError("the pools must start 16-byte aligned")
     cap = n if reply_cap is None else int(reply_cap)
@@ -96,63 +80,6 @@ def rx_icmp_echo_pool(rx_pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: t
 # ---------------------------------------------------------------------------
 # the same on the host
 # ---------------------------------------------------------------------------
-def _be_sum(b) -> int:
-    """Sum of the big-endian 16-bit words of b, an odd last byte zero-padded (util.rs:89-99)."""
-    a = np.frombuffer(bytes(b), dtype=np.uint8).astype(np.int64)
-    return int(a[0::2].sum()) * 256 + int(a[1::2].sum())
-
-
-def _fold(x: int) -> int:
-    while x > 0xFFFF:  # util.rs:101-103
-        x = (x & 0xFFFF) + (x >> 16)
-    return x
-
-
-def _verify_host(d: bytes, len0: int, local4: bytes, local6: bytes):
-    """(status, l4_sum, ip header length, is IPv6) of one datagram whose first buffer holds len0
-    bytes, as rns_rx_verify_pool_dev decides them (ip.rs:38-131, tcp.rs:838-850, icmp.rs:44-75)."""
-    bad = (_lib.RNS_RX_MALFORMED, 0, 0, False)
-    T = len(d)
-    if T == 0:
-        return bad
-    ver = d[0] >> 4
-    st = 0
-    if ver == 4:
-        hdr = (d[0] & 0xF) * 4
-        if hdr == 0 or len0 < 16 or hdr > len0:
-            return bad
-        if _fold(_be_sum(d[:hdr])) == 0xFFFF:
-            st |= _lib.RNS_RX_IP_OK
-        if (((d[6] << 8) | d[7]) & 0x3FFF) != 0:
-            st |= _lib.RNS_RX_FRAGMENT
-        proto, src, local = d[9], d[12:16], local4
-    elif ver == 6:
-        hdr = 40
-        if len0 < 24 or T < 40:
-            return bad
-        st |= _lib.RNS_RX_IP_OK
-        proto, src, local = d[6], d[8:24], local6
-    else:
-        return bad
-    l4len, l4 = T - hdr, 0
-    if proto in (6, 1, 58):
-        if proto == 58 and ver == 4:
-            return bad
-        seed = 0 if proto == 1 else _fold(_be_sum(src) + _be_sum(local6 if proto == 58 else local) +
-                                          (l4len >> 16) + (l4len & 0xFFFF) + proto)
-        l4 = _fold(seed + _be_sum(d[hdr:])) ^ 0xFFFF
-        if l4 == 0:
-            st |= _lib.RNS_RX_L4_OK
-    elif proto == 17:
-        st |= _lib.RNS_RX_L4_UNCHECKED
-    else:
-        st |= _lib.RNS_RX_UNKNOWN_PROTO
-    if (st & _lib.RNS_RX_IP_OK) and not (st & _lib.RNS_RX_FRAGMENT) and \
-            (st & (_lib.RNS_RX_L4_OK | _lib.RNS_RX_L4_UNCHECKED)):
-        st |= _lib.RNS_RX_ACCEPT
-    return st, l4, hdr, ver == 6
-
-
 def echo_host(rx_pool: np.ndarray, buf_idx, blk_first, len16, local_ipv4: bytes, local_ipv6: bytes, tx_pool: np.ndarray,
               free, *, buf_bytes: int = 512, reply_cap: int | None = None, ip_id_base: int = 0, ip_id_add: int = 0):
     """``rx_icmp_echo_pool`` in numpy over host pools (uint8 arrays; ``tx_pool`` is written in place, and
@@ -164,33 +91,15 @@ def echo_host(rx_pool: np.ndarray, buf_idx, blk_first, len16, local_ipv4: bytes,
     B = int(buf_bytes)
     log2 = _buf_log2(B, 256)
     ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
-    buf_idx = np.asarray(buf_idx, dtype=np.uint32).astype(np.int64)
-    blk_first = np.asarray(blk_first, dtype=np.uint32).astype(np.int64)
-    len16 = np.asarray(len16, dtype=np.uint16).astype(np.int64)
     free = np.asarray(free, dtype=np.uint32).astype(np.int64)
-    n, n_frags, n_free = len(len16), len(buf_idx), len(free)
+    n, n_free = len(len16), len(free)
     cap = n if reply_cap is None else int(reply_cap)
     tx_bufs = tx_pool.size >> log2
     status, l4_sum, echo = np.zeros(n, np.uint8), np.zeros(n, np.uint16), np.zeros(n, np.uint8)
     heads, pays, srcs, firsts = [], [], [], []
     R = F = V = 0
     full = False
-    for i in range(n):
-        T = int(len16[i])
-        nf = -(-T // B)
-        gi = int(blk_first[i // 64]) + int((-(-len16[64 * (i // 64):i] // B)).sum())
-        d, ok = b"", nf != 0 and gi + nf <= n_frags
-        if ok:
-            frags = []
-            for j in range(nf):
-                at, ln = int(buf_idx[gi + j]) << log2, min(B, T - j * B)
-                ok = ok and at + ln <= rx_pool.size
-                frags.append(rx_pool[at:at + ln].tobytes())
-            d = b"".join(frags)
-        if not ok:
-            status[i] = _lib.RNS_RX_MALFORMED
-            continue
-        st, l4, h, v6 = _verify_host(d, min(T, B), ip4, ip6)
+    for i, T, d, st, l4, h, v6 in _host_datagrams(rx_pool, buf_idx, blk_first, len16, ip4, ip6, B, log2):
         status[i], l4_sum[i] = st, l4
         if not (st & _lib.RNS_RX_ACCEPT) or T - h < 4 or (d[6] if v6 else d[9]) != (58 if v6 else 1) or \
                 d[h] != (128 if v6 else 8):

@@ -18,8 +18,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import _I32, _I64, _U8, _U16, _call, _descriptors, _local_addrs, _nonnull, _per_packet, _seq_gt, _status
-from .pool import _buf_log2
+from .batch import _I32, _I64, _U8, _call, _local_addrs, _nonnull, _per_packet, _seq_gt, _status
+from .pool import _pool_batch
 
 # rns_rx_tcp_meta (rns_checksum.h), one record per datagram
 META_DTYPE = np.dtype([("flow", "<u4"), ("seq", "<u4"), ("ack", "<u4"), ("sport", "<u2"), ("dport", "<u2"),
@@ -84,15 +84,10 @@ def rx_tcp_place_pool(pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: torc
     its flow is in the table and its payload lies inside the window, the payload is copied to
     ``win_off[f] + (seq - next_seq[f])``.  Returns ``(status, l4_sum, meta)``; status and l4_sum are
     ``rx_verify_pool``'s."""
-    dev = _descriptors(pool, ("buf_idx", buf_idx, _I32), ("blk_first", blk_first, _I32), ("len16", len16, _U16),
-                       ("table", table, _U8), ("next_seq", next_seq, _I32), ("win_off", win_off, _I64),
-                       ("win_len", win_len, _I32), ("stream", stream, _U8))
-    log2 = _buf_log2(buf_bytes, 128)
-    n, nf, nfl = len16.numel(), buf_idx.numel(), next_seq.numel()
-    if blk_first.numel() < (n + 63) // 64:
-        raise ValueError("blk_first needs one entry per 64 datagrams")
-    if n > _lib.RNS_CHAIN_MAX_PACKETS or nf >= 2 ** 32:
-        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} datagrams and 2^32-1 buffers per pool call")
+    dev, log2, n, nf = _pool_batch(pool, buf_idx, blk_first, len16, buf_bytes, 128, ("table", table, _U8),
+                                   ("next_seq", next_seq, _I32), ("win_off", win_off, _I64), ("win_len", win_len, _I32),
+                                   ("stream", stream, _U8))
+    nfl = next_seq.numel()
     if win_off.numel() != nfl or win_len.numel() != nfl:
         raise ValueError("next_seq, win_off and win_len need one entry per flow each")
     if pool.data_ptr() & 15:

@@ -10,7 +10,8 @@ with the remainder, alloc_header (buf.rs:262-291) prepends a buffer whose data s
 a datagram is implied by its head length, its payload length and its buffers' indices.
 ``tx_pool_layout`` computes the index, ``tx_fill_pool`` finalizes on the device
 (rns_tx_fill_pool_dev) and ``send_batch_pool`` sends from that form.  The functions are re-exported
-by ``batch``, whose argument checks they use.
+by ``batch``, whose argument checks they use; ``_pool_batch`` and ``_host_datagrams`` are what the
+verify's consumers (``place``, ``icmp``, ``udp``) share.
 """
 from __future__ import annotations
 
@@ -20,7 +21,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import (_I32, _U8, _U16, _call, _descriptors, _local_addrs, _per_packet, _recv_chain_args, _status)
+from .batch import (_I32, _U8, _U16, _call, _descriptors, _local_addrs, _per_packet, _recv_chain_args, _require_cuda,
+                    _status)
 
 
 def _buf_log2(buf_bytes: int, lowest: int = 64) -> int:
@@ -52,6 +54,39 @@ def rx_pool_layout(length, buf_bytes: int = 512):
     return blk[:nb], first, int(nf.value)
 
 
+def _pool_batch(pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: torch.Tensor, len16: torch.Tensor, buf_bytes: int,
+                lowest: int, *more, more_bufs: int = 0, demux: bool = False):
+    """The checks every call over the pool receive form opens with, but the pool's alignment (``more``: further
+    ``_descriptors`` entries; ``more_bufs``: a second buffer count under the cap; ``demux``: the demux's cap).
+    Returns ``(device, log2 of buf_bytes, datagrams, buffer indices)``."""
+    dev = _descriptors(pool, ("buf_idx", buf_idx, _I32), ("blk_first", blk_first, _I32), ("len16", len16, _U16), *more)
+    log2 = _buf_log2(buf_bytes, lowest)
+    n, nf = len16.numel(), buf_idx.numel()
+    if blk_first.numel() < (n + 63) // 64:
+        raise ValueError("blk_first needs one entry per 64 datagrams")
+    many, what = ((nf << log2) >= 2 ** 36, "2^36 bytes of buffers per demux call") if demux else \
+        (nf >= 2 ** 32 or more_bufs >= 2 ** 32, "2^32-1 buffers per pool call")
+    if n > _lib.RNS_CHAIN_MAX_PACKETS or many:
+        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} datagrams and {what}")
+    return dev, log2, n, nf
+
+
+def _new(t: torch.Tensor | None, name: str, n: int, dtype, dev) -> torch.Tensor:
+    """An output tensor of at least n entries: the caller's, or a new one."""
+    if t is None:
+        return torch.empty(max(n, 1), dtype=dtype, device=dev)
+    _require_cuda(t, name, (dtype,) if dtype not in _U16 else _U16)
+    if t.numel() < n or t.device != dev:
+        raise ValueError(f"{name} needs at least {n} entries on {dev}")
+    return t
+
+
+def _np(t, dtype):
+    if isinstance(t, torch.Tensor):
+        t = t.cpu().numpy()
+    return np.ascontiguousarray(t).reshape(-1).view(dtype)
+
+
 def rx_verify_pool(pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: torch.Tensor, len16: torch.Tensor,
                    local_ipv4: bytes, local_ipv6: bytes, *, buf_bytes: int = 512, status: torch.Tensor | None = None,
                    l4_sum: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor | None]:
@@ -62,13 +97,7 @@ def rx_verify_pool(pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: torch.T
     (see ``rx_pool_layout``; ``recv_batch_pool`` produces all three).  Exactly the results of
     ``rx_verify_chain`` on the chains this expands to, from a third of the descriptor bytes.
     Returns ``(status, l4_sum)`` as rx_verify_chain does."""
-    dev = _descriptors(pool, ("buf_idx", buf_idx, _I32), ("blk_first", blk_first, _I32), ("len16", len16, _U16))
-    log2 = _buf_log2(buf_bytes)
-    n, nf = len16.numel(), buf_idx.numel()
-    if blk_first.numel() < (n + 63) // 64:
-        raise ValueError("blk_first needs one entry per 64 datagrams")
-    if n > _lib.RNS_CHAIN_MAX_PACKETS or nf >= 2 ** 32:
-        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} datagrams and 2^32-1 buffers per pool call")
+    dev, log2, n, nf = _pool_batch(pool, buf_idx, blk_first, len16, buf_bytes, 64)
     if pool.data_ptr() & 15:
         raise ValueError("the pool must start 16-byte aligned")
     ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
@@ -77,6 +106,88 @@ def rx_verify_pool(pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: torch.T
           blk_first.data_ptr(), len16.data_ptr(), n, ip4, ip6, status.data_ptr(),
           _per_packet(l4_sum, "l4_sum", n, dev))
     return status, l4_sum
+
+
+# --- the pool receive form on the host: what echo_host and demux_host are written over ---
+def _be_sum(b) -> int:
+    """Sum of the big-endian 16-bit words of b, an odd last byte zero-padded (util.rs:89-99)."""
+    a = np.frombuffer(bytes(b), dtype=np.uint8).astype(np.int64)
+    return int(a[0::2].sum()) * 256 + int(a[1::2].sum())
+
+
+def _fold(x: int) -> int:
+    while x > 0xFFFF:  # util.rs:101-103
+        x = (x & 0xFFFF) + (x >> 16)
+    return x
+
+
+def _verify_host(d: bytes, len0: int, local4: bytes, local6: bytes):
+    """(status, l4_sum, ip header length, is IPv6) of one datagram whose first buffer holds len0
+    bytes, as rns_rx_verify_pool_dev decides them (ip.rs:38-131, tcp.rs:838-850, icmp.rs:44-75)."""
+    bad = (_lib.RNS_RX_MALFORMED, 0, 0, False)
+    T = len(d)
+    if T == 0:
+        return bad
+    ver = d[0] >> 4
+    st = 0
+    if ver == 4:
+        hdr = (d[0] & 0xF) * 4
+        if hdr == 0 or len0 < 16 or hdr > len0:
+            return bad
+        if _fold(_be_sum(d[:hdr])) == 0xFFFF:
+            st |= _lib.RNS_RX_IP_OK
+        if (((d[6] << 8) | d[7]) & 0x3FFF) != 0:
+            st |= _lib.RNS_RX_FRAGMENT
+        proto, src, local = d[9], d[12:16], local4
+    elif ver == 6:
+        hdr = 40
+        if len0 < 24 or T < 40:
+            return bad
+        st |= _lib.RNS_RX_IP_OK
+        proto, src, local = d[6], d[8:24], local6
+    else:
+        return bad
+    l4len, l4 = T - hdr, 0
+    if proto in (6, 1, 58):
+        if proto == 58 and ver == 4:
+            return bad
+        seed = 0 if proto == 1 else _fold(_be_sum(src) + _be_sum(local6 if proto == 58 else local) +
+                                          (l4len >> 16) + (l4len & 0xFFFF) + proto)
+        l4 = _fold(seed + _be_sum(d[hdr:])) ^ 0xFFFF
+        if l4 == 0:
+            st |= _lib.RNS_RX_L4_OK
+    elif proto == 17:
+        st |= _lib.RNS_RX_L4_UNCHECKED
+    else:
+        st |= _lib.RNS_RX_UNKNOWN_PROTO
+    if (st & _lib.RNS_RX_IP_OK) and not (st & _lib.RNS_RX_FRAGMENT) and \
+            (st & (_lib.RNS_RX_L4_OK | _lib.RNS_RX_L4_UNCHECKED)):
+        st |= _lib.RNS_RX_ACCEPT
+    return st, l4, hdr, ver == 6
+
+
+def _host_datagrams(rx_pool: np.ndarray, buf_idx, blk_first, len16, ip4: bytes, ip6: bytes, B: int, log2: int):
+    """The pool receive form on the host, one ``(i, T, d, status, l4_sum, ip header length, is IPv6)`` per
+    datagram: its length, its bytes gathered from its buffers and ``_verify_host``'s verdict — or, for a
+    datagram whose buffers are not all inside ``buf_idx`` and the pool, ``d`` empty and RNS_RX_MALFORMED."""
+    buf_idx = np.asarray(buf_idx, dtype=np.uint32).astype(np.int64)
+    blk_first = np.asarray(blk_first, dtype=np.uint32).astype(np.int64)
+    len16 = np.asarray(len16, dtype=np.uint16).astype(np.int64)
+    nfr = -(-len16 // B)
+    for i in range(len(len16)):
+        T, nf = int(len16[i]), int(nfr[i])
+        gi = int(blk_first[i // 64]) + int(nfr[64 * (i // 64):i].sum())  # the running fragment index of its block
+        ok = nf != 0 and gi + nf <= len(buf_idx)
+        frags = []
+        for j in range(nf if ok else 0):
+            at, ln = int(buf_idx[gi + j]) << log2, min(B, T - j * B)
+            ok = ok and at + ln <= rx_pool.size
+            frags.append(rx_pool[at:at + ln].tobytes())
+        if ok:
+            d = b"".join(frags)
+            yield (i, T, d) + _verify_host(d, min(T, B), ip4, ip6)
+        else:
+            yield i, T, b"", _lib.RNS_RX_MALFORMED, 0, 0, False
 
 
 def recv_batch_pool(fd: int, pool: np.ndarray, free: np.ndarray, buf_bytes: int = 512, mru: int = 2048,

@@ -19,10 +19,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import (_I32, _U8, _U16, _call, _descriptors, _local_addrs, _nonnull, _per_packet, _require_cuda, _status,
-                    _work_bytes)
-from .icmp import _new, _verify_host
-from .pool import _buf_log2, recv_batch_pool
+from .batch import _U8, _U16, _call, _local_addrs, _nonnull, _per_packet, _require_cuda, _status, _work_bytes
+from .pool import _buf_log2, _host_datagrams, _new, _np, _pool_batch, recv_batch_pool
 
 REC = np.dtype([("ip", "u1", 16), ("src", "<u4"), ("off16", "<u4"), ("sport", "<u2"), ("len", "<u2"), ("family", "u1"),
                 ("flags", "u1"), ("pad", "u1", 2)])  # rns_udp_rec
@@ -77,13 +75,8 @@ def rx_udp_demux_pool(rx_pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: t
     per datagram) and ``data`` (default: one byte per pool-buffer byte in use, so nothing is cut) bound what
     is written; entries past them get RNS_UDP_NOROOM.  Nothing is synchronised here.  Returns a
     ``UdpDemux`` of device tensors (``udp`` uint8 [n], ``pos`` / ``q_first`` / ``count`` int32)."""
-    dev = _descriptors(rx_pool, ("buf_idx", buf_idx, _I32), ("blk_first", blk_first, _I32), ("len16", len16, _U16))
-    log2 = _buf_log2(buf_bytes, 128)
-    n, nf, n_socks = len16.numel(), buf_idx.numel(), int(n_socks)
-    if blk_first.numel() < (n + 63) // 64:
-        raise ValueError("blk_first needs one entry per 64 datagrams")
-    if n > _lib.RNS_CHAIN_MAX_PACKETS or (nf << log2) >= 2 ** 36:
-        raise ValueError(f"at most {_lib.RNS_CHAIN_MAX_PACKETS} datagrams and 2^36 bytes of buffers per demux call")
+    dev, log2, n, nf = _pool_batch(rx_pool, buf_idx, blk_first, len16, buf_bytes, 128, demux=True)
+    n_socks = int(n_socks)
     if not 0 <= n_socks <= _lib.RNS_UDP_MAX_SOCKS:
         raise ValueError(f"n_socks must be at most {_lib.RNS_UDP_MAX_SOCKS}")
     if rx_pool.data_ptr() & 15:
@@ -137,9 +130,6 @@ def demux_host(rx_pool: np.ndarray, buf_idx, blk_first, len16, local_ipv4: bytes
     B = int(buf_bytes)
     log2 = _buf_log2(B, 128)
     ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
-    buf_idx = np.asarray(buf_idx, dtype=np.uint32).astype(np.int64)
-    blk_first = np.asarray(blk_first, dtype=np.uint32).astype(np.int64)
-    len16 = np.asarray(len16, dtype=np.uint16).astype(np.int64)
     n, n_frags, n_socks = len(len16), len(buf_idx), int(n_socks)
     if not 0 <= n_socks <= _lib.RNS_UDP_MAX_SOCKS:
         raise ValueError(f"n_socks must be at most {_lib.RNS_UDP_MAX_SOCKS}")
@@ -151,23 +141,8 @@ def demux_host(rx_pool: np.ndarray, buf_idx, blk_first, len16, local_ipv4: bytes
         rec = np.zeros(cap, dtype=REC)
     status, l4_sum, udp = np.zeros(n, np.uint8), np.zeros(n, np.uint16), np.zeros(n, np.uint8)
     pos = np.full(n, NO_POS, dtype=np.uint32)
-    nfr = -(-len16 // B)
     entries = []  # (socket, datagram, source address, source port, family, payload)
-    for i in range(n):
-        T, nf = int(len16[i]), int(nfr[i])
-        gi = int(blk_first[i // 64]) + int(nfr[64 * (i // 64):i].sum())
-        d, ok = b"", nf != 0 and gi + nf <= n_frags
-        if ok:
-            frags = []
-            for j in range(nf):
-                at, ln = int(buf_idx[gi + j]) << log2, min(B, T - j * B)
-                ok = ok and at + ln <= rx_pool.size
-                frags.append(rx_pool[at:at + ln].tobytes())
-            d = b"".join(frags)
-        if not ok:
-            status[i] = _lib.RNS_RX_MALFORMED
-            continue
-        st, l4, h, v6 = _verify_host(d, min(T, B), ip4, ip6)
+    for i, T, d, st, l4, h, v6 in _host_datagrams(rx_pool, buf_idx, blk_first, len16, ip4, ip6, B, log2):
         status[i], l4_sum[i] = st, l4
         if not (st & _lib.RNS_RX_ACCEPT) or (d[6] if v6 else d[9]) != 17 or T - h < 8:
             continue
@@ -194,12 +169,6 @@ def demux_host(rx_pool: np.ndarray, buf_idx, blk_first, len16, local_ipv4: bytes
             udp[i] |= _lib.RNS_UDP_NOROOM
         off += units
     return UdpDemux(status, l4_sum, udp, pos, rec, q_first, np.array([len(entries), off], dtype=np.uint32), data)
-
-
-def _np(t, dtype):
-    if isinstance(t, torch.Tensor):
-        t = t.cpu().numpy()
-    return np.ascontiguousarray(t).reshape(-1).view(dtype)
 
 
 def drain(result: UdpDemux, s: int):
