@@ -616,6 +616,89 @@ int rns_rx_udp_demux_work(uint32_t n_pkts, uint32_t n_socks, uint64_t *bytes);
  * then unspecified), n_socks > RNS_UDP_MAX_SOCKS, a NULL tbl, or a NULL ports with n_socks > 0. */
 int rns_rx_udp_port_table_build(const uint16_t *ports, uint32_t n_socks, uint16_t *tbl /* 65536 */);
 
+/* UDP send build over pool buffers: udp_send -> udp_output -> ip_output_v4 / ip_output_v6 (udp.rs:101-114 and
+ * 150-173, ip.rs:133-177) for a batch of sends on the device — the UDP twin of the echo responder's build step.
+ * Every send becomes a finished datagram in a transmit pool, described by the compact descriptors
+ * rns_tx_fill_pool_dev and rns_io_send_batch_pool take; its buffers are drawn from a free list on the device and
+ * its IPv4 id is numbered as NEXT_PACKET_ID would number it.  It reads the demux's records as they are, so
+ * receive -> demux -> send -> sendmmsg is one stream of launches (the reference's udp_echo.rs: udp_recv, then
+ * udp_send back to the sender) and the host touches no datagram.  Buffers have 2^buf_log2 bytes, B below.
+ * The form is defined by what it expands to:
+ *   A record read as a send: rns_udp_rec is taken unchanged.  The send goes TO ip (family 4: ip[0..4], family 6:
+ *     all 16), TO port sport, with the len bytes at d_data[16 * off16 ..).  src and pad are not read.  The demux's
+ *     output is therefore an echo server's input with no transformation; a host that builds sends of its own
+ *     fills the same struct with flags = RNS_UDP_QUEUED.
+ *   Which records are sends: record k < n_recs is a send (RNS_UDPTX_SEND) iff k < d_q_first[n_socks] — read on
+ *     the device: the host need not read it back and may pass n_recs = rec_cap — its flags have RNS_UDP_QUEUED,
+ *     its family is 4 or 6, and 16 * off16 + len <= data_bytes (computed in 64 bits).  Every other record has
+ *     d_send[k] == 0 and takes no buffer and no id.  The demux writes no record for an RNS_UDP_NOROOM entry, so
+ *     a d_rec that was zeroed before a cut demux is safe to pass whole: the unwritten records lack
+ *     RNS_UDP_QUEUED.
+ *   Source port: d_sock_port[s], s the socket whose range [d_q_first[s], d_q_first[s + 1]) holds k — the demux's
+ *     socket-major layout; a host caller groups its sends by socket, which is how udp_send is called anyway.
+ *     (s is the last socket with d_q_first[s] <= k, socket 0 if there is none.)  A table that is not
+ *     non-decreasing is outside the domain: which socket a record gets is then unspecified — still nothing
+ *     outside the arrays is read or written.  n_socks is 1 .. RNS_UDP_MAX_SOCKS.
+ *   Allocation (the echo responder's rule): send k needs nf_k = 1 + ceil(len_k / B) buffers.  With R_k and F_k
+ *     the inclusive counts of sends and of their buffers up to k in record order, it is built iff R_k <= send_cap
+ *     and F_k <= n_free; both counts are monotone, so the built sends are a prefix of the sends.  The others get
+ *     RNS_UDPTX_NOBUF and nothing is written for them: the host sends those.  Datagram r = R_k - 1 takes
+ *     d_free[F_k - nf_k .. F_k), head buffer first, so the descriptors' buf_idx IS d_free[0 .. d_count[1]) itself
+ *     (d_free is read-only), d_tx_blk_first[r / 64] is the number of buffers before datagram 64 * (r / 64),
+ *     d_tx_head_len8[r] is 28 or 48, d_tx_pay_len16[r] = len_k, d_tx_src[r] = k, and d_count = {datagrams,
+ *     buffers, IPv4 datagrams}.  Entries of the descriptor arrays at and past d_count[0] (for d_tx_blk_first: of
+ *     blocks without a datagram) are not written.  (The buffers are counted as payload buffers + sends, the
+ *     payload buffers in 32 bits: always exact up to 2^24 records; a batch whose sends hold 2^32 payload buffers
+ *     or more is outside the domain — still nothing outside the arrays and the pool is read or written.)
+ *   Bytes: the datagram is laid out as append_from_slice, then alloc_header(8), then alloc_header(20 / 40) leave
+ *     it: the head is the LAST 28 / 48 bytes of the head buffer, and payload byte j is at offset j & (B - 1) of
+ *     buffer 1 + (j >> buf_log2): whole buffers from offset 0 and a last one with the remainder, none for
+ *     len == 0.  IPv4: 45 00, total length (28 + len) mod 2^16, id = (ip_id_base + *d_ip_id_add + the IPv4 sends
+ *     before it) mod 2^16 in record order, flags/offset 0, TTL 64, protocol 17, the header checksum, source =
+ *     the local address, then the destination.  IPv6: 60 00 00 00, payload length (8 + len) mod 2^16, next
+ *     header 17, hop limit 64, the local address, the destination, and no id taken.  UDP: source port,
+ *     destination port, length (8 + len) mod 2^16, and the checksum compute_buffer_ones_comp(pseudo(local,
+ *     destination, that length, 17), packet) ^ 0xffff; a computed 0 is stored as 0, as the reference stores it.
+ *     The mod-2^16 lengths are the reference's `as u16` and are pinned, not corrected.  The stored bytes equal
+ *     those rns_tx_fill_pool_dev produces from the same heads with zeroed checksum fields.
+ *     Only a datagram's own buffers are written: the head bytes, the payload bytes, and at most the bytes from
+ *     the payload's end up to the next 16-byte boundary of its last buffer (unspecified values: the buffer is
+ *     the datagram's alone and a sender reads len bytes).  Every other byte of the transmit pool, d_data, d_rec
+ *     and every input array stay as they were.  A datagram with any buffer index >= tx_pool_bytes >> buf_log2
+ *     is counted and described, but gets d_tx_head_len8[r] = 0 (malformed to rns_tx_fill_pool_dev and the
+ *     sender) and RNS_UDPTX_SEND | RNS_UDPTX_BADBUF without RNS_UDPTX_BUILT, and nothing is written for it.
+ *     The same inputs give the same bytes on every run.
+ * The launches: one that classifies, two one-workgroup scans, and one that copies each payload once — summing
+ * what it copies — and writes the heads, both checksums filled.  No atomic decides an output.
+ * n_recs == 0 is RNS_OK with d_count zeroed.  buf_log2 outside 8..15, n_socks == 0 or > RNS_UDP_MAX_SOCKS, a
+ * NULL d_data / d_rec / d_q_first / d_sock_port / d_tx_pool / d_count / d_send / d_work / local address, a NULL
+ * d_free with n_free > 0, a d_data, d_rec or d_tx_pool that is not 16-byte aligned, a d_work that is not 8-byte
+ * aligned, work_bytes below rns_tx_udp_send_work's answer, or n_recs > RNS_CHAIN_MAX_PACKETS is RNS_E_INVALID,
+ * all before the device is touched.  d_tx_blk_first / d_tx_head_len8 / d_tx_pay_len16 may be NULL iff
+ * send_cap == 0; d_tx_src and d_ip_id_add are optional. */
+#define RNS_UDPTX_SEND   0x01u  /* a well-formed send: udp_send would be called for it */
+#define RNS_UDPTX_BUILT  0x02u  /* its datagram is built and described in the tx descriptors */
+#define RNS_UDPTX_NOBUF  0x04u  /* past send_cap or past the free list: the host sends it */
+#define RNS_UDPTX_BADBUF 0x08u  /* a buffer it drew lies outside the tx pool: nothing written */
+int rns_tx_udp_send_pool_dev(const uint8_t *d_data, uint64_t data_bytes,
+                             const rns_udp_rec *d_rec, uint32_t n_recs,
+                             const uint32_t *d_q_first /* n_socks + 1 */,
+                             const uint16_t *d_sock_port /* n_socks, host byte order */, uint32_t n_socks,
+                             const uint8_t *local_ipv4, const uint8_t *local_ipv6,
+                             uint8_t *d_tx_pool, uint64_t tx_pool_bytes, uint32_t buf_log2,
+                             const uint32_t *d_free, uint32_t n_free,      /* free tx buffers, taken in order */
+                             uint32_t send_cap,
+                             uint16_t ip_id_base, const uint32_t *d_ip_id_add /* optional device dword, added to the base */,
+                             uint32_t *d_tx_blk_first /* (send_cap + 63) / 64 */, uint8_t *d_tx_head_len8,
+                             uint16_t *d_tx_pay_len16, uint32_t *d_tx_src /* optional, send_cap: the record's index */,
+                             uint32_t *d_count /* 3 dwords: datagrams, buffers taken, IPv4 ids taken */,
+                             uint8_t *d_send /* n_recs */,
+                             void *d_work, uint64_t work_bytes, void *stream);
+
+/* The send build's workspace in bytes for n_recs records (CPU only): non-zero and monotone in n_recs.
+ * RNS_E_INVALID for a NULL bytes or n_recs > RNS_CHAIN_MAX_PACKETS. */
+int rns_tx_udp_send_work(uint32_t n_recs, uint64_t *bytes);
+
 /* TCP flow update: the rest of tcp_input for an Established socket (tcp.rs:642-740) on the device,
  * over the placement's d_meta as it is — the advance of receive_next_seq and the reassembler's
  * next_sequence, the delayed-ACK count and its immediate ACKs, the ACK-field check that trims the

@@ -22,7 +22,8 @@
                   the host for what the device leaves (also ``batch.*``);
 * ``udp``       — UDP receive demux: every accepted UDP datagram to a bound port becomes a record and a
                   payload in its socket's queue on the device, the queues contiguous and in arrival order;
-                  the same on the host for what the device leaves (also ``batch.*``);
+                  the same on the host for what the device leaves — and the UDP send build: every record
+                  read as a send becomes a finished datagram in a transmit pool (also ``batch.*``);
 * ``workloads`` — the synthetic packet batches BASELINE.json's configs name.
 """
 from . import _lib, util  # noqa: F401

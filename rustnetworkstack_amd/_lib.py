@@ -50,6 +50,10 @@ RNS_UDP_DGRAM = 0x01      # ... and its d_udp
 RNS_UDP_SOCK = 0x02
 RNS_UDP_QUEUED = 0x04
 RNS_UDP_NOROOM = 0x08
+RNS_UDPTX_SEND = 0x01     # rns_tx_udp_send_pool_dev's d_send
+RNS_UDPTX_BUILT = 0x02
+RNS_UDPTX_NOBUF = 0x04
+RNS_UDPTX_BADBUF = 0x08
 RNS_TCP_ESTABLISHED = 1  # rns_tcp_flow.state: the only one the flow update's fast path takes
 RNS_FLOW_MAX_SEGS = 1024  # a flow's datagrams per flow-update call
 RNS_SEG_CONSUMED = 0x01
@@ -93,6 +97,8 @@ EXPORTED_SYMBOLS = (
     "rns_rx_udp_demux_pool_dev",
     "rns_rx_udp_demux_work",
     "rns_rx_udp_port_table_build",
+    "rns_tx_udp_send_pool_dev",
+    "rns_tx_udp_send_work",
     "rns_rx_tcp_flow_update_dev",
     "rns_rx_tcp_flow_update_work",
     "rns_tx_ack_build_dev",
@@ -200,6 +206,9 @@ _SIGNATURES = {
                                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "rns_rx_udp_demux_work": (_int, [_u32, _u32, ctypes.POINTER(_u64)]),
     "rns_rx_udp_port_table_build": (_int, [_vp, _u32, _vp]),
+    "rns_tx_udp_send_pool_dev": (_int, [_vp, _u64, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u64, _u32, _vp, _u32, _u32, _u16,
+                                        _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "rns_tx_udp_send_work": (_int, [_u32, ctypes.POINTER(_u64)]),
     "rns_rx_tcp_flow_update_dev": (_int, [_vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "rns_rx_tcp_flow_update_work": (_int, [_u32, _u32, ctypes.POINTER(_u64)]),
     "rns_tx_ack_build_dev": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u16, _vp, _u64, _vp, _u32, _vp, _vp, _vp,

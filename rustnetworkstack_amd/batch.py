@@ -859,8 +859,10 @@ _SEND_API = ("PLAN_RES_DTYPE", "plan_host", "tx_plan_work", "tx_tcp_plan", "tx_t
 # and the ICMP echo responder (icmp.py): batch.rx_icmp_echo_pool, batch.echo_host, batch.echo_respond, batch.echo_work.
 _ICMP_API = ("echo_host", "echo_respond", "echo_work", "rx_icmp_echo_pool")
 # and the UDP receive demux (udp.py): batch.rx_udp_demux_pool, batch.demux_host, batch.drain, batch.udp_demux,
-# batch.port_table, batch.demux_work.
-_UDP_API = ("demux_host", "demux_work", "drain", "port_table", "rx_udp_demux_pool", "udp_demux")
+# batch.port_table, batch.demux_work — and its send build: batch.tx_udp_send_pool, batch.send_host,
+# batch.udp_send_work, batch.udp_echo, batch.UdpSend.
+_UDP_API = ("demux_host", "demux_work", "drain", "port_table", "rx_udp_demux_pool", "udp_demux",
+            "UdpSend", "send_host", "tx_udp_send_pool", "udp_echo", "udp_send_work")
 
 
 def __getattr__(name):

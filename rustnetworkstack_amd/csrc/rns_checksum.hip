@@ -570,6 +570,62 @@ int rns_rx_udp_demux_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
     return launch_rx_udp(a, nt, static_cast<hipStream_t>(stream));
 }
 
+int rns_tx_udp_send_pool_dev(const uint8_t *d_data, uint64_t data_bytes, const rns_udp_rec *d_rec, uint32_t n_recs,
+                             const uint32_t *d_q_first, const uint16_t *d_sock_port, uint32_t n_socks,
+                             const uint8_t *local_ipv4, const uint8_t *local_ipv6, uint8_t *d_tx_pool,
+                             uint64_t tx_pool_bytes, uint32_t buf_log2, const uint32_t *d_free, uint32_t n_free,
+                             uint32_t send_cap, uint16_t ip_id_base, const uint32_t *d_ip_id_add, uint32_t *d_tx_blk_first,
+                             uint8_t *d_tx_head_len8, uint16_t *d_tx_pay_len16, uint32_t *d_tx_src, uint32_t *d_count,
+                             uint8_t *d_send, void *d_work, uint64_t work_bytes, void *stream)
+{
+    static_assert(sizeof(rns_udp_rec) == 32, "rns_k_udp_tx.hpp: a record is two 16-byte loads");
+    if (n_recs == 0) {  // no record: the counts alone
+        if (!d_count || misaligned(d_count, 3))
+            return RNS_E_INVALID;
+        RNS_TRY(check_device());
+        return hip_status(hipMemsetAsync(d_count, 0, 12, static_cast<hipStream_t>(stream)));
+    }
+    // every rejection, before the device is touched
+    if (buf_log2 < kUdpTxMinLog2 || buf_log2 > kPoolMaxLog2 || n_recs > RNS_CHAIN_MAX_PACKETS || n_socks == 0 ||
+        n_socks > RNS_UDP_MAX_SOCKS || !d_data || !d_rec || !d_q_first || !d_sock_port || !local_ipv4 || !local_ipv6 ||
+        !d_tx_pool || !d_count || !d_send || !d_work || (n_free && !d_free) ||
+        (send_cap && (!d_tx_blk_first || !d_tx_head_len8 || !d_tx_pay_len16)) || misaligned(d_data, 15) ||
+        misaligned(d_rec, 15) || misaligned(d_tx_pool, 15) || misaligned(d_q_first, 3) || misaligned(d_sock_port, 1) ||
+        misaligned(d_free, 3) || misaligned(d_ip_id_add, 3) || misaligned(d_tx_blk_first, 3) ||
+        misaligned(d_tx_pay_len16, 1) || misaligned(d_tx_src, 3) || misaligned(d_count, 3) || misaligned(d_work, 7) ||
+        work_bytes < udp_tx_work_bytes(n_recs))
+        return RNS_E_INVALID;
+    RNS_TRY(check_device());
+    UdpTxArgs a{};
+    a.data = d_data;
+    a.data_bytes = data_bytes;
+    a.rec_in = reinterpret_cast<const uint4 *>(d_rec);
+    a.q_first = d_q_first;
+    a.sock_port = d_sock_port;
+    a.tx_pool = d_tx_pool;
+    a.tx_bufs = tx_pool_bytes >> buf_log2;
+    a.free = d_free;
+    a.ip_id_add = d_ip_id_add;
+    a.tx_blk_first = d_tx_blk_first;
+    a.tx_head_len8 = d_tx_head_len8;
+    a.tx_pay_len16 = d_tx_pay_len16;
+    a.tx_src = d_tx_src;
+    a.count = d_count;
+    a.send = d_send;
+    a.part_a = static_cast<uint2 *>(d_work);
+    a.part_b = a.part_a + scan_blocks(n_recs) + 1;
+    a.rec = reinterpret_cast<uint32_t *>(a.part_b + scan_blocks(n_recs) + 1);
+    std::memcpy(&a.local4, local_ipv4, 4);
+    std::memcpy(a.local6, local_ipv6, 16);
+    a.n_recs = n_recs;
+    a.n_socks = n_socks;
+    a.blog = buf_log2;
+    a.n_free = n_free;
+    a.send_cap = send_cap;
+    a.ip_id_base = ip_id_base;
+    return launch_tx_udp(a, static_cast<hipStream_t>(stream));
+}
+
 int rns_rx_tcp_flow_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,
                                const rns_tcp_flow *d_flow_in, const uint32_t *d_pend_in, uint32_t pend_cap,
                                rns_tcp_flow *d_flow_out, uint32_t *d_pend_out, rns_rx_tcp_seg *d_seg,

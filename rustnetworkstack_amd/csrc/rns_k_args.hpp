@@ -1,6 +1,7 @@
 // What every translation unit sees of the entry points that are sequences of launches: their kernel
 // arguments, constants and workspace sizes.  Their kernels are no templates, so each family's header is
-// included by the one translation unit that launches it (k_flow.hip, k_plan.hip, k_echo.hip, k_udp.hip).
+// included by the one translation unit that launches it (k_flow.hip, k_plan.hip, k_echo.hip, k_udp.hip,
+// k_udp_tx.hip).
 // (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
 #pragma once
 
@@ -142,5 +143,35 @@ inline uint64_t udp_work_bytes(uint64_t n_pkts, uint64_t n_socks)
     const uint64_t m = n_socks * udp_tiles(n_pkts);
     return 8ull * (scan_blocks(m) + 1) + 8ull * m + 4ull * n_pkts;
 }
+
+// --- the UDP send build (rns_k_udp_tx.hpp) ---
+constexpr uint32_t kUdpTxMinLog2 = 8;  // the transmit pool form's: a head fits its buffer
+
+struct UdpTxArgs {
+    const uint8_t *data;       // 16-byte aligned: the payloads, record k's at 16 * off16
+    uint64_t data_bytes;
+    const uint4 *rec_in;       // two per record (rns_udp_rec)
+    const uint32_t *q_first;   // n_socks + 1
+    const uint16_t *sock_port; // n_socks
+    uint8_t *tx_pool;
+    uint64_t tx_bufs;          // whole buffers of the transmit pool
+    const uint32_t *free;
+    const uint32_t *ip_id_add;
+    uint32_t *tx_blk_first;
+    uint8_t *tx_head_len8;
+    uint16_t *tx_pay_len16;
+    uint32_t *tx_src;
+    uint32_t *count;
+    uint8_t *send;
+    uint32_t *rec;             // workspace: a dword per record
+    uint2 *part_a;             // workspace: the workgroups' (payload buffers, sends), blocks + 1
+    uint2 *part_b;             // workspace: the workgroups' (IPv4 sends, 0), blocks + 1
+    uint32_t local4;           // the local addresses as they lie in memory
+    uint32_t local6[4];
+    uint32_t n_recs, n_socks, blog, n_free, send_cap, ip_id_base;
+};
+
+// The workspace, 8-byte aligned: the two arrays of block sums, then the records' dwords.
+inline uint64_t udp_tx_work_bytes(uint64_t n_recs) { return 16ull * (scan_blocks(n_recs) + 1) + 4ull * n_recs; }
 
 }  // namespace rns

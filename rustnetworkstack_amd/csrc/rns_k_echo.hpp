@@ -86,10 +86,8 @@ __global__ __launch_bounds__(kScanBlock) void echo_classify_kernel(const EchoArg
 }
 
 // Stores the chunk whole (zeros after a payload's last byte) and adds its little-endian word sum to its
-// datagram's in LDS.  A datagram's chunks are consecutive lanes, so its sum over this step is a range of
-// the wave's prefix sum (DPP, no LDS round trip), as the rows kernels take a packet's: the datagram's last
-// lane of the step subtracts the prefix before its first lane — lane - min(c, lane), c the chunk's index in
-// its payload — and adds the range.  (Called by the whole wave.)
+// datagram's in LDS (wave_dgram_sum, rns_k_pool_view.hpp, which the UDP send build shares).  (Called by the
+// whole wave.)
 __device__ __forceinline__ void echo_emit(const PlaceChunk &ck, const uint4 y, uint32_t (&pd)[kEchoPd][64], uint32_t lane)
 {
     uint32_t sum = 0;
@@ -104,13 +102,7 @@ __device__ __forceinline__ void echo_emit(const PlaceChunk &ck, const uint4 y, u
         *reinterpret_cast<uint4 *>(ck.dc) = make_uint4(o[0], o[1], o[2], o[3]);
         sum = sad4(make_uint4(o[0], o[1], o[2], o[3]), 0u);  // <= 8 * 0xffff
     }
-    const uint32_t S = wave_incl_scan(sum);  // <= 64 * 8 * 0xffff
-    const uint32_t a = lane - min(ck.c, lane);
-    const uint32_t before = static_cast<uint32_t>(__shfl(static_cast<int>(S), static_cast<int>(max(a, 1u)) - 1, 64));
-    const uint32_t jn = static_cast<uint32_t>(__shfl_down(static_cast<int>(ck.j), 1, 64));
-    if (ck.hi != 0 && (lane == 63u || jn != ck.j))
-        pd[kEchoPdSum][ck.j] += S - (a ? before : 0u);  // one lane per datagram; a payload's sum stays below 4096 * 8 * 0xffff < 2^32
-    wave_lds_fence();
+    wave_dgram_sum(sum, ck.j, ck.c, ck.hi != 0, lane, pd[kEchoPdSum]);
 }
 
 template <bool NT>

@@ -238,6 +238,23 @@ __device__ __forceinline__ void place_emit_whole(PlaceChunk ck, const uint4 y)
     place_emit(ck, y);
 }
 
+// A chunk's word sum added to its datagram's in the LDS row `row`, for the builders that checksum what they
+// copy (the echo responder, the UDP send build): lane by lane the wave holds 64 consecutive chunks of its
+// concatenated datagrams, this lane chunk c of datagram j (has: it holds one).  A datagram's chunks are
+// consecutive lanes, so its sum over this step is a range of the wave's prefix sum (DPP, no LDS round trip),
+// as the rows kernels take a packet's: the datagram's last lane of the step subtracts the prefix before its
+// first lane — lane - min(c, lane) — and adds the range.  (Called by the whole wave.)
+__device__ __forceinline__ void wave_dgram_sum(uint32_t sum, uint32_t j, uint32_t c, bool has, uint32_t lane, uint32_t (&row)[64])
+{
+    const uint32_t S = wave_incl_scan(sum);  // <= 64 * 8 * 0xffff
+    const uint32_t a = lane - min(c, lane);
+    const uint32_t before = static_cast<uint32_t>(__shfl(static_cast<int>(S), static_cast<int>(max(a, 1u)) - 1, 64));
+    const uint32_t jn = static_cast<uint32_t>(__shfl_down(static_cast<int>(j), 1, 64));
+    if (has && (lane == 63u || jn != j))
+        row[j] += S - (a ? before : 0u);  // one lane per datagram; a payload's sum stays below 4096 * 8 * 0xffff < 2^32
+    wave_lds_fence();
+}
+
 // The walk over the wave's W concatenated destination chunks (W wave-uniform, the table written and
 // fenced): mis and dst say where a chunk goes (pool_chunk), emit(chunk, second source chunk) stores it.
 template <bool NT, int ROWS, class Mis, class Dst, class Emit>

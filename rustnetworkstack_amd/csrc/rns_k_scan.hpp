@@ -1,5 +1,6 @@
 // The grid-wide exclusive prefix sum of pairs of u32, 256 per workgroup, in three launches on one
-// stream, for the flow update, the ACK build, the send planning, the echo responder and the UDP demux:
+// stream, for the flow update, the ACK build, the send planning, the echo responder, the UDP demux and the
+// UDP send build:
 //   1. scan2_reduce_kernel<V, A>: part[b] = block b's sum of V::value(a, i) (or the user's own kernel).
 //   2. scan2_parts_kernel, one workgroup: part[0..nb) to its exclusive prefix sums, part[nb] = the total.
 //      It is no template, so k_scan.hip alone compiles it, with its launcher launch_scan2_parts.

@@ -8,8 +8,16 @@ a 32-byte record and a payload copied to a 16-byte-aligned place, the records an
 socket contiguous and in arrival order (rns_rx_udp_demux_pool_dev).  ``demux_host`` is the same function
 in numpy over a host pool — the host's path for the entries the device leaves (``RNS_UDP_NOROOM``) and
 what the GPU tests compare with — ``drain`` the list repeated udp_recv calls would return, and
-``udp_demux`` one receive -> device -> drain step.  The functions are re-exported by ``batch``, whose
-argument checks they use.
+``udp_demux`` one receive -> device -> drain step.
+
+The send build is the other half: udp_send -> udp_output -> ip_output_v4 / ip_output_v6 (udp.rs:101-114 and
+150-173, ip.rs:133-177) for a batch.  ``tx_udp_send_pool`` reads the demux's records as sends back to their
+senders (or a host's own records) and builds every datagram, both checksums filled, in a transmit pool in the
+form ``pool.tx_fill_pool`` and ``pool.send_batch_pool`` take (rns_tx_udp_send_pool_dev); ``send_host`` is the
+same function in numpy — the host's path for what the device leaves (``RNS_UDPTX_NOBUF``) — and ``udp_echo`` the
+reference's udp_echo application as one receive -> demux -> send -> sendmmsg step.
+
+The functions are re-exported by ``batch``, whose argument checks they use.
 """
 from __future__ import annotations
 
@@ -19,8 +27,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import _U8, _U16, _call, _local_addrs, _nonnull, _per_packet, _require_cuda, _status, _work_bytes
-from .pool import _buf_log2, _host_datagrams, _new, _np, _pool_batch, recv_batch_pool
+from .batch import (_I32, _U8, _U16, _call, _descriptors, _local_addrs, _nonnull, _per_packet, _require_cuda, _status,
+                    _work_bytes, _workspace)
+from .pool import _be_sum, _buf_log2, _fold, _host_datagrams, _new, _np, _pool_batch, recv_batch_pool, send_batch_pool
 
 REC = np.dtype([("ip", "u1", 16), ("src", "<u4"), ("off16", "<u4"), ("sport", "<u2"), ("len", "<u2"), ("family", "u1"),
                 ("flags", "u1"), ("pad", "u1", 2)])  # rns_udp_rec
@@ -216,3 +225,219 @@ def udp_demux(fd: int, pool: np.ndarray, free: np.ndarray, ports, local_ipv4: by
     return n, UdpDemux(_np(r.status, np.uint8), None, _np(r.udp, np.uint8)[:n], _np(r.pos, np.uint32)[:n],
                        _np(r.rec[:32 * nrec], np.uint8).view(REC), _np(r.q_first, np.uint32), cnt,
                        _np(r.data[:16 * nunits], np.uint8))
+
+
+# ---------------------------------------------------------------------------
+# the send build: udp_send -> udp_output -> ip_output for a batch of records read as sends
+# ---------------------------------------------------------------------------
+class UdpSend(NamedTuple):
+    """What a send build leaves: torch tensors from ``tx_udp_send_pool``, numpy arrays from ``send_host`` (there
+    the descriptor arrays are cut to the built datagrams)."""
+    send: object          # uint8 [n_recs]: RNS_UDPTX_* bits
+    tx_blk_first: object  # uint32: buffers before datagram 64 * b
+    tx_head_len8: object  # uint8: 28 / 48, 0 for RNS_UDPTX_BADBUF
+    tx_pay_len16: object  # uint16
+    tx_src: object        # uint32: the record's index
+    count: object         # uint32 [3]: datagrams, buffers taken, IPv4 ids taken
+
+
+def udp_send_work(n_recs: int) -> int:
+    """Bytes of workspace ``tx_udp_send_pool`` needs for ``n_recs`` records (rns_tx_udp_send_work)."""
+    return _work_bytes("rns_tx_udp_send_work", int(n_recs))
+
+
+def tx_udp_send_pool(data: torch.Tensor, rec: torch.Tensor, q_first: torch.Tensor, sock_port: torch.Tensor,
+                     local_ipv4: bytes, local_ipv6: bytes, tx_pool: torch.Tensor, free: torch.Tensor, *,
+                     buf_bytes: int = 512, n_recs: int | None = None, send_cap: int | None = None, ip_id_base: int = 0,
+                     ip_id_add: torch.Tensor | None = None, send: torch.Tensor | None = None,
+                     tx_blk_first: torch.Tensor | None = None, tx_head_len8: torch.Tensor | None = None,
+                     tx_pay_len16: torch.Tensor | None = None, tx_src: torch.Tensor | None = None,
+                     count: torch.Tensor | None = None, work: torch.Tensor | None = None) -> UdpSend:
+    """UDP send build over pool buffers (rns_tx_udp_send_pool_dev).  ``data`` / ``rec`` / ``q_first`` as
+    ``rx_udp_demux_pool`` leaves them (``rec`` uint8, 32 bytes per record, ``REC``; ``n_recs`` defaults to all of
+    ``rec``: the records past ``q_first[-1]`` are no sends), or a host's own sends grouped by socket with flags =
+    RNS_UDP_QUEUED; ``sock_port`` = the sockets' ports, int16 / uint16 [n_socks]; ``free`` = int32 indices of free
+    buffers of ``tx_pool``, taken in order (``buf_bytes`` a power of two in 256..32768).  Record k is a send to its
+    address and port from its socket's port; every send within ``send_cap`` (default: one per record) and the
+    free list becomes a finished datagram: datagram r has its head (28 / 48 bytes, both checksums filled, source =
+    the local address, IPv4 id = ``ip_id_base`` + ``ip_id_add[0]`` + the IPv4 sends before it) at the end of its
+    first buffer and its payload in the following ones, and the datagrams' buffers are ``free[:count[1]]`` in
+    order — the ``buf_idx`` of the transmit pool form, with ``tx_blk_first`` / ``tx_head_len8`` / ``tx_pay_len16``
+    its other descriptors and ``tx_src[r]`` the record's index.  ``send[k]`` holds RNS_UDPTX_* bits; ``count`` =
+    (datagrams, buffers, IPv4 datagrams), int32 on the device: nothing is synchronised here.  Returns a
+    ``UdpSend`` of device tensors."""
+    dev = _descriptors(data, ("rec", rec, _U8), ("q_first", q_first, _I32), ("sock_port", sock_port, _U16),
+                       ("tx_pool", tx_pool, _U8), ("free", free, _I32))
+    log2 = _buf_log2(buf_bytes, 256)
+    n_socks = sock_port.numel()
+    if not 1 <= n_socks <= _lib.RNS_UDP_MAX_SOCKS or q_first.numel() < n_socks + 1:
+        raise ValueError(f"sock_port needs 1..{_lib.RNS_UDP_MAX_SOCKS} ports and q_first one entry more")
+    n = rec.numel() // 32 if n_recs is None else int(n_recs)
+    if not 0 <= n <= min(rec.numel() // 32, _lib.RNS_CHAIN_MAX_PACKETS):
+        raise ValueError("n_recs must be a count of the 32-byte records in rec")
+    for name, t in (("data", data), ("rec", rec), ("tx_pool", tx_pool)):
+        if t.data_ptr() & 15:
+            raise ValueError(f"{name} must start 16-byte aligned")
+    n_free = free.numel()
+    cap = n if send_cap is None else int(send_cap)
+    if not 0 <= cap <= _lib.RNS_CHAIN_MAX_PACKETS or not 0 <= int(ip_id_base) <= 0xFFFF:
+        raise ValueError("send_cap must be a record count and ip_id_base a u16")
+    ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
+    if ip_id_add is not None:
+        _require_cuda(ip_id_add, "ip_id_add", _I32)
+        if ip_id_add.numel() < 1 or ip_id_add.device != dev:
+            raise ValueError(f"ip_id_add must be an int32 tensor (at least 1 entry) on {dev}")
+    send = _new(send, "send", n, torch.uint8, dev)
+    tx_blk_first = _new(tx_blk_first, "tx_blk_first", (cap + 63) // 64, torch.int32, dev)
+    tx_head_len8 = _new(tx_head_len8, "tx_head_len8", cap, torch.uint8, dev)
+    tx_pay_len16 = _new(tx_pay_len16, "tx_pay_len16", cap, torch.uint16, dev)
+    tx_src = _new(tx_src, "tx_src", cap, torch.int32, dev)
+    count = _new(count, "count", 3, torch.int32, dev)
+    need = udp_send_work(n)
+    work = _workspace(work, need, dev, torch.int64, f"work needs {need} bytes (udp_send_work) on {dev}")
+    ptr = _nonnull(dev)
+    _call("rns_tx_udp_send_pool_dev", dev, ptr(data), data.numel(), ptr(rec), n, q_first.data_ptr(), sock_port.data_ptr(),
+          n_socks, ip4, ip6, ptr(tx_pool), tx_pool.numel(), log2, free.data_ptr(), n_free, cap, int(ip_id_base),
+          None if ip_id_add is None else ip_id_add.data_ptr(), tx_blk_first.data_ptr(), tx_head_len8.data_ptr(),
+          tx_pay_len16.data_ptr(), tx_src.data_ptr(), count.data_ptr(), send.data_ptr(), work.data_ptr(), work.numel() * 8)
+    return UdpSend(send, tx_blk_first, tx_head_len8, tx_pay_len16, tx_src, count)
+
+
+def send_host(data: np.ndarray, rec, q_first, sock_port, local_ipv4: bytes, local_ipv6: bytes, tx_pool: np.ndarray, free, *,
+              buf_bytes: int = 512, n_recs: int | None = None, send_cap: int | None = None, ip_id_base: int = 0,
+              ip_id_add: int = 0) -> UdpSend:
+    """``tx_udp_send_pool`` in numpy over host arrays (``data`` / ``tx_pool`` uint8, ``rec`` a ``REC`` array or its
+    bytes; ``tx_pool`` is written in place): the same sends, sockets, allocation, descriptors, counts and datagram
+    bytes — the host's path for the sends the device leaves with RNS_UDPTX_NOBUF, and what the GPU tests compare
+    with.  Returns a ``UdpSend`` of numpy arrays, the descriptor arrays cut to the built datagrams.  The bytes
+    after a payload's end in its last buffer stay as they were."""
+    B = int(buf_bytes)
+    log2 = _buf_log2(B, 256)
+    ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
+    rec = _np(rec, np.uint8)
+    rec = rec[:rec.size // 32 * 32].view(REC)
+    q = np.asarray(q_first, dtype=np.uint32).astype(np.int64)
+    ports = np.asarray(sock_port).astype(np.uint16)
+    n_socks = len(ports)
+    if not 1 <= n_socks <= _lib.RNS_UDP_MAX_SOCKS or len(q) < n_socks + 1:
+        raise ValueError(f"sock_port needs 1..{_lib.RNS_UDP_MAX_SOCKS} ports and q_first one entry more")
+    free = np.asarray(free, dtype=np.uint32).astype(np.int64)
+    n, n_free = len(rec) if n_recs is None else int(n_recs), len(free)
+    cap = n if send_cap is None else int(send_cap)
+    tx_bufs = tx_pool.size >> log2
+    send = np.zeros(n, np.uint8)
+    heads, pays, srcs, firsts = [], [], [], []
+    R = F = V = 0
+    full = False
+    for k in range(min(n, int(q[n_socks]))):
+        r = rec[k]
+        fam, ln, at = int(r["family"]), int(r["len"]), 16 * int(r["off16"])
+        if not int(r["flags"]) & _lib.RNS_UDP_QUEUED or fam not in (4, 6) or at + ln > data.size:
+            continue
+        s = max(int(np.searchsorted(q[:n_socks], k, side="right")) - 1, 0)
+        pay = data[at:at + ln].tobytes()
+        nfr = 1 + -(-ln // B)
+        R, F = R + 1, F + nfr
+        if full or R > cap or F > n_free:
+            full = True  # (both counts are monotone: every later send is past them too)
+            send[k] = _lib.RNS_UDPTX_SEND | _lib.RNS_UDPTX_NOBUF
+            continue
+        bufs = free[F - nfr:F]
+        if (R - 1) % 64 == 0:
+            firsts.append(F - nfr)
+        pays.append(ln)
+        srcs.append(k)
+        if (bufs >= tx_bufs).any():
+            send[k] = _lib.RNS_UDPTX_SEND | _lib.RNS_UDPTX_BADBUF
+            heads.append(0)
+            V += 1 if fam == 4 else 0
+            continue
+        send[k] = _lib.RNS_UDPTX_SEND | _lib.RNS_UDPTX_BUILT
+        ulen = (8 + ln) & 0xFFFF  # udp.rs:152 `as u16`
+        dst = r["ip"][:4 if fam == 4 else 16].tobytes()
+        src = ip4 if fam == 4 else ip6
+        udp = bytearray(int(ports[s]).to_bytes(2, "big") + int(r["sport"]).to_bytes(2, "big") + ulen.to_bytes(2, "big") + b"\0\0")
+        udp[6:8] = (_fold(_be_sum(src) + _be_sum(dst) + 17 + ulen + _be_sum(udp) + _be_sum(pay)) ^ 0xFFFF).to_bytes(2, "big")
+        if fam == 6:
+            ip = bytes([0x60, 0, 0, 0]) + ulen.to_bytes(2, "big") + bytes([17, 64]) + ip6 + dst
+        else:
+            ipb = bytearray([0x45, 0]) + ((28 + ln) & 0xFFFF).to_bytes(2, "big") + \
+                ((int(ip_id_base) + int(ip_id_add) + V) & 0xFFFF).to_bytes(2, "big") + bytes([0, 0, 64, 17, 0, 0]) + ip4 + dst
+            ipb[10:12] = (_fold(_be_sum(ipb)) ^ 0xFFFF).to_bytes(2, "big")
+            ip = bytes(ipb)
+            V += 1
+        head = ip + bytes(udp)
+        heads.append(len(head))
+        at = (int(bufs[0]) << log2) + B - len(head)
+        tx_pool[at:at + len(head)] = np.frombuffer(head, dtype=np.uint8)
+        for j in range(nfr - 1):
+            part = pay[j * B:(j + 1) * B]
+            at = int(bufs[1 + j]) << log2
+            tx_pool[at:at + len(part)] = np.frombuffer(part, dtype=np.uint8)
+    nbuf = int(sum(1 + -(-p // B) for p in pays))
+    return UdpSend(send, np.array(firsts, dtype=np.uint32), np.array(heads, dtype=np.uint8), np.array(pays, dtype=np.uint16),
+                   np.array(srcs, dtype=np.uint32), np.array([len(pays), nbuf, V], dtype=np.uint32))
+
+
+def udp_echo(fd_in: int, fd_out: int, rx_pool: np.ndarray, rx_free: np.ndarray, tx_pool: np.ndarray, tx_free: np.ndarray,
+             ports, local_ipv4: bytes, local_ipv6: bytes, *, buf_bytes: int = 512, mru: int = 2048,
+             max_pkts: int | None = None, rec_cap: int | None = None, send_cap: int | None = None, ip_id_base: int = 0,
+             device: str = "cuda:0", timeout_ms: int = 0):
+    """The reference's udp_echo application (udp_recv, then udp_send back to the sender) for one batch:
+    ``recv_batch_pool`` from ``fd_in`` into the host ``rx_pool``, the used buffers to the device,
+    ``rx_udp_demux_pool`` over the sockets bound to ``ports``, ``tx_udp_send_pool`` over its records with nothing read
+    back in between, the 12-byte count read back, only the buffers ``tx_free[:count[1]]`` copied back into
+    ``tx_pool``, and ``send_batch_pool`` to ``fd_out``.  Every buffer is free again when a ``send_batch_pool``
+    returns (the free lists are the caller's arrays, unchanged), so the entries the device left — RNS_UDP_NOROOM
+    of the demux, RNS_UDPTX_NOBUF of the send build — are then answered from the host ``rx_pool`` by ``demux_host``
+    and ``send_host`` in as many further sends as the transmit pool asks for: nothing the reference would answer is
+    dropped (a datagram that needs more buffers than ``tx_free`` holds raises).  Returns ``(datagrams received,
+    datagrams sent, udp uint8 [n], (entries, built on the device, built on the host))``."""
+    B = int(buf_bytes)
+    ports = list(ports)
+    n, len16, blk_first, nf = recv_batch_pool(fd_in, rx_pool, rx_free, B, mru, max_pkts, timeout_ms)
+    if n == 0 or not ports:
+        return n, 0, np.zeros(n, np.uint8), (0, 0, 0)
+    dev = torch.device(device)
+    rows = rx_pool.reshape(-1, B)
+    used = torch.from_numpy(rx_free[:nf].astype(np.int64))
+    d_rx = torch.zeros(rows.shape, dtype=torch.uint8, device=dev)
+    d_rx[used.to(dev)] = torch.from_numpy(rows[rx_free[:nf]]).to(dev)  # the received buffers only
+    d_tx = torch.zeros(tx_pool.size, dtype=torch.uint8, device=dev)
+    to_dev = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).to(dev)  # noqa: E731
+    cap = n if rec_cap is None else int(rec_cap)
+    d_rec = torch.zeros(32 * max(cap, 1), dtype=torch.uint8, device=dev)  # zeroed: a record the cut leaves is no send
+    r = rx_udp_demux_pool(d_rx.reshape(-1), to_dev(rx_free[:nf].astype(np.uint32), np.int32),
+                          to_dev(blk_first.astype(np.uint32), np.int32), to_dev(len16, np.int16), local_ipv4, local_ipv6,
+                          to_dev(port_table(ports), np.int16), len(ports), buf_bytes=B, rec_cap=cap, rec=d_rec)
+    s = tx_udp_send_pool(r.data, r.rec, r.q_first, to_dev(np.array(ports, dtype=np.uint16), np.int16), local_ipv4, local_ipv6,
+                         d_tx, to_dev(tx_free.astype(np.uint32), np.int32), buf_bytes=B, n_recs=cap, send_cap=send_cap,
+                         ip_id_base=ip_id_base)
+    cnt = _np(s.count, np.uint32)  # the one synchronisation: 12 bytes
+    nbuilt, nbuf, ids = int(cnt[0]), int(cnt[1]), int(cnt[2])
+    sent = 0
+    if nbuilt:
+        taken = tx_free[:nbuf].astype(np.int64)
+        tx_pool.reshape(-1, B)[taken] = d_tx.reshape(-1, B)[torch.from_numpy(taken).to(dev)].cpu().numpy()
+        sent = send_batch_pool(fd_out, tx_pool, tx_free[:nbuf], _np(s.tx_blk_first, np.uint32)[:(nbuilt + 63) // 64],
+                               _np(s.tx_head_len8, np.uint8)[:nbuilt], _np(s.tx_pay_len16.view(torch.int16), np.uint16)[:nbuilt], B)
+    udp = _np(r.udp, np.uint8)[:n]
+    entries = int(_np(r.count, np.uint32)[0])
+    host_built = 0
+    if nbuilt < entries:
+        # the host's path: the whole batch demultiplexed uncut (the same positions), the device's datagrams struck out
+        h = demux_host(rx_pool, rx_free[:nf], blk_first, len16, local_ipv4, local_ipv6, port_table(ports), len(ports), buf_bytes=B)
+        done = np.zeros(entries, dtype=bool)
+        done[_np(s.tx_src, np.uint32)[:nbuilt]] = True
+        while not done.all():
+            h.rec["flags"][:entries][done] = 0
+            t = send_host(h.data, h.rec, h.q_first, ports, local_ipv4, local_ipv6, tx_pool, tx_free, buf_bytes=B,
+                          ip_id_base=(int(ip_id_base) + ids) & 0xFFFF)
+            k = int(t.count[0])
+            if k == 0:
+                raise ValueError("a datagram needs more buffers than tx_free holds")
+            sent += send_batch_pool(fd_out, tx_pool, tx_free[:int(t.count[1])], t.tx_blk_first, t.tx_head_len8, t.tx_pay_len16, B)
+            done[t.tx_src] = True
+            ids += int(t.count[2])
+            host_built += k
+    return n, sent, udp, (entries, nbuilt, host_built)

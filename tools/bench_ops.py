@@ -80,6 +80,14 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              existing copy; the queues of (a) are checked on the device before timing: d_q_first against the
              sockets' counts, and every record and payload of a sample.  Timed once per run, whatever
              --configs names
+* tx_udp   — rns_tx_udp_send_pool_dev over the demux's own records and payloads (an echo server's sends):
+             2^20 sends of 1472 bytes from 1024 sockets, 2^20 of 64 bytes from one socket, and 2^23 IMIX-sized
+             ones (workloads.imix_lengths less 28 header bytes) from 16 sockets, IPv4 into 512-byte buffers
+             drawn from a shuffled free list.  Timed in alternating rounds: (a) the send build, (b)
+             rns_tx_fill_pool_dev over the datagrams it built — the floor that copies nothing, (c) the demux
+             and then the send build, (d) the demux alone, (e) a plain device copy of the payload bytes; the
+             datagrams of (a) are compared with send_host on a sample before timing.  Timed once per run,
+             whatever --configs names
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -174,7 +182,8 @@ def main():
     ap.add_argument("--echo-shapes", default="ping84,ping1500,imix", help="rx_echo: the shapes to time")
     ap.add_argument("--echo-n", type=int, default=0, help="rx_echo: datagrams per shape (0 = 2^20 pings, 2^23 imix)")
     ap.add_argument("--udp-shapes", default="udp1500:1024,udp64:1,imix:16", help="rx_udp: shape:sockets to time")
-    ap.add_argument("--udp-n", type=int, default=0, help="rx_udp: datagrams per shape (0 = 2^20, 2^23 imix)")
+    ap.add_argument("--udp-n", type=int, default=0, help="rx_udp, tx_udp: datagrams per shape (0 = 2^20, 2^23 imix)")
+    ap.add_argument("--tx-udp-shapes", default="udp1472:1024,udp64:1,imix:16", help="tx_udp: shape (payload bytes):sockets to time")
     ap.add_argument("--tx-modes", default="plain,runs,txpacked", help="chain_fill: hint flags to time")
     args = ap.parse_args()
     ops = set(args.ops.split(","))
@@ -233,6 +242,10 @@ def main():
             for spec in args.udp_shapes.split(","):
                 shape, socks = spec.split(":")
                 r.update(bench_rx_udp(shape, int(socks), dev, args))
+        if "tx_udp" in ops and cfg == args.configs.split(",")[0]:
+            for spec in args.tx_udp_shapes.split(","):
+                shape, socks = spec.split(":")
+                r.update(bench_tx_udp(shape, int(socks), dev, args))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -1164,6 +1177,100 @@ def bench_rx_udp(shape, n_socks, dev, args, B=512):
     del pool, keep, rb
     torch.cuda.empty_cache()
     return {f"rx_udp_{shape}_{n_socks}": row}
+
+
+def bench_tx_udp(shape, n_socks, dev, args, B=512):
+    """rns_tx_udp_send_pool_dev over the demux's own output — an echo server's sends — against
+    rns_tx_fill_pool_dev over the datagrams it built (the floor that copies nothing), the demux followed by the
+    send build against the demux alone, and a plain device copy of the payload bytes, in alternating rounds."""
+    from rustnetworkstack_amd.batch import (demux_work, port_table, rx_udp_demux_pool, send_host, tx_fill_pool, tx_udp_send_pool,
+                                            udp_send_work)
+    n = args.udp_n or (1 << 23 if shape == "imix" else 1 << 20)
+    rx_shape = shape if shape == "imix" else f"udp{int(shape[3:]) + 28}"  # the received datagram: 28 bytes of headers more
+    pool, idx, blk, len16, T, sock, ports, nf = _udp_batch(rx_shape, n, n_socks, dev, B)
+    pay = T - 28
+    units = -(-pay // 16)
+    tbl = torch.from_numpy(port_table(ports).view(np.int16)).to(dev)
+    dm = dict(status=torch.empty(n, dtype=torch.uint8, device=dev), udp=torch.empty(n, dtype=torch.uint8, device=dev),
+              pos=torch.empty(n, dtype=torch.int32, device=dev), rec=torch.zeros(32 * n, dtype=torch.uint8, device=dev),
+              data=torch.empty(16 * int(units.sum()) + 16, dtype=torch.uint8, device=dev),
+              q_first=torch.empty(n_socks + 1, dtype=torch.int32, device=dev), count=torch.empty(2, dtype=torch.int32, device=dev),
+              work=torch.empty((demux_work(n, n_socks) + 15) // 8, dtype=torch.int64, device=dev))
+
+    def demux():
+        rx_udp_demux_pool(pool, idx, blk, len16, L4, L6, tbl, n_socks, buf_bytes=B, **dm)
+
+    demux()
+    nbuf = int((1 + -(-pay // B)).sum())
+    free_h = np.random.default_rng(18).permutation(nbuf).astype(np.uint32)
+    free = torch.from_numpy(free_h.view(np.int32)).to(dev)
+    tx = torch.zeros(nbuf * B, dtype=torch.uint8, device=dev)
+    d_ports = torch.from_numpy(ports.astype(np.uint16).view(np.int16)).to(dev)
+    keep = dict(send=torch.empty(n, dtype=torch.uint8, device=dev), tx_blk_first=torch.empty((n + 63) // 64, dtype=torch.int32, device=dev),
+                tx_head_len8=torch.empty(n, dtype=torch.uint8, device=dev), tx_pay_len16=torch.empty(n, dtype=torch.uint16, device=dev),
+                tx_src=torch.empty(n, dtype=torch.int32, device=dev), count=torch.empty(3, dtype=torch.int32, device=dev),
+                work=torch.empty((udp_send_work(n) + 7) // 8, dtype=torch.int64, device=dev))
+
+    def send():
+        tx_udp_send_pool(dm["data"], dm["rec"], dm["q_first"], d_ports, L4, L6, tx, free, buf_bytes=B, ip_id_base=1, **keep)
+
+    send()
+    torch.cuda.synchronize()
+    cnt = keep["count"].cpu().numpy().view(np.uint32)
+    assert cnt.tolist() == [n, nbuf, n], cnt
+    assert int((keep["send"] == 3).sum().item()) == n
+    # a sample against the host path: the first 256 records' datagrams, byte for byte
+    m = 256
+    rec_h = dm["rec"][:32 * m].cpu().numpy()
+    from rustnetworkstack_amd.udp import REC
+    r256 = rec_h.view(REC)
+    end = int((r256["off16"].astype(np.int64) + -(-r256["len"].astype(np.int64) // 16)).max())
+    k = int((1 + -(-r256["len"].astype(np.int64) // B)).sum())
+    txh = np.zeros(k * B, dtype=np.uint8)
+    qh = np.minimum(dm["q_first"].cpu().numpy().view(np.uint32), m)
+    e = send_host(dm["data"][:16 * end].cpu().numpy(), r256, qh, ports, L4, L6, txh, np.arange(k, dtype=np.uint32), buf_bytes=B, ip_id_base=1)
+    assert int(e.count[0]) == m and int(e.count[1]) == k
+    got = tx.view(-1, B)[torch.from_numpy(free_h[:k].astype(np.int64)).to(dev)].cpu().numpy()
+    want, nb = txh.reshape(-1, B), 0
+    for hl, pl in zip(e.tx_head_len8.tolist(), e.tx_pay_len16.tolist()):  # the head's bytes and the payload's, not the slack after them
+        npay = -(-pl // B)
+        assert np.array_equal(got[nb, B - hl:], want[nb, B - hl:])
+        assert np.array_equal(got[nb + 1:nb + 1 + npay].reshape(-1)[:pl], want[nb + 1:nb + 1 + npay].reshape(-1)[:pl])
+        nb += 1 + npay
+    assert nb == k
+    tst = torch.empty(n, dtype=torch.uint8, device=dev)
+
+    def fill():
+        tx_fill_pool(tx, free, keep["tx_blk_first"], keep["tx_head_len8"], keep["tx_pay_len16"], buf_bytes=B, status=tst)
+
+    fill()
+    torch.cuda.synchronize()
+    assert int((tst == 3).sum().item()) == n
+
+    def demux_send():
+        demux()
+        send()
+
+    pay_bytes = int(pay.sum())
+    src_copy = dm["data"][:pay_bytes]
+    dst_copy = torch.empty(pay_bytes, dtype=torch.uint8, device=dev)
+
+    def copy():
+        dst_copy.copy_(src_copy)
+
+    names = ("send", "fill", "demux_send", "demux", "copy")
+    rs = timed_rounds([send, fill, demux_send, demux, copy], args.steps, args.rounds)
+    med = [r[len(r) // 2] for r in rs]
+    row = {"sends": n, "sockets": n_socks, "tx_buffers": nbuf, "payload_bytes": pay_bytes, "work_bytes": udp_send_work(n),
+           "send_us": round(med[0] * 1e3, 1), "fill_us": round(med[1] * 1e3, 1), "demux_send_us": round(med[2] * 1e3, 1),
+           "demux_us": round(med[3] * 1e3, 1), "copy_us": round(med[4] * 1e3, 1),
+           "send_over_fill": round(med[0] / med[1], 3), "send_over_copy": round(med[0] / med[4], 3),
+           "demux_send_minus_demux_us": round((med[2] - med[3]) * 1e3, 1),
+           "send_GBps_read_plus_written": round((2 * pay_bytes + 32 * n + (28 + 7) * n) / med[0] / 1e6, 1),
+           "rounds_us": {k: [round(x * 1e3, 1) for x in r] for k, r in zip(names, rs)}}
+    del pool, dm, keep, tx, dst_copy
+    torch.cuda.empty_cache()
+    return {f"tx_udp_{shape}_{n_socks}": row}
 
 
 def bench_chain_netbuf(lay, dev, args, shuffled=False, runs=False):
