@@ -845,6 +845,135 @@ int rns_tx_ack_build_dev(const rns_rx_tcp_meta *d_meta, const rns_rx_tcp_seg *d_
                          uint8_t *d_out, uint32_t ack_cap, uint32_t *d_ack_src, uint8_t *d_ack_len8,
                          uint32_t *d_n_acks /* 2 */, void *stream);
 
+/* TCP listen responder over pool buffers: tcp_input's branch for a segment whose key is not in PORT_MAP
+ * (tcp.rs:579-615) with handle_new_connection (tcp.rs:894-936), send_packet, tcp_output and ip_output on
+ * the device.  It takes over the branch rns_rx_tcp_place_pool_dev leaves to the host (RNS_PLACE_TCP without
+ * RNS_PLACE_FLOW): it reads the placement's d_meta as it is, over the same pool and descriptors, and builds
+ * the RST|ACK of every stray segment, the SYN|ACK of every new connection and the new socket's state, the
+ * replies in 64-byte slots as rns_tx_ack_build_dev leaves its ACKs.  The verify is not run again and there
+ * is no d_status: a decoded meta record says the datagram was accepted.  Every rule is a line of the
+ * reference, restated for a batch processed in index order.
+ * The form is defined by what it expands to:
+ *   Unmatched: datagram i is unmatched (RNS_CONN_UNMATCHED) iff d_meta[i].place has RNS_PLACE_TCP and not
+ *     RNS_PLACE_FLOW.  Everything else has d_conn[i] == 0.  Its key (rns_rx_flow_key) is the source
+ *     address read from its first pool buffer — bytes 12..16 (IPv4) or 8..24 (IPv6), the family from the
+ *     version nibble —, d_meta[i].sport and d_meta[i].dport.  What d_meta claims is checked again before a
+ *     byte of the pool is read, as the consumers of a verified batch do: the datagram's fragments inside
+ *     d_buf_idx, its first buffer inside the pool, T = d_len16[i] >= 16, the version 4 or 6, ip_hdr the
+ *     header length the first buffer gives (IHL * 4, or 40) and >= 20, 20 <= tcp_hdr <= 60 a multiple of
+ *     4, ip_hdr + tcp_hdr <= T.  A record that fails (the placement writes none) is no segment: d_conn[i]
+ *     == 0.
+ *   Candidate: an unmatched datagram is a candidate iff flags & 0x02 (SYN) and d_listen[dport] names a
+ *     listener: an entry < n_listen.  d_listen is the table rns_rx_udp_port_table_build writes, over the
+ *     listening ports.  No other flag is looked at: SYN|ACK, SYN|RST and SYN|FIN to a listening port all
+ *     open a connection in the reference, and a payload on the SYN is ignored.
+ *   First of its key: let s(key) be the smallest index among the batch's candidates with that key (the
+ *     reference inserts the new socket into PORT_MAP there, tcp.rs:611).  An unmatched datagram i is
+ *       i == s(key): a new connection, RNS_CONN_SYN if its options parse (below), else RNS_CONN_HOST: no
+ *         reply, no id, no accept record; the host's.  It still owns its key.
+ *       i > s(key): RNS_CONN_LATER, whatever became of datagram s (RNS_CONN_NOBUF or RNS_CONN_HOST too):
+ *         the reference would find the socket s created, so a duplicate SYN or the handshake's third
+ *         segment gets no RST.  The host replays it against the accept record.  No reply, no id.
+ *       otherwise (no candidate of its key at or before it): RNS_CONN_RST, a segment that itself
+ *         carries RST and a SYN to a port nobody listens on included.
+ *   Replies: reply k belongs to the k-th datagram i, in ascending i, with RNS_CONN_SYN or RNS_CONN_RST.
+ *     Its head goes to d_out + 64 * k, d_rep_src[k] = i and d_rep_len8[k] = its length, so the slots go
+ *     out through rns_io_send_batch(off = 64 * k, len).  Bytes past the length in a slot are not written.
+ *     IPv4 replies take the id ip_id_base + *d_ip_id_add (0 without it) + (the IPv4 replies among
+ *     replies 0..k-1) mod 2^16; IPv6 replies take none.
+ *   Head bytes (tcp_output -> ip_output_v4 / ip_output_v6):
+ *     IPv4: 45 00, the total length, the id, 00 00, TTL 64, protocol 6, the header checksum, source = the
+ *       local address, destination = the segment's source.
+ *     IPv6: 60 00 00 00, the payload length, next header 6, hop limit 64, the local address, the
+ *       segment's source.
+ *     TCP: source port = the segment's dport, destination port = its sport, urgent pointer 0, the
+ *       checksum over the pseudo-header of (local, remote, TCP length, 6), and
+ *                      RST (tcp.rs:582-595)            SYN-ACK (send_packet, tcp.rs:402-447)
+ *         length       40 (IPv4) / 60 (IPv6)           44 / 64
+ *         seq          1                               d_iss[a], a = its rank among the accepts
+ *         ack          d_meta[i].seq + 1 mod 2^32      the same
+ *         offset byte  0x50                            0x60
+ *         flags        0x14                            0x12
+ *         window       0                               0xffff
+ *         options      none                            02 04 05 dc
+ *     The RST's ack does not add the payload length.  The stored bytes equal what rns_tx_fill_dev
+ *     produces for the same head as a datagram without payload and with zeroed checksum fields.
+ *   Accept record: accept a is the a-th RNS_CONN_SYN datagram in ascending i.  d_accept[a] holds key, src
+ *     = i, listener = d_listen[dport], mss (below) and flow as handle_new_connection leaves the socket:
+ *     state = RNS_TCP_SYN_RECEIVED, rcv_nxt = rcv_max = seq + 1, snd_nxt = d_iss[a], snd_una = seq (the
+ *     reference stores the PEER's sequence number there, tcp.rs:917; not corrected), snd_wl1 = seq,
+ *     snd_wl2 = d_meta[i].ack, snd_wnd = d_meta[i].window, every other field 0.  The reference draws
+ *     the ISS from rand::random; here the host supplies it, so the same inputs give the same bytes on
+ *     every run.
+ *   Options: parse_options (tcp.rs:856-892) over the header bytes [20, tcp_hdr) of the first buffer
+ *     (buf_log2 >= 7 keeps them there): type 0 ends the walk, type 1 advances by 1, any other type reads
+ *     its length byte; type 2 reads the big-endian u16 at +2 as mss, whatever the length byte says, the
+ *     last such option wins; the offset then advances by the length.  mss is 0 without the option.
+ *     RNS_CONN_HOST covers the inputs on which the reference does not return: a length byte of 0 (it loops
+ *     for ever), an option type whose length byte lies past the options' end (it panics), and type 2 with
+ *     fewer than 4 bytes left (it panics).  The walk is bounded by the 40 option bytes.
+ *   Caps: a reply at or past reply_cap is counted, gets RNS_CONN_NOBUF without RNS_CONN_BUILT, and nothing
+ *     is written for it, the accept record of a SYN included: the host answers it.  Its key stays opened.
+ *     d_count = (replies, IPv4 replies, accepts), each counted as if reply_cap were unbounded, always
+ *     written; with d_count[0] <= reply_cap everything is written, otherwise replies 0 .. reply_cap - 1
+ *     and the accepts of the SYNs among them, which are a prefix of the accepts (d_conn says which).  An
+ *     accept's rank is never above its reply's, so reply_cap entries of d_accept and d_iss suffice.
+ *     reply_cap == 0 allows NULL d_out / d_rep_src / d_rep_len8 / d_accept / d_iss: the call counts and
+ *     classifies only.
+ * No byte is written outside d_out[0 .. 64 * reply_cap), the first min(count, cap) entries of the reply
+ * and accept arrays, d_count, d_conn and d_work; the pool, d_meta and d_listen are read-only.  Whatever
+ * meta, descriptors and table hold, nothing outside the arguments is read or written.  The keys of a batch
+ * meet in an open-addressing table in d_work through integer atomics; only a key's minimum candidate
+ * index is read back, which no order of the atomics changes.  The call allocates nothing: d_work is
+ * the caller's, work_bytes at least what rns_rx_tcp_listen_work gives for n_pkts (2^20 datagrams: 28
+ * MiB); its contents before and after the call mean nothing.
+ * Unpinned: a segment from 0.0.0.0 port 0 (the reference finds the listen socket itself under that key;
+ * here it is a source like any other); d_meta[i].seq + 1 for 0xffffffff (the reference's seq_num + 1
+ * overflows: a panic in a debug build, a wrap in a release one; here it wraps); the panicking decodes
+ * inherited from the placement.  The reference parses the options of every segment before the lookup;
+ * here only a first SYN's are walked.
+ * n_pkts == 0 is RNS_OK with d_count zeroed.  A NULL d_pool / d_blk_first / d_len16 / d_meta / d_count /
+ * d_conn / d_work / local address, a NULL d_buf_idx with n_frags > 0, a NULL d_listen with n_listen > 0, a
+ * NULL d_out / d_rep_src / d_rep_len8 / d_accept / d_iss with reply_cap > 0, buf_log2 outside 7..15, a
+ * d_pool that is not 16-byte aligned, a d_meta / d_accept / d_out / d_count / d_rep_src / d_iss /
+ * d_ip_id_add that is not 4-byte aligned, a d_work that is not 8-byte aligned, n_listen >
+ * RNS_UDP_MAX_SOCKS, work_bytes below the need or n_pkts > RNS_CHAIN_MAX_PACKETS is RNS_E_INVALID, all
+ * before the device is touched. */
+#define RNS_TCP_SYN_RECEIVED 2u           /* rns_tcp_flow.state of an accepted connection */
+#define RNS_CONN_UNMATCHED 0x01u  /* decoded TCP (RNS_PLACE_TCP) without RNS_PLACE_FLOW: tcp.rs:579's branch */
+#define RNS_CONN_SYN       0x02u  /* SYN to a listening port, the first of its key in the batch: a new connection */
+#define RNS_CONN_LATER     0x04u  /* an earlier SYN of this batch opened its key: the new socket's, the host's; no reply */
+#define RNS_CONN_RST       0x08u  /* answered with RST|ACK */
+#define RNS_CONN_BUILT     0x10u  /* its reply (and, for a SYN, its accept record) is written */
+#define RNS_CONN_NOBUF     0x20u  /* a reply at or past reply_cap: counted, nothing written, the host answers */
+#define RNS_CONN_HOST      0x40u  /* a first SYN whose options the device does not parse: the host's; no reply */
+typedef struct rns_tcp_accept {   /* 72 bytes */
+    rns_rx_flow_key key;          /* what handle_new_connection inserts into PORT_MAP */
+    rns_tcp_flow    flow;         /* the new socket's state after handle_new_connection */
+    uint32_t        src;          /* the SYN's datagram index */
+    uint16_t        listener;     /* the listen table's entry for its destination port */
+    uint16_t        mss;          /* parse_options' max_segment_size, 0 without the option */
+} rns_tcp_accept;
+int rns_rx_tcp_listen_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2,
+                               const uint32_t *d_buf_idx, uint32_t n_frags,
+                               const uint32_t *d_blk_first,   /* (n_pkts + 63) / 64 entries */
+                               const uint16_t *d_len16, uint32_t n_pkts,
+                               const uint8_t *local_ipv4, const uint8_t *local_ipv6,
+                               const rns_rx_tcp_meta *d_meta,          /* the placement's, as it is */
+                               const uint16_t *d_listen /* 65536 */, uint32_t n_listen,
+                               const uint32_t *d_iss,                  /* reply_cap: accept a takes d_iss[a] */
+                               uint16_t ip_id_base, const uint32_t *d_ip_id_add /* optional */,
+                               uint8_t *d_out /* 64 * reply_cap */, uint32_t reply_cap,
+                               uint32_t *d_rep_src, uint8_t *d_rep_len8,   /* reply_cap each */
+                               rns_tcp_accept *d_accept,                   /* reply_cap */
+                               uint32_t *d_count /* 3: replies, IPv4 replies, accepts */,
+                               uint8_t *d_conn /* n_pkts */,
+                               void *d_work, uint64_t work_bytes, void *stream);
+
+/* The workspace of rns_rx_tcp_listen_pool_dev (CPU only): *bytes for n_pkts datagrams, monotone in it.  A
+ * NULL bytes or n_pkts > RNS_CHAIN_MAX_PACKETS is RNS_E_INVALID. */
+int rns_rx_tcp_listen_work(uint32_t n_pkts, uint64_t *bytes);
+
 /* TCP send planning: tcp_write's window gate (tcp.rs:256-292) and retransmit (tcp.rs:329-348) on the
  * device, with the head fields send_packet sets (tcp.rs:402-447).  It reads the flow records where
  * rns_rx_tcp_flow_update_dev left them and writes exactly the descriptor set rns_tx_segment_dev takes,

@@ -24,16 +24,20 @@
                   payload in its socket's queue on the device, the queues contiguous and in arrival order;
                   the same on the host for what the device leaves — and the UDP send build: every record
                   read as a send becomes a finished datagram in a transmit pool (also ``batch.*``);
+* ``listen``    — TCP listen responder: every segment the placement decoded without a flow is answered on the
+                  device — RST|ACK for a stray, SYN|ACK and an accept record for a new connection — in batch
+                  order; the same on the host for what the device leaves (also ``batch.*``);
 * ``workloads`` — the synthetic packet batches BASELINE.json's configs name.
 """
 from . import _lib, util  # noqa: F401
 from ._lib import ChecksumError, ChecksumLibraryMissing  # noqa: F401
 
-__all__ = ["util", "batch", "pool", "segment", "place", "flow", "send", "icmp", "udp", "workloads", "ChecksumError", "ChecksumLibraryMissing"]
+__all__ = ["util", "batch", "pool", "segment", "place", "flow", "send", "icmp", "udp", "listen", "workloads", "ChecksumError",
+           "ChecksumLibraryMissing"]
 
 
 def __getattr__(name):
-    if name in ("batch", "pool", "segment", "place", "flow", "send", "icmp", "udp", "workloads"):
+    if name in ("batch", "pool", "segment", "place", "flow", "send", "icmp", "udp", "listen", "workloads"):
         import importlib
         return importlib.import_module(f".{name}", __name__)
     raise AttributeError(name)

@@ -54,6 +54,14 @@ RNS_UDPTX_SEND = 0x01     # rns_tx_udp_send_pool_dev's d_send
 RNS_UDPTX_BUILT = 0x02
 RNS_UDPTX_NOBUF = 0x04
 RNS_UDPTX_BADBUF = 0x08
+RNS_CONN_UNMATCHED = 0x01  # rns_rx_tcp_listen_pool_dev's d_conn
+RNS_CONN_SYN = 0x02
+RNS_CONN_LATER = 0x04
+RNS_CONN_RST = 0x08
+RNS_CONN_BUILT = 0x10
+RNS_CONN_NOBUF = 0x20
+RNS_CONN_HOST = 0x40
+RNS_TCP_SYN_RECEIVED = 2  # rns_tcp_flow.state of a connection the listen responder accepted
 RNS_TCP_ESTABLISHED = 1  # rns_tcp_flow.state: the only one the flow update's fast path takes
 RNS_FLOW_MAX_SEGS = 1024  # a flow's datagrams per flow-update call
 RNS_SEG_CONSUMED = 0x01
@@ -102,6 +110,8 @@ EXPORTED_SYMBOLS = (
     "rns_rx_tcp_flow_update_dev",
     "rns_rx_tcp_flow_update_work",
     "rns_tx_ack_build_dev",
+    "rns_rx_tcp_listen_pool_dev",
+    "rns_rx_tcp_listen_work",
     "rns_tx_tcp_plan_dev",
     "rns_tx_tcp_plan_work",
     "rns_tx_fill_dev",
@@ -213,6 +223,9 @@ _SIGNATURES = {
     "rns_rx_tcp_flow_update_work": (_int, [_u32, _u32, ctypes.POINTER(_u64)]),
     "rns_tx_ack_build_dev": (_int, [_vp, _vp, _u32, _vp, _u32, _vp, _u32, _vp, _u16, _vp, _u64, _vp, _u32, _vp, _vp, _vp,
                                     _vp]),
+    "rns_rx_tcp_listen_pool_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u16, _vp,
+                                          _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "rns_rx_tcp_listen_work": (_int, [_u32, ctypes.POINTER(_u64)]),
     "rns_tx_tcp_plan_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u16, _vp, _u64, _u32, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "rns_tx_tcp_plan_work": (_int, [_u32, ctypes.POINTER(_u64)]),

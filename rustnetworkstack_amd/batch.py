@@ -863,6 +863,9 @@ _ICMP_API = ("echo_host", "echo_respond", "echo_work", "rx_icmp_echo_pool")
 # batch.udp_send_work, batch.udp_echo, batch.UdpSend.
 _UDP_API = ("demux_host", "demux_work", "drain", "port_table", "rx_udp_demux_pool", "udp_demux",
             "UdpSend", "send_host", "tx_udp_send_pool", "udp_echo", "udp_send_work")
+# and the TCP listen responder (listen.py): batch.rx_tcp_listen_pool, batch.listen_host, batch.listen_work,
+# batch.tcp_listen, batch.accept_merge, batch.TcpListen.
+_LISTEN_API = ("TcpListen", "accept_merge", "listen_host", "listen_work", "rx_tcp_listen_pool", "tcp_listen")
 
 
 def __getattr__(name):
@@ -887,4 +890,7 @@ def __getattr__(name):
     if name in _UDP_API:
         from . import udp
         return getattr(udp, name)
+    if name in _LISTEN_API:
+        from . import listen
+        return getattr(listen, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

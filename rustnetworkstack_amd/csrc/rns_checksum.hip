@@ -476,6 +476,57 @@ int rns_rx_tcp_place_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
     return launch_rx_place(p, nt, static_cast<hipStream_t>(stream));
 }
 
+int rns_rx_tcp_listen_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32_t buf_log2, const uint32_t *d_buf_idx,
+                               uint32_t n_frags, const uint32_t *d_blk_first, const uint16_t *d_len16, uint32_t n_pkts,
+                               const uint8_t *local_ipv4, const uint8_t *local_ipv6, const rns_rx_tcp_meta *d_meta,
+                               const uint16_t *d_listen, uint32_t n_listen, const uint32_t *d_iss, uint16_t ip_id_base,
+                               const uint32_t *d_ip_id_add, uint8_t *d_out, uint32_t reply_cap, uint32_t *d_rep_src,
+                               uint8_t *d_rep_len8, rns_tcp_accept *d_accept, uint32_t *d_count, uint8_t *d_conn, void *d_work,
+                               uint64_t work_bytes, void *stream)
+{
+    static_assert(sizeof(rns_tcp_accept) == 72 && sizeof(rns_rx_flow_key) == 24 && sizeof(rns_tcp_flow) == 40,
+                  "rns_k_listen.hpp: an accept record is 18 dwords");
+    if (n_listen > RNS_UDP_MAX_SOCKS || !d_count || misaligned(d_count, 3))
+        return RNS_E_INVALID;
+    if (n_pkts == 0) {  // no datagram: the counts alone
+        RNS_TRY(check_device());
+        return hip_status(hipMemsetAsync(d_count, 0, 12, static_cast<hipStream_t>(stream)));
+    }
+    // every rejection, before the device is touched
+    if (!d_pool || buf_log2 < kPlaceMinLog2 || buf_log2 > kPoolMaxLog2 || !d_blk_first || !d_len16 || (n_frags && !d_buf_idx) ||
+        n_pkts > RNS_CHAIN_MAX_PACKETS || misaligned(d_pool, 15) || !local_ipv4 || !local_ipv6 || !d_meta || !d_conn ||
+        !d_work || (n_listen && !d_listen) || (reply_cap && (!d_out || !d_rep_src || !d_rep_len8 || !d_accept || !d_iss)) ||
+        misaligned(d_meta, 3) || misaligned(d_listen, 1) || misaligned(d_iss, 3) || misaligned(d_ip_id_add, 3) ||
+        misaligned(d_out, 3) || misaligned(d_rep_src, 3) || misaligned(d_accept, 3) || misaligned(d_work, 7) ||
+        work_bytes < listen_work_bytes(n_pkts))
+        return RNS_E_INVALID;
+    RNS_TRY(check_device());
+    ListenArgs a{};
+    a.rx = PoolRx{d_pool, pool_bytes, d_buf_idx, d_blk_first, d_len16, nullptr, n_pkts, n_frags, buf_log2};
+    a.meta = reinterpret_cast<const uint32_t *>(d_meta);
+    a.listen = d_listen;
+    a.iss = d_iss;
+    a.ip_id_add = d_ip_id_add;
+    a.out = d_out;
+    a.rep_src = d_rep_src;
+    a.rep_len8 = d_rep_len8;
+    a.accept = reinterpret_cast<uint32_t *>(d_accept);
+    a.count = d_count;
+    a.conn = d_conn;
+    a.slots = flow_slots(n_pkts);
+    a.part_a = static_cast<uint2 *>(d_work);
+    a.part_b = a.part_a + scan_blocks(n_pkts) + 1;
+    a.tbl = reinterpret_cast<unsigned long long *>(a.part_b + scan_blocks(n_pkts) + 1);
+    a.first = reinterpret_cast<uint32_t *>(a.tbl + a.slots);
+    a.rec = a.first + a.slots;
+    std::memcpy(&a.local4, local_ipv4, 4);
+    std::memcpy(a.local6, local_ipv6, 16);
+    a.n_listen = n_listen;
+    a.reply_cap = reply_cap;
+    a.ip_id_base = ip_id_base;
+    return launch_rx_listen(a, static_cast<hipStream_t>(stream));
+}
+
 int rns_rx_icmp_echo_pool_dev(const uint8_t *d_rx_pool, uint64_t rx_pool_bytes, uint32_t buf_log2,
                               const uint32_t *d_buf_idx, uint32_t n_frags, const uint32_t *d_blk_first,
                               const uint16_t *d_len16, uint32_t n_pkts, const uint8_t *local_ipv4,

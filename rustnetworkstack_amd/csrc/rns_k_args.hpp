@@ -1,7 +1,7 @@
 // What every translation unit sees of the entry points that are sequences of launches: their kernel
 // arguments, constants and workspace sizes.  Their kernels are no templates, so each family's header is
 // included by the one translation unit that launches it (k_flow.hip, k_plan.hip, k_echo.hip, k_udp.hip,
-// k_udp_tx.hip).
+// k_udp_tx.hip, k_listen.hip).
 // (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
 #pragma once
 
@@ -173,5 +173,37 @@ struct UdpTxArgs {
 
 // The workspace, 8-byte aligned: the two arrays of block sums, then the records' dwords.
 inline uint64_t udp_tx_work_bytes(uint64_t n_recs) { return 16ull * (scan_blocks(n_recs) + 1) + 4ull * n_recs; }
+
+// --- the TCP listen responder (rns_k_listen.hpp) ---
+struct ListenArgs {
+    PoolRx rx;                 // (status is not read: the meta records carry the verify's verdict)
+    const uint32_t *meta;      // 6 dwords per datagram
+    const uint16_t *listen;    // 65536 entries
+    const uint32_t *iss;
+    const uint32_t *ip_id_add;
+    uint8_t *out;
+    uint32_t *rep_src;
+    uint8_t *rep_len8;
+    uint32_t *accept;          // 18 dwords per record
+    uint32_t *count;
+    uint8_t *conn;
+    uint2 *part_a;             // workspace: the workgroups' (replies, IPv4 replies), blocks + 1
+    uint2 *part_b;             // workspace: the workgroups' (accepts, 0), blocks + 1
+    unsigned long long *tbl;   // workspace: the key table's slots, resident | the key's hash << 32
+    uint32_t *first;           // workspace: a slot's smallest candidate index
+    uint32_t *rec;             // workspace: a dword per datagram
+    uint64_t slots;
+    uint32_t local4;           // the local addresses as they lie in memory
+    uint32_t local6[4];
+    uint32_t n_listen, reply_cap, ip_id_base;
+};
+
+// Slots of the key table for n_pkts datagrams: the flow table's rule, a power of two >= 2 * n_pkts and >= 64.
+// The workspace, 8-byte aligned: the two arrays of block sums, the table (8 + 4 B per slot, the two arrays one after
+// the other so that one memset clears both), then the datagrams' dwords.  2^20 datagrams: 28 MiB.
+inline uint64_t listen_work_bytes(uint64_t n_pkts)
+{
+    return 16ull * (scan_blocks(n_pkts) + 1) + 12ull * flow_slots(static_cast<uint32_t>(n_pkts)) + 4ull * n_pkts;
+}
 
 }  // namespace rns

@@ -3,9 +3,9 @@
 //   k_shapes.hip, k_packed.hip, k_chain.hip, k_stash.hip  the checksum, fill, verify and finalize forms
 //   k_segment.hip, k_place.hip                            TCP segmentation offload, receive placement
 //   k_flow.hip, k_plan.hip, k_echo.hip, k_udp.hip,        the sequences of launches; each includes its own
-//   k_udp_tx.hip                                          kernels header (rns_k_flow / plan / echo / udp / udp_tx.hpp)
+//   k_udp_tx.hip, k_listen.hip                            kernels header (rns_k_flow / plan / echo / udp / udp_tx / listen.hpp)
 //   (k_place, k_echo and k_udp, the pool verify's consumers, share rns_k_pool_view.hpp: view, decode, walk)
-//   k_scan.hip                                            the scan's middle launch, which those five share
+//   k_scan.hip                                            the scan's middle launch, which those six share
 // rns_checksum.hip holds the device entry points of the C ABI, rns_pipeline.hip the host-resident
 // pipeline and the multi-GPU contexts.
 #pragma once
@@ -163,6 +163,8 @@ int launch_rx_echo(const EchoArgs &a, bool nt, hipStream_t st);
 int launch_rx_udp(const UdpArgs &a, bool nt, hipStream_t st);
 // k_udp_tx.hip: the UDP send build (classify, two scans, build)
 int launch_tx_udp(const UdpTxArgs &a, hipStream_t st);
+// k_listen.hip: the TCP listen responder (clear, classify + insert, resolve, two scans, build), after the placement
+int launch_rx_listen(const ListenArgs &a, hipStream_t st);
 // k_stash.hip: the class kernel's stash modes on one-wave workgroups
 int launch_fill(const CsumArgs &a, dim3 grid, hipStream_t st);
 int launch_rx(const CsumArgs &a, dim3 grid, hipStream_t st);

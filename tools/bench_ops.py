@@ -88,6 +88,13 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              and then the send build, (d) the demux alone, (e) a plain device copy of the payload bytes; the
              datagrams of (a) are compared with send_host on a sample before timing.  Timed once per run,
              whatever --configs names
+* rx_listen — rns_rx_tcp_listen_pool_dev behind the placement: 2^20 IPv4 SYNs with an MSS option from distinct sources
+             to one listening port, 2^20 stray 40-byte segments (all RSTs), and 2^23 IMIX-sized datagrams over 1024
+             known flows with 1 % SYNs and 1 % strays, in 512-byte buffers.  Timed in alternating rounds: (a) the
+             responder, (b) verify + placement alone (the launches it follows), (c) both, (d) rns_tx_ack_build_dev
+             over the same number of heads — the floor that classifies nothing; counts, d_conn and the replies and
+             accept records of the first 4096 datagrams are compared with listen_host before timing.  Timed once per
+             run, whatever --configs names
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -184,6 +191,8 @@ def main():
     ap.add_argument("--udp-shapes", default="udp1500:1024,udp64:1,imix:16", help="rx_udp: shape:sockets to time")
     ap.add_argument("--udp-n", type=int, default=0, help="rx_udp, tx_udp: datagrams per shape (0 = 2^20, 2^23 imix)")
     ap.add_argument("--tx-udp-shapes", default="udp1472:1024,udp64:1,imix:16", help="tx_udp: shape (payload bytes):sockets to time")
+    ap.add_argument("--listen-shapes", default="syn,stray,imix", help="rx_listen: the shapes to time")
+    ap.add_argument("--listen-n", type=int, default=0, help="rx_listen: datagrams per shape (0 = 2^20 syn / stray, 2^23 imix)")
     ap.add_argument("--tx-modes", default="plain,runs,txpacked", help="chain_fill: hint flags to time")
     args = ap.parse_args()
     ops = set(args.ops.split(","))
@@ -246,6 +255,9 @@ def main():
             for spec in args.tx_udp_shapes.split(","):
                 shape, socks = spec.split(":")
                 r.update(bench_tx_udp(shape, int(socks), dev, args))
+        if "rx_listen" in ops and cfg == args.configs.split(",")[0]:
+            for shape in args.listen_shapes.split(","):
+                r.update(bench_rx_listen(shape, dev, args))
         if "fill" in ops:
             ms = timed(lambda: csum_fill(b.arena, b.off, b.length, b.seed, field_off=16), args.steps, args.rounds)
             r["fill"] = {"us": round(ms * 1e3, 1), "GBps": round((pay + 2 * n) / ms / 1e6, 1)}
@@ -1271,6 +1283,141 @@ def bench_tx_udp(shape, n_socks, dev, args, B=512):
     del pool, dm, keep, tx, dst_copy
     torch.cuda.empty_cache()
     return {f"tx_udp_{shape}_{n_socks}": row}
+
+
+def _listen_batch(shape, n, dev):
+    """The rx_listen op's batch as an RxPlaceBatch whose pool the placement reads: syn — 44-byte IPv4 SYNs with an MSS
+    option from distinct sources to port 80; stray — 40-byte pure ACKs from distinct sources; imix — RxPlaceBatch's imix
+    over 1024 flows, of which every hundredth datagram is a SYN from a source of its own and the one after it a stray."""
+    from rustnetworkstack_amd.workloads import LOCAL4
+    B = RxPlaceBatch.BUF
+    if shape == "imix":
+        rb = RxPlaceBatch("imix", dev, n, 1024, False)
+        who = torch.arange(0, n, 100, device=dev)
+        for k, flags in ((0, 0x02), (1, 0x10)):                      # a SYN, then a stray ACK, each from 10.(2 + k).x.y:p
+            i = who + k
+            i = i[i < n]
+            at = torch.from_numpy(rb.flat_off).to(dev)[i]
+            src = i // 100
+            rb.pool[at + 13] = 2 + k
+            rb.pool[at + 14] = ((src >> 8) & 0xFF).to(torch.uint8)
+            rb.pool[at + 15] = (src & 0xFF).to(torch.uint8)
+            rb.pool[at + 20] = (4 + (src >> 16)).to(torch.uint8)     # the source port's high byte: more sources than 2^16
+            rb.pool[at + 33] = flags
+        length = torch.from_numpy(rb.d_len16.cpu().numpy().astype(np.int32)).to(dev)
+        st = tx_fill(rb.pool, torch.from_numpy(rb.flat_off).to(dev), length)
+        assert int((st != 3).sum().item()) == 0
+        return rb, (n + 99) // 100, (n + 98) // 100
+    H = 44 if shape == "syn" else 40
+    rb = RxPlaceBatch.__new__(RxPlaceBatch)
+    from rustnetworkstack_amd.batch import rx_flow_table
+    i = np.arange(n)
+    h = np.zeros((n, B), dtype=np.uint8)
+    h[:, 0], h[:, 3], h[:, 6], h[:, 8], h[:, 9] = 0x45, H, 0x40, 64, 6
+    h[:, 12], h[:, 13], h[:, 14], h[:, 15] = 10, 2 + (i >> 16), (i >> 8) & 0xFF, i & 0xFF
+    h[:, 16:20] = np.frombuffer(LOCAL4, dtype=np.uint8)
+    h[:, 20], h[:, 21], h[:, 23] = 0x90, i & 0xFF, 80
+    h[:, 24:28] = np.stack([(i >> 16) & 0xFF, (i >> 8) & 0xFF, i & 0xFF, 7 * i & 0xFF], axis=1)
+    h[:, 32], h[:, 33], h[:, 34] = (H - 20) << 2, 0x02 if shape == "syn" else 0x10, 0x20
+    if shape == "syn":
+        h[:, 40:44] = [2, 4, 0x05, 0xB4]
+    rb.pool = torch.from_numpy(h.reshape(-1)).to(dev)
+    rb.flat_off = i.astype(np.int64) * B
+    st = tx_fill(rb.pool, torch.from_numpy(rb.flat_off).to(dev), torch.full((n,), H, dtype=torch.int32, device=dev))
+    assert int((st != 3).sum().item()) == 0
+    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(dev)  # noqa: E731
+    rb.n, rb.n_flows, rb.n_frags = n, 1024, n
+    rb.d_buf_idx, rb.d_len16 = t(i, np.uint32).view(torch.int32), t(np.full(n, H), np.uint16)
+    rb.d_blk_first = t(i[::64], np.uint32).view(torch.int32)
+    rb.d_table = torch.from_numpy(rx_flow_table([(bytes([10, 1, f >> 8, f & 0xFF]), 40000 + f, 80) for f in range(1024)])).to(dev)
+    rb.d_next_seq = torch.zeros(1024, dtype=torch.int32, device=dev)
+    rb.d_win_off, rb.d_win_len = torch.zeros(1024, dtype=torch.int64, device=dev), torch.zeros(1024, dtype=torch.int32, device=dev)
+    rb.stream = torch.zeros(16, dtype=torch.uint8, device=dev)
+    rb.status, rb.l4_sum = torch.empty(n, dtype=torch.uint8, device=dev), torch.empty(n, dtype=torch.uint16, device=dev)
+    rb.meta = torch.empty((n, 24), dtype=torch.uint8, device=dev)
+    return rb, (n if shape == "syn" else 0), (0 if shape == "syn" else n)
+
+
+def bench_rx_listen(shape, dev, args):
+    """rns_rx_tcp_listen_pool_dev behind the placement, against verify + placement alone (the launches it follows) and
+    against rns_tx_ack_build_dev over the same number of heads (the floor that classifies nothing), in alternating
+    rounds; counts and a sample of replies and accept records compared with listen_host before timing."""
+    from rustnetworkstack_amd.batch import listen_host, listen_work, port_table, rx_tcp_listen_pool, rx_tcp_place_pool
+    from rustnetworkstack_amd.flow import FLOW_DTYPE, SEG_DTYPE, flow_update_work, tx_ack_build
+    from rustnetworkstack_amd.listen import ACCEPT_DTYPE
+    from rustnetworkstack_amd.place import meta_records
+    from rustnetworkstack_amd.workloads import LOCAL4, LOCAL6
+    n = args.listen_n or (1 << 23 if shape == "imix" else 1 << 20)
+    rb, syns, strays = _listen_batch(shape, n, dev)
+    replies = syns + strays
+    place = lambda: rx_tcp_place_pool(rb.pool, rb.d_buf_idx, rb.d_blk_first, rb.d_len16, LOCAL4, LOCAL6,  # noqa: E731
+                                      rb.d_table, rb.d_next_seq, rb.d_win_off, rb.d_win_len, rb.stream,
+                                      status=rb.status, l4_sum=rb.l4_sum, meta=rb.meta)
+    place()
+    tbl = torch.from_numpy(port_table([80]).view(np.int16)).to(dev)
+    iss = torch.arange(1, replies + 1, dtype=torch.int32, device=dev)
+    keep = dict(out=torch.empty(64 * replies, dtype=torch.uint8, device=dev), rep_src=torch.empty(replies, dtype=torch.int32, device=dev),
+                rep_len8=torch.empty(replies, dtype=torch.uint8, device=dev),
+                accept=torch.empty(72 * replies, dtype=torch.uint8, device=dev), count=torch.empty(3, dtype=torch.int32, device=dev),
+                conn=torch.empty(n, dtype=torch.uint8, device=dev),
+                work=torch.empty((listen_work(n) + 7) // 8, dtype=torch.int64, device=dev))
+    meta = rb.meta.reshape(-1)
+
+    def listen():
+        rx_tcp_listen_pool(rb.pool, rb.d_buf_idx, rb.d_blk_first, rb.d_len16, LOCAL4, LOCAL6, meta, tbl, 1, iss, reply_cap=replies,
+                           ip_id_base=1, **keep)
+
+    listen()
+    torch.cuda.synchronize()
+    cnt = keep["count"].cpu().numpy().view(np.uint32)
+    assert cnt.tolist() == [replies, replies, syns], (cnt, replies, syns)
+    # a sample against the host path: the first 4096 datagrams' replies and accept records, byte for byte
+    m = min(n, 4096)
+    nfh = int(rb.d_blk_first[m // 64].item()) if m < n else rb.n_frags
+    e = listen_host(rb.pool[:nfh * rb.BUF].cpu().numpy(), rb.d_buf_idx[:nfh].cpu().numpy().view(np.uint32),
+                    rb.d_blk_first[:m // 64].cpu().numpy().view(np.uint32), rb.d_len16[:m].cpu().numpy(), LOCAL4, LOCAL6,
+                    meta_records(rb.meta[:m]), port_table([80]), 1, np.arange(1, m + 1), ip_id_base=1)
+    R, A = int(e.count[0]), int(e.count[2])
+    assert R > 0 and np.array_equal(keep["conn"][:m].cpu().numpy(), e.conn)
+    lens = keep["rep_len8"][:R].cpu().numpy().astype(np.int64)
+    got = keep["out"][:64 * R].cpu().numpy().reshape(R, 64)
+    assert np.array_equal(lens, e.rep_len8[:R]) and all(np.array_equal(got[k, :lens[k]], e.out[64 * k:64 * k + lens[k]]) for k in range(R))
+    assert keep["accept"][:72 * A].cpu().numpy().tobytes() == e.accept[:A].tobytes() and ACCEPT_DTYPE.itemsize == 72
+    # the floor: the ACK build over as many heads, one flow's template, nothing classified
+    seg_h = np.zeros(n, dtype=SEG_DTYPE)
+    conn_h = keep["conn"].cpu().numpy()
+    seg_h["act"][(conn_h & 0x0A) != 0] = 2                           # an ACK where the responder answers
+    d_seg = torch.from_numpy(seg_h.view(np.uint8)).to(dev)
+    fmeta = rb.meta.clone().reshape(-1)
+    fmeta.view(torch.int32).reshape(n, 6)[:, 0] = 0                  # every ACK is flow 0's
+    tmpl, hl8 = _flow_templates(1, dev)
+    fl = torch.from_numpy(np.zeros(1, dtype=FLOW_DTYPE).view(np.uint8)).to(dev)
+    ak = dict(out=torch.empty((replies, 64), dtype=torch.uint8, device=dev), ack_src=torch.empty(replies, dtype=torch.int32, device=dev),
+              ack_len8=torch.empty(replies, dtype=torch.uint8, device=dev), n_acks=torch.empty(2, dtype=torch.int32, device=dev),
+              work=torch.empty(flow_update_work(n, 0), dtype=torch.uint8, device=dev))
+
+    def acks():
+        tx_ack_build(fmeta, d_seg, fl, tmpl, hl8, 1, ack_cap=replies, **ak)
+
+    acks()
+    torch.cuda.synchronize()
+    assert ak["n_acks"].cpu().numpy().tolist() == [replies, replies]
+
+    def place_listen():
+        place()
+        listen()
+
+    names = ("listen", "place", "place_listen", "ack_floor")
+    rs = timed_rounds([listen, place, place_listen, acks], args.steps, args.rounds)
+    med = [r[len(r) // 2] for r in rs]
+    row = {"datagrams": n, "syns": syns, "strays": strays, "replies": replies, "work_bytes": listen_work(n),
+           "listen_us": round(med[0] * 1e3, 1), "place_us": round(med[1] * 1e3, 1), "place_listen_us": round(med[2] * 1e3, 1),
+           "ack_floor_us": round(med[3] * 1e3, 1), "added_us": round((med[2] - med[1]) * 1e3, 1),
+           "added_ratio_to_place": round((med[2] - med[1]) / med[1], 4), "listen_over_ack_floor": round(med[0] / med[3], 3),
+           "rounds_us": {k: [round(x * 1e3, 1) for x in r] for k, r in zip(names, rs)}}
+    del rb, keep, ak, fmeta
+    torch.cuda.empty_cache()
+    return {f"rx_listen_{shape}": row}
 
 
 def bench_chain_netbuf(lay, dev, args, shuffled=False, runs=False):
