@@ -7,17 +7,20 @@ namespace rns {
 
 int launch_rx_echo(const EchoArgs &a, bool nt, hipStream_t st)
 {
-    const uint32_t nb = static_cast<uint32_t>(scan_blocks(a.rx.n));
-    RNS_TRY(hip_status(hipMemsetAsync(a.count, 0, 12, st)));
-    RNS_LAUNCH(echo_classify_kernel, nb, kScanBlock, st, a);
-    RNS_TRY(launch_scan2_parts(a.part_a, nb, nullptr, st));
-    RNS_TRY(launch_scan2_parts(a.part_b, nb, nullptr, st));
-    return with_flags(
-        [&](auto NT) {
-            RNS_LAUNCH(echo_build_kernel<NT()>, nb, kScanBlock, st, a);
+    return launch_build_seq(
+        a.tx.count, a.w, a.rx.n, st,
+        [&](uint32_t nb) {
+            RNS_LAUNCH(echo_classify_kernel, nb, kScanBlock, st, a);
             return static_cast<int>(RNS_OK);
         },
-        nt);
+        [&](uint32_t nb) {
+            return with_flags(
+                [&](auto NT) {
+                    RNS_LAUNCH(echo_build_kernel<NT()>, nb, kScanBlock, st, a);
+                    return static_cast<int>(RNS_OK);
+                },
+                nt);
+        });
 }
 
 }  // namespace rns

@@ -11,8 +11,8 @@ int launch_rx_listen(const ListenArgs &a, hipStream_t st)
     RNS_TRY(hip_status(hipMemsetAsync(a.tbl, 0xff, 12ull * a.slots, st)));  // every slot kListenEmpty64, kListenEmpty
     RNS_LAUNCH(listen_classify_kernel, nb, kScanBlock, st, a);
     RNS_LAUNCH(listen_resolve_kernel, nb, kScanBlock, st, a);
-    RNS_TRY(launch_scan2_parts(a.part_a, nb, nullptr, st));
-    RNS_TRY(launch_scan2_parts(a.part_b, nb, nullptr, st));
+    RNS_TRY(launch_scan2_parts(a.w.part_a, nb, nullptr, st));
+    RNS_TRY(launch_scan2_parts(a.w.part_b, nb, nullptr, st));
     RNS_LAUNCH(listen_build_kernel, nb, kScanBlock, st, a);
     return RNS_OK;
 }

@@ -7,13 +7,16 @@ namespace rns {
 
 int launch_tx_udp(const UdpTxArgs &a, hipStream_t st)
 {
-    const uint32_t nb = static_cast<uint32_t>(scan_blocks(a.n_recs));
-    RNS_TRY(hip_status(hipMemsetAsync(a.count, 0, 12, st)));
-    RNS_LAUNCH(udp_tx_classify_kernel, nb, kScanBlock, st, a);
-    RNS_TRY(launch_scan2_parts(a.part_a, nb, nullptr, st));
-    RNS_TRY(launch_scan2_parts(a.part_b, nb, nullptr, st));
-    RNS_LAUNCH(udp_tx_build_kernel, nb, kScanBlock, st, a);
-    return RNS_OK;
+    return launch_build_seq(
+        a.tx.count, a.w, a.n_recs, st,
+        [&](uint32_t nb) {
+            RNS_LAUNCH(udp_tx_classify_kernel, nb, kScanBlock, st, a);
+            return static_cast<int>(RNS_OK);
+        },
+        [&](uint32_t nb) {
+            RNS_LAUNCH(udp_tx_build_kernel, nb, kScanBlock, st, a);
+            return static_cast<int>(RNS_OK);
+        });
 }
 
 }  // namespace rns

@@ -245,6 +245,34 @@ int pool_rx_verify(PoolRx &rx, bool &nt, const uint8_t *d_pool, uint64_t pool_by
     return RNS_OK;
 }
 
+// The pool transmit form's arguments, as its builders take them (cap: the datagrams the descriptors have room for).
+bool pool_tx_valid(const uint8_t *d_tx_pool, const uint32_t *d_free, uint32_t n_free, uint32_t cap, const uint32_t *d_ip_id_add,
+                   const uint32_t *d_tx_blk_first, const uint8_t *d_tx_head_len8, const uint16_t *d_tx_pay_len16,
+                   const uint32_t *d_tx_src, const uint32_t *d_count)
+{
+    return d_tx_pool && d_count && (!n_free || d_free) && (!cap || (d_tx_blk_first && d_tx_head_len8 && d_tx_pay_len16)) &&
+           !misaligned(d_tx_pool, 15) && !misaligned(d_free, 3) && !misaligned(d_ip_id_add, 3) &&
+           !misaligned(d_tx_blk_first, 3) && !misaligned(d_tx_pay_len16, 1) && !misaligned(d_tx_src, 3) &&
+           !misaligned(d_count, 3);
+}
+
+void set_pool_tx(PoolTx &tx, uint8_t *d_tx_pool, uint64_t tx_pool_bytes, uint32_t buf_log2, const uint32_t *d_free,
+                 uint32_t n_free, uint32_t cap, uint16_t ip_id_base, const uint32_t *d_ip_id_add, uint32_t *d_tx_blk_first,
+                 uint8_t *d_tx_head_len8, uint16_t *d_tx_pay_len16, uint32_t *d_tx_src, uint32_t *d_count)
+{
+    tx = PoolTx{d_tx_pool, tx_pool_bytes >> buf_log2, d_free, d_ip_id_add, d_tx_blk_first, d_tx_head_len8, d_tx_pay_len16,
+                d_tx_src, d_count, n_free, cap, ip_id_base, buf_log2};
+}
+
+// An empty batch of an entry that leaves counts: the zeroed counts alone.
+int count_only(uint32_t *d_count, size_t bytes, void *stream)
+{
+    if (!d_count || misaligned(d_count, 3))
+        return RNS_E_INVALID;
+    RNS_TRY(check_device());
+    return hip_status(hipMemsetAsync(d_count, 0, bytes, static_cast<hipStream_t>(stream)));
+}
+
 }  // namespace
 
 extern "C" {
@@ -488,10 +516,8 @@ int rns_rx_tcp_listen_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint3
                   "rns_k_listen.hpp: an accept record is 18 dwords");
     if (n_listen > RNS_UDP_MAX_SOCKS || !d_count || misaligned(d_count, 3))
         return RNS_E_INVALID;
-    if (n_pkts == 0) {  // no datagram: the counts alone
-        RNS_TRY(check_device());
-        return hip_status(hipMemsetAsync(d_count, 0, 12, static_cast<hipStream_t>(stream)));
-    }
+    if (n_pkts == 0)  // no datagram: the counts alone
+        return count_only(d_count, 12, stream);
     // every rejection, before the device is touched
     if (!d_pool || buf_log2 < kPlaceMinLog2 || buf_log2 > kPoolMaxLog2 || !d_blk_first || !d_len16 || (n_frags && !d_buf_idx) ||
         n_pkts > RNS_CHAIN_MAX_PACKETS || misaligned(d_pool, 15) || !local_ipv4 || !local_ipv6 || !d_meta || !d_conn ||
@@ -514,13 +540,10 @@ int rns_rx_tcp_listen_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint3
     a.count = d_count;
     a.conn = d_conn;
     a.slots = flow_slots(n_pkts);
-    a.part_a = static_cast<uint2 *>(d_work);
-    a.part_b = a.part_a + scan_blocks(n_pkts) + 1;
-    a.tbl = reinterpret_cast<unsigned long long *>(a.part_b + scan_blocks(n_pkts) + 1);
+    a.tbl = static_cast<unsigned long long *>(d_work);
     a.first = reinterpret_cast<uint32_t *>(a.tbl + a.slots);
-    a.rec = a.first + a.slots;
-    std::memcpy(&a.local4, local_ipv4, 4);
-    std::memcpy(a.local6, local_ipv6, 16);
+    a.w = carve_build_work(a.first + a.slots, n_pkts);  // (12 * slots bytes on: 8-byte aligned)
+    set_local(a.local, local_ipv4, local_ipv6);
     a.n_listen = n_listen;
     a.reply_cap = reply_cap;
     a.ip_id_base = ip_id_base;
@@ -536,43 +559,24 @@ int rns_rx_icmp_echo_pool_dev(const uint8_t *d_rx_pool, uint64_t rx_pool_bytes, 
                               uint32_t *d_tx_src, uint32_t *d_count, uint8_t *d_status, uint16_t *d_l4_sum, uint8_t *d_echo,
                               void *d_work, uint64_t work_bytes, void *stream)
 {
-    if (n_pkts == 0) {  // no datagram: the counts alone
-        if (!d_count || misaligned(d_count, 3))
-            return RNS_E_INVALID;
-        RNS_TRY(check_device());
-        return hip_status(hipMemsetAsync(d_count, 0, 12, static_cast<hipStream_t>(stream)));
-    }
+    if (n_pkts == 0)  // no datagram: the counts alone
+        return count_only(d_count, 12, stream);
     // every rejection of the verify's and this entry's own, before the device is touched
     if (!pool_rx_valid(d_rx_pool, buf_log2, kEchoMinLog2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, local_ipv4,
                        local_ipv6, d_status) ||
-        !d_tx_pool || !d_count || !d_echo || !d_work || (n_free && !d_free) ||
-        (reply_cap && (!d_tx_blk_first || !d_tx_head_len8 || !d_tx_pay_len16)) || misaligned(d_tx_pool, 15) ||
-        misaligned(d_free, 3) || misaligned(d_ip_id_add, 3) || misaligned(d_tx_blk_first, 3) ||
-        misaligned(d_tx_pay_len16, 1) || misaligned(d_tx_src, 3) || misaligned(d_count, 3) || misaligned(d_work, 7) ||
-        work_bytes < echo_work_bytes(n_pkts))
+        !pool_tx_valid(d_tx_pool, d_free, n_free, reply_cap, d_ip_id_add, d_tx_blk_first, d_tx_head_len8, d_tx_pay_len16,
+                       d_tx_src, d_count) ||
+        !d_echo || !d_work || misaligned(d_work, 7) || work_bytes < echo_work_bytes(n_pkts))
         return RNS_E_INVALID;
     EchoArgs a{};
     bool nt;
     RNS_TRY(pool_rx_verify(a.rx, nt, d_rx_pool, rx_pool_bytes, buf_log2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts,
                            local_ipv4, local_ipv6, d_status, d_l4_sum, stream));
-    a.tx_pool = d_tx_pool;
-    a.tx_bufs = tx_pool_bytes >> buf_log2;
-    a.free = d_free;
-    a.ip_id_add = d_ip_id_add;
-    a.tx_blk_first = d_tx_blk_first;
-    a.tx_head_len8 = d_tx_head_len8;
-    a.tx_pay_len16 = d_tx_pay_len16;
-    a.tx_src = d_tx_src;
-    a.count = d_count;
+    set_pool_tx(a.tx, d_tx_pool, tx_pool_bytes, buf_log2, d_free, n_free, reply_cap, ip_id_base, d_ip_id_add, d_tx_blk_first,
+                d_tx_head_len8, d_tx_pay_len16, d_tx_src, d_count);
+    a.w = carve_build_work(d_work, n_pkts);
+    set_local(a.local, local_ipv4, local_ipv6);
     a.echo = d_echo;
-    a.part_a = static_cast<uint2 *>(d_work);
-    a.part_b = a.part_a + scan_blocks(n_pkts) + 1;
-    a.rec = reinterpret_cast<uint32_t *>(a.part_b + scan_blocks(n_pkts) + 1);
-    std::memcpy(&a.local4, local_ipv4, 4);
-    std::memcpy(a.local6, local_ipv6, 16);
-    a.n_free = n_free;
-    a.reply_cap = reply_cap;
-    a.ip_id_base = ip_id_base;
     return launch_rx_echo(a, nt, static_cast<hipStream_t>(stream));
 }
 
@@ -630,21 +634,15 @@ int rns_tx_udp_send_pool_dev(const uint8_t *d_data, uint64_t data_bytes, const r
                              uint8_t *d_send, void *d_work, uint64_t work_bytes, void *stream)
 {
     static_assert(sizeof(rns_udp_rec) == 32, "rns_k_udp_tx.hpp: a record is two 16-byte loads");
-    if (n_recs == 0) {  // no record: the counts alone
-        if (!d_count || misaligned(d_count, 3))
-            return RNS_E_INVALID;
-        RNS_TRY(check_device());
-        return hip_status(hipMemsetAsync(d_count, 0, 12, static_cast<hipStream_t>(stream)));
-    }
+    if (n_recs == 0)  // no record: the counts alone
+        return count_only(d_count, 12, stream);
     // every rejection, before the device is touched
     if (buf_log2 < kUdpTxMinLog2 || buf_log2 > kPoolMaxLog2 || n_recs > RNS_CHAIN_MAX_PACKETS || n_socks == 0 ||
         n_socks > RNS_UDP_MAX_SOCKS || !d_data || !d_rec || !d_q_first || !d_sock_port || !local_ipv4 || !local_ipv6 ||
-        !d_tx_pool || !d_count || !d_send || !d_work || (n_free && !d_free) ||
-        (send_cap && (!d_tx_blk_first || !d_tx_head_len8 || !d_tx_pay_len16)) || misaligned(d_data, 15) ||
-        misaligned(d_rec, 15) || misaligned(d_tx_pool, 15) || misaligned(d_q_first, 3) || misaligned(d_sock_port, 1) ||
-        misaligned(d_free, 3) || misaligned(d_ip_id_add, 3) || misaligned(d_tx_blk_first, 3) ||
-        misaligned(d_tx_pay_len16, 1) || misaligned(d_tx_src, 3) || misaligned(d_count, 3) || misaligned(d_work, 7) ||
-        work_bytes < udp_tx_work_bytes(n_recs))
+        !pool_tx_valid(d_tx_pool, d_free, n_free, send_cap, d_ip_id_add, d_tx_blk_first, d_tx_head_len8, d_tx_pay_len16,
+                       d_tx_src, d_count) ||
+        !d_send || !d_work || misaligned(d_data, 15) || misaligned(d_rec, 15) || misaligned(d_q_first, 3) ||
+        misaligned(d_sock_port, 1) || misaligned(d_work, 7) || work_bytes < udp_tx_work_bytes(n_recs))
         return RNS_E_INVALID;
     RNS_TRY(check_device());
     UdpTxArgs a{};
@@ -653,27 +651,13 @@ int rns_tx_udp_send_pool_dev(const uint8_t *d_data, uint64_t data_bytes, const r
     a.rec_in = reinterpret_cast<const uint4 *>(d_rec);
     a.q_first = d_q_first;
     a.sock_port = d_sock_port;
-    a.tx_pool = d_tx_pool;
-    a.tx_bufs = tx_pool_bytes >> buf_log2;
-    a.free = d_free;
-    a.ip_id_add = d_ip_id_add;
-    a.tx_blk_first = d_tx_blk_first;
-    a.tx_head_len8 = d_tx_head_len8;
-    a.tx_pay_len16 = d_tx_pay_len16;
-    a.tx_src = d_tx_src;
-    a.count = d_count;
+    set_pool_tx(a.tx, d_tx_pool, tx_pool_bytes, buf_log2, d_free, n_free, send_cap, ip_id_base, d_ip_id_add, d_tx_blk_first,
+                d_tx_head_len8, d_tx_pay_len16, d_tx_src, d_count);
+    a.w = carve_build_work(d_work, n_recs);
+    set_local(a.local, local_ipv4, local_ipv6);
     a.send = d_send;
-    a.part_a = static_cast<uint2 *>(d_work);
-    a.part_b = a.part_a + scan_blocks(n_recs) + 1;
-    a.rec = reinterpret_cast<uint32_t *>(a.part_b + scan_blocks(n_recs) + 1);
-    std::memcpy(&a.local4, local_ipv4, 4);
-    std::memcpy(a.local6, local_ipv6, 16);
     a.n_recs = n_recs;
     a.n_socks = n_socks;
-    a.blog = buf_log2;
-    a.n_free = n_free;
-    a.send_cap = send_cap;
-    a.ip_id_base = ip_id_base;
     return launch_tx_udp(a, static_cast<hipStream_t>(stream));
 }
 

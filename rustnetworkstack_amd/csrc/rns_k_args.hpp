@@ -6,6 +6,7 @@
 #pragma once
 
 #include "rns_k_pool_place.hpp"
+#include "rns_k_pool_txform.hpp"
 #include "rns_k_scan.hpp"
 
 namespace rns {
@@ -90,26 +91,13 @@ constexpr uint32_t kEchoMinLog2 = 8;  // the transmit pool form's: a head fits i
 
 struct EchoArgs {
     PoolRx rx;
-    uint8_t *tx_pool;
-    uint64_t tx_bufs;  // whole buffers of the transmit pool
-    const uint32_t *free;
-    const uint32_t *ip_id_add;
-    uint32_t *tx_blk_first;
-    uint8_t *tx_head_len8;
-    uint16_t *tx_pay_len16;
-    uint32_t *tx_src;
-    uint32_t *count;
+    PoolTx tx;  // (blog = rx.blog: both pools have the same buffer size)
+    BuildWork w;
+    LocalAddrs local;
     uint8_t *echo;
-    uint32_t *rec;        // workspace: a dword per datagram
-    uint2 *part_a;        // workspace: the workgroups' (payload buffers, requests), blocks + 1
-    uint2 *part_b;        // workspace: the workgroups' (IPv4 requests, 0), blocks + 1
-    uint32_t local4;      // the local addresses as they lie in memory
-    uint32_t local6[4];
-    uint32_t n_free, reply_cap, ip_id_base;
 };
 
-// The workspace, 8-byte aligned: the two arrays of block sums, then the datagrams' dwords.
-inline uint64_t echo_work_bytes(uint64_t n_pkts) { return 16ull * (scan_blocks(n_pkts) + 1) + 4ull * n_pkts; }
+inline uint64_t echo_work_bytes(uint64_t n_pkts) { return build_work_bytes(n_pkts); }
 
 // --- the UDP receive demux (rns_k_udp.hpp) ---
 constexpr uint32_t kUdpMinLog2 = 7;  // 60 + 8 header bytes lie inside the first buffer
@@ -153,26 +141,14 @@ struct UdpTxArgs {
     const uint4 *rec_in;       // two per record (rns_udp_rec)
     const uint32_t *q_first;   // n_socks + 1
     const uint16_t *sock_port; // n_socks
-    uint8_t *tx_pool;
-    uint64_t tx_bufs;          // whole buffers of the transmit pool
-    const uint32_t *free;
-    const uint32_t *ip_id_add;
-    uint32_t *tx_blk_first;
-    uint8_t *tx_head_len8;
-    uint16_t *tx_pay_len16;
-    uint32_t *tx_src;
-    uint32_t *count;
+    PoolTx tx;
+    BuildWork w;
+    LocalAddrs local;
     uint8_t *send;
-    uint32_t *rec;             // workspace: a dword per record
-    uint2 *part_a;             // workspace: the workgroups' (payload buffers, sends), blocks + 1
-    uint2 *part_b;             // workspace: the workgroups' (IPv4 sends, 0), blocks + 1
-    uint32_t local4;           // the local addresses as they lie in memory
-    uint32_t local6[4];
-    uint32_t n_recs, n_socks, blog, n_free, send_cap, ip_id_base;
+    uint32_t n_recs, n_socks;
 };
 
-// The workspace, 8-byte aligned: the two arrays of block sums, then the records' dwords.
-inline uint64_t udp_tx_work_bytes(uint64_t n_recs) { return 16ull * (scan_blocks(n_recs) + 1) + 4ull * n_recs; }
+inline uint64_t udp_tx_work_bytes(uint64_t n_recs) { return build_work_bytes(n_recs); }
 
 // --- the TCP listen responder (rns_k_listen.hpp) ---
 struct ListenArgs {
@@ -187,23 +163,20 @@ struct ListenArgs {
     uint32_t *accept;          // 18 dwords per record
     uint32_t *count;
     uint8_t *conn;
-    uint2 *part_a;             // workspace: the workgroups' (replies, IPv4 replies), blocks + 1
-    uint2 *part_b;             // workspace: the workgroups' (accepts, 0), blocks + 1
+    BuildWork w;               // workspace: here part_a = (replies, IPv4 replies), part_b = (accepts, 0)
     unsigned long long *tbl;   // workspace: the key table's slots, resident | the key's hash << 32
     uint32_t *first;           // workspace: a slot's smallest candidate index
-    uint32_t *rec;             // workspace: a dword per datagram
     uint64_t slots;
-    uint32_t local4;           // the local addresses as they lie in memory
-    uint32_t local6[4];
+    LocalAddrs local;
     uint32_t n_listen, reply_cap, ip_id_base;
 };
 
 // Slots of the key table for n_pkts datagrams: the flow table's rule, a power of two >= 2 * n_pkts and >= 64.
-// The workspace, 8-byte aligned: the two arrays of block sums, the table (8 + 4 B per slot, the two arrays one after
-// the other so that one memset clears both), then the datagrams' dwords.  2^20 datagrams: 28 MiB.
+// The workspace, 8-byte aligned: the table (8 + 4 B per slot, the two arrays one after the other so that one memset
+// clears both; 12 * slots is a multiple of 8), then the build's own.  2^20 datagrams: 28 MiB.
 inline uint64_t listen_work_bytes(uint64_t n_pkts)
 {
-    return 16ull * (scan_blocks(n_pkts) + 1) + 12ull * flow_slots(static_cast<uint32_t>(n_pkts)) + 4ull * n_pkts;
+    return build_work_bytes(n_pkts) + 12ull * flow_slots(static_cast<uint32_t>(n_pkts));
 }
 
 }  // namespace rns

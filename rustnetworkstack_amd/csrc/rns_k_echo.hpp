@@ -21,9 +21,8 @@ namespace rns {
 //   2. scan2_parts_kernel    (rns_k_scan.hpp, through k_scan.hip) over each of the two sum arrays.
 //                            The buffers before a request are payload buffers + requests, added in
 //                            64 bits.
-//   3. echo_build_kernel     the same decomposition: scans its workgroup again, applies reply_cap
-//                            and the free list's length (both counts are monotone: the answered
-//                            requests are a prefix), then each wave walks the destination 16-byte
+//   3. echo_build_kernel     the same decomposition: allocates the replies' buffers (tx_alloc,
+//                            rns_k_pool_txform.hpp), then each wave walks the destination 16-byte
 //                            chunks of all its replies concatenated (pool_walk, rns_k_pool_view.hpp),
 //                            the destination in the reply's payload buffers, which start 16-byte aligned:
 //                            every chunk is one whole aligned store, a payload's last chunk with
@@ -34,8 +33,8 @@ namespace rns {
 //                            then folds in the head and the IPv6 pseudo-header, and stores the head —
 //                            both checksums filled — and the descriptors.  The payload is read once and
 //                            written once after the verify.
-// The counts are stored by one lane of the grid — the first request that is not answered (its exclusive
-// counts) or, when all are, the last request — into the zeroed d_count: no atomics.
+// The allocation, the counts, the status bits and the descriptors are the pool transmit form's
+// (rns_k_pool_txform.hpp), shared with the UDP send build; the IP head words are composed there too.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kEchoWaves = kScanBlock / 64;
 // The wave's LDS table: pool_walk's rows, then an answered request's first payload buffer's place in d_free
@@ -74,15 +73,8 @@ __global__ __launch_bounds__(kScanBlock) void echo_classify_kernel(const EchoArg
         }
     }
     if (e.live)
-        a.rec[e.p] = rec;
-    const uint32_t req = rec & kEchoRecReq;
-    uint2 ta, tb;
-    (void)scan2_block(make_uint2((rec >> kEchoRecBufShift) & 0x3ffu, req), ta);
-    (void)scan2_block(make_uint2((rec & kEchoRecV4) ? 1u : 0u, 0u), tb);
-    if (threadIdx.x == 0) {
-        a.part_a[blockIdx.x] = ta;
-        a.part_b[blockIdx.x] = tb;
-    }
+        a.w.rec[e.p] = rec;
+    build_parts(a.w, (rec >> kEchoRecBufShift) & 0x3ffu, rec & kEchoRecReq, (rec & kEchoRecV4) != 0);
 }
 
 // Stores the chunk whole (zeros after a payload's last byte) and adds its little-endian word sum to its
@@ -113,102 +105,59 @@ __global__ __launch_bounds__(kScanBlock) void echo_build_kernel(const EchoArgs a
     uint32_t(&pd)[kEchoPd][64] = pds[wv];
     const uint32_t blk = blockIdx.x * kEchoWaves + wv;
     const PoolLane e = pool_lane(a.rx, blk, lane);
-    const uint32_t rec = e.live ? a.rec[e.p] : 0u;
+    const uint32_t rec = e.live ? a.w.rec[e.p] : 0u;
     const bool req = (rec & kEchoRecReq) != 0, v4 = (rec & kEchoRecV4) != 0;
     const uint32_t pbufs = (rec >> kEchoRecBufShift) & 0x3ffu, ip_hdr = ((rec >> kEchoRecIhlShift) & 0xfu) * 4u;
-    uint2 ta, tb;
-    const uint2 xa = scan2_block(make_uint2(pbufs, req ? 1u : 0u), ta);
-    const uint2 xb = scan2_block(make_uint2(v4 ? 1u : 0u, 0u), tb);
-    const uint2 ca = a.part_a[blockIdx.x], cb = a.part_b[blockIdx.x];
-    // exclusive counts before this datagram: requests, their buffers (64 bits), IPv4 requests
-    const uint32_t r = ca.y + xa.y, v4_before = cb.x + xb.x;
-    const uint64_t f0 = static_cast<uint64_t>(ca.x + xa.x) + r;
-    const uint32_t nfr = 1u + pbufs;
-    const bool built = req && r < a.reply_cap && f0 + nfr <= a.n_free;
+    const TxSlot t = tx_alloc(a.tx, a.w, req, pbufs, v4, [](bool) {});
     const uint32_t pay = req ? e.T - ip_hdr - 4u : 0u;
-    const uint32_t fi = static_cast<uint32_t>(f0);  // built: f0 < n_free
-    bool bad = false;
-    if (built) {
-        for (uint32_t k = 0; k < nfr; ++k)
-            bad = bad || a.free[fi + k] >= a.tx_bufs;
-    }
     if (e.live)
-        a.echo[e.p] = static_cast<uint8_t>(!req ? 0u : !built ? RNS_ECHO_REQUEST | RNS_ECHO_NOBUF
-                                                   : bad    ? RNS_ECHO_REQUEST | RNS_ECHO_BADBUF
-                                                            : RNS_ECHO_REQUEST | RNS_ECHO_BUILT);
-    // the totals, stored by one lane of the grid: the first request that is not answered holds them as its
-    // exclusive counts (its predecessor was answered: r - 1 < reply_cap and f0 <= n_free), and when every
-    // request is answered the last one holds them as its inclusive counts.  (No request answered: the
-    // zeroed d_count stands.)
-    if (req && (built ? r + 1u == a.part_a[gridDim.x].y : r != 0 && r - 1u < a.reply_cap && f0 <= a.n_free)) {
-        a.count[0] = r + (built ? 1u : 0u);
-        a.count[1] = fi + (built ? nfr : 0u);
-        a.count[2] = v4_before + (built && v4 ? 1u : 0u);
-    }
-    const uint64_t bm = __ballot(built);
+        a.echo[e.p] = tx_status(t, req);
+    const uint64_t bm = __ballot(t.built);
     if (!bm)
         return;  // (after the workgroup's last barrier)
     // the wave's destination chunks, concatenated: at most 64 * 4096 of them
-    const bool copy = built && !bad;
+    const bool copy = t.built && !t.bad;
     const uint32_t nck = copy ? (pay + 15u) >> 4 : 0u;
     const uint32_t cinc = wave_incl_scan(nck);
     const uint32_t W = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cinc), 63));
     pd[kEchoPdSum][lane] = 0u;
     if (W != 0) {
         pool_rows(pd, lane, cinc - nck, e.gi, ip_hdr + 4u, pay);
-        pd[kEchoPdFree][lane] = fi + 1u;
+        pd[kEchoPdFree][lane] = t.fi + 1u;
         wave_lds_fence();
         pool_walk<NT>(
             a.rx, pd, W, lane,
             [](uint32_t) { return 0u; },
-            [&](uint32_t j, uint32_t c) {
-                // chunk c of a payload lies in buffer c >> (blog - 4); the reply's buffers were found inside the
-                // transmit pool before its chunks were counted
-                const uint32_t bi = a.free[pd[kEchoPdFree][j] + (c >> (a.rx.blog - 4u))];
-                return a.tx_pool + (static_cast<uint64_t>(bi) << a.rx.blog) + ((16u * c) & ((1u << a.rx.blog) - 1u));
-            },
+            [&](uint32_t j, uint32_t c) { return tx_chunk_dst(a.tx, pd[kEchoPdFree][j], c); },
             [&](const PlaceChunk &ck, const uint4 y) { echo_emit(ck, y, pd, lane); });
     }
     wave_lds_fence();
-    if (!built)
+    if (!t.built)
         return;
     // the owner lane: the descriptors, then the head with both checksums
-    a.tx_head_len8[r] = static_cast<uint8_t>(bad ? 0u : v4 ? 24u : 44u);
-    a.tx_pay_len16[r] = static_cast<uint16_t>(pay);
-    if (a.tx_src)
-        a.tx_src[r] = static_cast<uint32_t>(e.p);
-    if ((r & 63u) == 0)
-        a.tx_blk_first[r >> 6] = fi;
-    if (bad)
+    uint8_t *const hb = tx_describe(a.tx, t, v4 ? 24u : 44u, pay, e.p);
+    if (t.bad)
         return;
-    const uint32_t B = 1u << a.rx.blog;
     const uint32_t *h = pool_first(a.rx, e);  // a request: the classify found it inside the pool
-    uint8_t *const hb = a.tx_pool + (static_cast<uint64_t>(a.free[fi]) << a.rx.blog) + B;
     const uint32_t pay_be = bswap16_u32(fold16(pd[kEchoPdSum][lane]));  // the payload's big-endian word sum, folded (RFC 1071 2(B))
     if (v4) {
-        // ip_output_v4: 45 00 len | id 0000 | 40 01 csum | local | requester; then 00 00 csum (icmp_output)
-        const uint32_t total = (24u + pay) & 0xffffu;
-        const uint32_t id = (a.ip_id_base + (a.ip_id_add ? *a.ip_id_add : 0u) + v4_before) & 0xffffu;
-        const uint32_t peer = h[3];
-        const uint32_t ipck = fold16(0x4500u + total + id + 0x4001u + be2(a.local4) + be2(peer)) ^ 0xffffu;
+        // ip_output_v4, protocol 1, to the requester; then 00 00 csum (icmp_output)
+        const Ip4Head ip = ip4_head(24u + pay, ip_id(a.tx.ip_id_base, a.tx.ip_id_add, t.v4_before), 1u, a.local.v4, h[3]);
         const uint32_t ck = pay_be ^ 0xffffu;  // seed 0, a head of zeros
         uint8_t *const at = hb - 24u;  // 8 mod 16
-        *reinterpret_cast<uint2 *>(at) = make_uint2(0x45u | (bswap16_u32(total) << 16), bswap16_u32(id));
-        *reinterpret_cast<uint4 *>(at + 8) =
-            make_uint4(0x0140u | (bswap16_u32(ipck) << 16), a.local4, peer, bswap16_u32(ck) << 16);
+        *reinterpret_cast<uint2 *>(at) = make_uint2(ip.d[0], ip.d[1]);
+        *reinterpret_cast<uint4 *>(at + 8) = make_uint4(ip.d[2], ip.d[3], ip.d[4], bswap16_u32(ck) << 16);
     } else {
-        // ip_output_v6: 60 00 00 00 | len 3a 40 | local | requester; then 81 00 csum
+        // ip_output_v6, next header 58, to the requester; then 81 00 csum
         const uint32_t plen = 4u + pay;
-        const uint32_t p0 = h[2], p1 = h[3], p2 = h[4], p3 = h[5];
-        uint32_t s = plen + 58u + 0x8100u + pay_be;
-        s += be2(a.local6[0]) + be2(a.local6[1]) + be2(a.local6[2]) + be2(a.local6[3]);
-        s += be2(p0) + be2(p1) + be2(p2) + be2(p3);
-        const uint32_t ck = fold16(s) ^ 0xffffu;
+        const uint32_t peer[4] = {h[2], h[3], h[4], h[5]};
+        const Ip6Head ip = ip6_head(plen, 58u, a.local.v6, peer);
+        const uint32_t ck = fold16(plen + 58u + 0x8100u + pay_be + addr_sum6(a.local.v6, peer)) ^ 0xffffu;
         uint8_t *const at = hb - 44u;  // 4 mod 16
-        *reinterpret_cast<uint32_t *>(at) = 0x60u;
-        *reinterpret_cast<uint2 *>(at + 4) = make_uint2(bswap16_u32(plen) | (58u << 16) | (64u << 24), a.local6[0]);
-        *reinterpret_cast<uint4 *>(at + 12) = make_uint4(a.local6[1], a.local6[2], a.local6[3], p0);
-        *reinterpret_cast<uint4 *>(at + 28) = make_uint4(p1, p2, p3, 0x81u | (bswap16_u32(ck) << 16));
+        *reinterpret_cast<uint32_t *>(at) = ip.d[0];
+        *reinterpret_cast<uint2 *>(at + 4) = make_uint2(ip.d[1], ip.d[2]);
+        *reinterpret_cast<uint4 *>(at + 12) = make_uint4(ip.d[3], ip.d[4], ip.d[5], ip.d[6]);
+        *reinterpret_cast<uint4 *>(at + 28) = make_uint4(ip.d[7], ip.d[8], ip.d[9], 0x81u | (bswap16_u32(ck) << 16));
     }
 }
 

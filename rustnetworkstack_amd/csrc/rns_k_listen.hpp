@@ -175,7 +175,7 @@ __global__ __launch_bounds__(kScanBlock) void listen_classify_kernel(const Liste
             }
         }
     }
-    a.rec[e.p] = rec;
+    a.w.rec[e.p] = rec;
 }
 
 // s(key): the smallest candidate index of key k in the batch, kListenEmpty if it has none.  p: the asking
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(kScanBlock) void listen_resolve_kernel(const Listen
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t blk = blockIdx.x * kListenWaves + (threadIdx.x >> 6);
     const PoolLane e = pool_lane(a.rx, blk, lane);
-    uint32_t rec = e.live ? a.rec[e.p] : 0u;
+    uint32_t rec = e.live ? a.w.rec[e.p] : 0u;
     ListenSeg s;
     if ((rec & RNS_CONN_UNMATCHED) && listen_seg(a, e.p, e.gi, s)) {  // (the classify found it so: the same inputs)
         const uint32_t p = static_cast<uint32_t>(e.p);
@@ -250,14 +250,14 @@ __global__ __launch_bounds__(kScanBlock) void listen_resolve_kernel(const Listen
         rec = 0;
     }
     if (e.live)
-        a.rec[e.p] = rec;
+        a.w.rec[e.p] = rec;
     const uint32_t reply = (rec & (RNS_CONN_SYN | RNS_CONN_RST)) ? 1u : 0u;
     uint2 ta, tb;
     (void)scan2_block(make_uint2(reply, (reply && (rec & kListenRecV4)) ? 1u : 0u), ta);
     (void)scan2_block(make_uint2((rec & RNS_CONN_SYN) ? 1u : 0u, 0u), tb);
     if (threadIdx.x == 0) {
-        a.part_a[blockIdx.x] = ta;
-        a.part_b[blockIdx.x] = tb;
+        a.w.part_a[blockIdx.x] = ta;
+        a.w.part_b[blockIdx.x] = tb;
     }
 }
 
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(kScanBlock) void listen_resolve_kernel(const Listen
 // ip_output_v4 / ip_output_v6.  IPD = the IP header's dwords.  Every dword but the two that hold a checksum is
 // stored as it is summed.
 template <uint32_t IPD>
-__device__ __forceinline__ void listen_head(const ListenArgs &a, const ListenSeg &s, uint32_t *o, bool syn, uint32_t seq,
+__device__ __forceinline__ void listen_head(const LocalAddrs &local, const ListenSeg &s, uint32_t *o, bool syn, uint32_t seq,
                                             uint32_t id)
 {
     constexpr bool v4 = IPD == 5u;
@@ -275,14 +275,14 @@ __device__ __forceinline__ void listen_head(const ListenArgs &a, const ListenSeg
         d[0] = 0x45u | (bswap16_u32(20u + tcplen) << 16);
         d[1] = bswap16_u32(id);
         d[2] = 0x0640u;
-        d[3] = a.local4;
+        d[3] = local.v4;
         d[4] = s.key[0];
     } else {
         d[0] = 0x60u;
         d[1] = bswap16_u32(tcplen) | (6u << 16) | (64u << 24);
 #pragma unroll
         for (uint32_t k = 0; k < 4u; ++k) {
-            d[2u + k] = a.local6[k];
+            d[2u + k] = local.v6[k];
             d[6u + k] = s.key[k];
         }
     }
@@ -314,15 +314,15 @@ __global__ __launch_bounds__(kScanBlock) void listen_build_kernel(const ListenAr
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t blk = blockIdx.x * kListenWaves + (threadIdx.x >> 6);
     const PoolLane e = pool_lane(a.rx, blk, lane);
-    const uint32_t rec = e.live ? a.rec[e.p] : 0u;
+    const uint32_t rec = e.live ? a.w.rec[e.p] : 0u;
     const bool syn = (rec & RNS_CONN_SYN) != 0, reply = (rec & (RNS_CONN_SYN | RNS_CONN_RST)) != 0;
     const bool v4 = (rec & kListenRecV4) != 0;
     uint2 ta, tb;
     const uint2 xa = scan2_block(make_uint2(reply ? 1u : 0u, (reply && v4) ? 1u : 0u), ta);
     const uint2 xb = scan2_block(make_uint2(syn ? 1u : 0u, 0u), tb);
-    const uint2 ca = a.part_a[blockIdx.x], cb = a.part_b[blockIdx.x];
+    const uint2 ca = a.w.part_a[blockIdx.x], cb = a.w.part_b[blockIdx.x];
     if (blockIdx.x == 0 && threadIdx.x == 0) {  // the totals, whatever reply_cap is
-        const uint2 na = a.part_a[gridDim.x], nb = a.part_b[gridDim.x];
+        const uint2 na = a.w.part_a[gridDim.x], nb = a.w.part_b[gridDim.x];
         a.count[0] = na.x;
         a.count[1] = na.y;
         a.count[2] = nb.x;
@@ -341,9 +341,9 @@ __global__ __launch_bounds__(kScanBlock) void listen_build_kernel(const ListenAr
     const uint32_t seq = syn ? a.iss[acc] : 1u;
     uint32_t *o = reinterpret_cast<uint32_t *>(a.out + 64ull * k);
     if (v4)
-        listen_head<5u>(a, s, o, syn, seq, (a.ip_id_base + (a.ip_id_add ? *a.ip_id_add : 0u) + v4_before) & 0xffffu);
+        listen_head<5u>(a.local, s, o, syn, seq, ip_id(a.ip_id_base, a.ip_id_add, v4_before));
     else
-        listen_head<10u>(a, s, o, syn, seq, 0u);
+        listen_head<10u>(a.local, s, o, syn, seq, 0u);
     if (!syn)
         return;
     // handle_new_connection: the key it inserts, the socket it leaves

@@ -8,12 +8,20 @@
 // (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
 #pragma once
 
-#include "rns_k_common.hpp"
+#include "rns_k_tcp_head.hpp"
 
 namespace rns {
 
+// (plain C++ that a host compiler takes: the workspace formulas are written over it)
 constexpr uint32_t kScanBlock = 256;
-__host__ __device__ inline uint64_t scan_blocks(uint64_t n) { return (n + kScanBlock - 1) / kScanBlock; }
+RNS_HD uint64_t scan_blocks(uint64_t n) { return (n + kScanBlock - 1) / kScanBlock; }
+
+}  // namespace rns
+
+#ifdef __HIPCC__
+#include "rns_k_common.hpp"
+
+namespace rns {
 
 __device__ __forceinline__ uint2 scan2_block(uint2 v, uint2 &total)
 {
@@ -52,3 +60,4 @@ __global__ __launch_bounds__(kScanBlock) void scan2_reduce_kernel(const A a, uin
 }
 
 }  // namespace rns
+#endif  // __HIPCC__

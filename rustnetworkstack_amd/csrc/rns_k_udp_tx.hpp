@@ -20,9 +20,9 @@ namespace rns {
 //                              in the workspace (send, IPv4, payload buffers, the socket's port) and the
 //                              workgroup's sums of (payload buffers, sends) and (IPv4 sends, 0).
 //   2. scan2_parts_kernel      (rns_k_scan.hpp, through k_scan.hip) over each of the two sum arrays.
-//   3. udp_tx_build_kernel     the same decomposition: scans its workgroup again, applies send_cap and the
-//                              free list's length (both counts are monotone: the built sends are a prefix),
-//                              then each wave walks the 16-byte chunks of all its payloads concatenated.
+//   3. udp_tx_build_kernel     the same decomposition: allocates the datagrams' buffers (tx_alloc,
+//                              rns_k_pool_txform.hpp), then each wave walks the 16-byte chunks of all its
+//                              payloads concatenated.
 //                              A payload starts 16-byte aligned in d_data and at the start of a buffer in
 //                              the pool: a chunk is one whole aligned load and one whole aligned store,
 //                              a payload's last chunk with zeros after its bytes (the datagram's own buffer).
@@ -30,8 +30,8 @@ namespace rns {
 //                              (wave_dgram_sum) into LDS.  The owner lane then folds in the UDP header and
 //                              the pseudo-header and stores the head — both checksums filled — and the
 //                              descriptors.  The payload is read once and written once.
-// The counts are stored by one lane of the grid — the first send that is not built (its exclusive counts) or,
-// when all are, the last send — into the zeroed d_count: no atomics.
+// The allocation, the counts, the status bits and the descriptors are the pool transmit form's
+// (rns_k_pool_txform.hpp), shared with the echo responder; the IP head words are composed there too.
 // ---------------------------------------------------------------------------
 constexpr uint32_t kUdpTxWaves = kScanBlock / 64;
 // The wave's LDS table, a row of 64 per field: the wave's chunks before the datagram (place_owner's row), its
@@ -61,19 +61,13 @@ __global__ __launch_bounds__(kScanBlock) void udp_tx_classify_kernel(const UdpTx
                 else
                     hi = mid;
             }
-            rec = kUtRecSend | (fam == 4u ? kUtRecV4 : 0u) | (((len + (1u << a.blog) - 1u) >> a.blog) << kUtRecBufShift) |
+            rec = kUtRecSend | (fam == 4u ? kUtRecV4 : 0u) | (((len + (1u << a.tx.blog) - 1u) >> a.tx.blog) << kUtRecBufShift) |
                   (static_cast<uint32_t>(a.sock_port[lo]) << kUtRecPortShift);
         }
     }
     if (live)
-        a.rec[k] = rec;
-    uint2 ta, tb;
-    (void)scan2_block(make_uint2((rec >> kUtRecBufShift) & kUtRecBufMask, rec & kUtRecSend), ta);
-    (void)scan2_block(make_uint2((rec & kUtRecV4) ? 1u : 0u, 0u), tb);
-    if (threadIdx.x == 0) {
-        a.part_a[blockIdx.x] = ta;
-        a.part_b[blockIdx.x] = tb;
-    }
+        a.w.rec[k] = rec;
+    build_parts(a.w, (rec >> kUtRecBufShift) & kUtRecBufMask, rec & kUtRecSend, (rec & kUtRecV4) != 0);
 }
 
 // One chunk of the wave's concatenated payloads: its 16 bytes (zeros after the payload's last byte) and where
@@ -114,10 +108,7 @@ __device__ __forceinline__ UdpTxChunk udp_tx_chunk(const UdpTxArgs &a, const uin
         ck.x = make_uint4(keep_bytes(ck.x.x, 0, hi, 0), keep_bytes(ck.x.y, 0, hi, 4), keep_bytes(ck.x.z, 0, hi, 8),
                           keep_bytes(ck.x.w, 0, hi, 12));
     }
-    // chunk c of a payload lies in buffer c >> (blog - 4); the datagram's buffers were found inside the transmit
-    // pool before its chunks were counted
-    const uint32_t bi = a.free[pd[kUtFree][j] + (c >> (a.blog - 4u))];
-    ck.dc = a.tx_pool + (static_cast<uint64_t>(bi) << a.blog) + ((16u * c) & ((1u << a.blog) - 1u));
+    ck.dc = tx_chunk_dst(a.tx, pd[kUtFree][j], c);
     ck.j = j;
     ck.c = c;
     return ck;
@@ -141,48 +132,24 @@ __global__ __launch_bounds__(kScanBlock) void udp_tx_build_kernel(const UdpTxArg
     uint32_t(&pd)[kUtRows][64] = pds[wv];
     const uint64_t k = static_cast<uint64_t>(blockIdx.x) * kScanBlock + threadIdx.x;
     const bool live = k < a.n_recs;
-    const uint32_t rec = live ? a.rec[k] : 0u;
+    const uint32_t rec = live ? a.w.rec[k] : 0u;
     const bool snd = (rec & kUtRecSend) != 0, v4 = (rec & kUtRecV4) != 0;
-    const uint32_t pbufs = (rec >> kUtRecBufShift) & kUtRecBufMask;
-    uint2 ta, tb;
-    const uint2 xa = scan2_block(make_uint2(pbufs, snd ? 1u : 0u), ta);
-    const uint2 xb = scan2_block(make_uint2(v4 ? 1u : 0u, 0u), tb);
-    const uint2 ca = a.part_a[blockIdx.x], cb = a.part_b[blockIdx.x];
-    // exclusive counts before this record: sends, their buffers (64 bits), IPv4 sends
-    const uint32_t r = ca.y + xa.y, v4_before = cb.x + xb.x;
-    const uint64_t f0 = static_cast<uint64_t>(ca.x + xa.x) + r;
-    const uint32_t nfr = 1u + pbufs;
-    const bool built = snd && r < a.send_cap && f0 + nfr <= a.n_free;
     // the record, as the classify read it: the destination, then src, off16, sport | len << 16, family | flags << 8
     uint4 r0 = make_uint4(0u, 0u, 0u, 0u), r1 = r0;
-    if (built) {
-        r0 = a.rec_in[2 * k];
-        r1 = a.rec_in[2 * k + 1];
-    }
+    const TxSlot t = tx_alloc(a.tx, a.w, snd, (rec >> kUtRecBufShift) & kUtRecBufMask, v4, [&](bool built) {
+        if (built) {
+            r0 = a.rec_in[2 * k];
+            r1 = a.rec_in[2 * k + 1];
+        }
+    });
     const uint32_t len = r1.z >> 16;
-    const uint32_t fi = static_cast<uint32_t>(f0);  // built: f0 < n_free
-    bool bad = false;
-    if (built) {
-        for (uint32_t q = 0; q < nfr; ++q)
-            bad = bad || a.free[fi + q] >= a.tx_bufs;
-    }
     if (live)
-        a.send[k] = static_cast<uint8_t>(!snd ? 0u : !built ? RNS_UDPTX_SEND | RNS_UDPTX_NOBUF
-                                                  : bad    ? RNS_UDPTX_SEND | RNS_UDPTX_BADBUF
-                                                           : RNS_UDPTX_SEND | RNS_UDPTX_BUILT);
-    // the totals, stored by one lane of the grid: the first send that is not built holds them as its exclusive
-    // counts (its predecessor was built: r - 1 < send_cap and f0 <= n_free), and when every send is built the
-    // last one holds them as its inclusive counts.  (No send built: the zeroed d_count stands.)
-    if (snd && (built ? r + 1u == a.part_a[gridDim.x].y : r != 0 && r - 1u < a.send_cap && f0 <= a.n_free)) {
-        a.count[0] = r + (built ? 1u : 0u);
-        a.count[1] = fi + (built ? nfr : 0u);
-        a.count[2] = v4_before + (built && v4 ? 1u : 0u);
-    }
-    const uint64_t bm = __ballot(built);
+        a.send[k] = tx_status(t, snd);
+    const uint64_t bm = __ballot(t.built);
     if (!bm)
         return;  // (after the workgroup's last barrier)
     // the wave's chunks, concatenated: at most 64 * 4096 of them, 128 at a time with both halves' loads in flight
-    const bool copy = built && !bad;
+    const bool copy = t.built && !t.bad;
     const uint32_t nck = copy ? (len + 15u) >> 4 : 0u;
     const uint32_t cinc = wave_incl_scan(nck);
     const uint32_t W = static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(cinc), 63));
@@ -191,7 +158,7 @@ __global__ __launch_bounds__(kScanBlock) void udp_tx_build_kernel(const UdpTxArg
         pd[kUtBefore][lane] = cinc - nck;
         pd[kUtOff][lane] = r1.y;
         pd[kUtLen][lane] = len;
-        pd[kUtFree][lane] = fi + 1u;
+        pd[kUtFree][lane] = t.fi + 1u;
         wave_lds_fence();
         for (uint32_t vb = 0; vb < W; vb += 128u) {
             const UdpTxChunk c0 = udp_tx_chunk(a, pd, vb + lane, W);
@@ -201,45 +168,34 @@ __global__ __launch_bounds__(kScanBlock) void udp_tx_build_kernel(const UdpTxArg
         }
     }
     wave_lds_fence();
-    if (!built)
+    if (!t.built)
         return;
     // the owner lane: the descriptors, then the head with both checksums
-    a.tx_head_len8[r] = static_cast<uint8_t>(bad ? 0u : v4 ? 28u : 48u);
-    a.tx_pay_len16[r] = static_cast<uint16_t>(len);
-    if (a.tx_src)
-        a.tx_src[r] = static_cast<uint32_t>(k);
-    if ((r & 63u) == 0)
-        a.tx_blk_first[r >> 6] = fi;
-    if (bad)
+    uint8_t *const hb = tx_describe(a.tx, t, v4 ? 28u : 48u, len, k);
+    if (t.bad)
         return;
-    const uint32_t B = 1u << a.blog;
-    uint8_t *const hb = a.tx_pool + (static_cast<uint64_t>(a.free[fi]) << a.blog) + B;
     const uint32_t pay_be = bswap16_u32(fold16(pd[kUtSum][lane]));  // the payload's big-endian word sum, folded (RFC 1071 2(B))
     // udp_output: source port, destination port, length as u16, checksum over the pseudo-header and the packet
     const uint32_t sport = rec >> kUtRecPortShift, dport = r1.z & 0xffffu, ulen = (8u + len) & 0xffffu;
     const uint32_t ports = bswap16_u32(sport) | (bswap16_u32(dport) << 16);
     const uint32_t l4 = 17u + ulen + sport + dport + ulen + pay_be;  // without the addresses
     if (v4) {
-        // ip_output_v4: 45 00 len | id 0000 | 40 11 csum | local | destination
-        const uint32_t total = (28u + len) & 0xffffu;
-        const uint32_t id = (a.ip_id_base + (a.ip_id_add ? *a.ip_id_add : 0u) + v4_before) & 0xffffu;
-        const uint32_t addrs = be2(a.local4) + be2(r0.x);
-        const uint32_t ipck = fold16(0x4500u + total + id + 0x4011u + addrs) ^ 0xffffu;
-        const uint32_t ck = fold16(l4 + addrs) ^ 0xffffu;  // a computed 0 is stored as 0
+        // ip_output_v4, protocol 17, to the record's address
+        const Ip4Head ip = ip4_head(28u + len, ip_id(a.tx.ip_id_base, a.tx.ip_id_add, t.v4_before), 17u, a.local.v4, r0.x);
+        const uint32_t ck = fold16(l4 + addr_sum4(a.local.v4, r0.x)) ^ 0xffffu;  // a computed 0 is stored as 0
         uint8_t *const at = hb - 28u;  // 4 mod 16
-        *reinterpret_cast<uint32_t *>(at) = 0x45u | (bswap16_u32(total) << 16);
-        *reinterpret_cast<uint2 *>(at + 4) = make_uint2(bswap16_u32(id), 0x1140u | (bswap16_u32(ipck) << 16));
-        *reinterpret_cast<uint4 *>(at + 12) = make_uint4(a.local4, r0.x, ports, bswap16_u32(ulen) | (bswap16_u32(ck) << 16));
+        *reinterpret_cast<uint32_t *>(at) = ip.d[0];
+        *reinterpret_cast<uint2 *>(at + 4) = make_uint2(ip.d[1], ip.d[2]);
+        *reinterpret_cast<uint4 *>(at + 12) = make_uint4(ip.d[3], ip.d[4], ports, bswap16_u32(ulen) | (bswap16_u32(ck) << 16));
     } else {
-        // ip_output_v6: 60 00 00 00 | len 11 40 | local | destination
-        uint32_t s = l4;
-        s += be2(a.local6[0]) + be2(a.local6[1]) + be2(a.local6[2]) + be2(a.local6[3]);
-        s += be2(r0.x) + be2(r0.y) + be2(r0.z) + be2(r0.w);
-        const uint32_t ck = fold16(s) ^ 0xffffu;
+        // ip_output_v6, next header 17, to the record's address
+        const uint32_t peer[4] = {r0.x, r0.y, r0.z, r0.w};
+        const Ip6Head ip = ip6_head(ulen, 17u, a.local.v6, peer);
+        const uint32_t ck = fold16(l4 + addr_sum6(a.local.v6, peer)) ^ 0xffffu;
         uint8_t *const at = hb - 48u;  // 0 mod 16
-        *reinterpret_cast<uint4 *>(at) = make_uint4(0x60u, bswap16_u32(ulen) | (17u << 16) | (64u << 24), a.local6[0], a.local6[1]);
-        *reinterpret_cast<uint4 *>(at + 16) = make_uint4(a.local6[2], a.local6[3], r0.x, r0.y);
-        *reinterpret_cast<uint4 *>(at + 32) = make_uint4(r0.z, r0.w, ports, bswap16_u32(ulen) | (bswap16_u32(ck) << 16));
+        *reinterpret_cast<uint4 *>(at) = make_uint4(ip.d[0], ip.d[1], ip.d[2], ip.d[3]);
+        *reinterpret_cast<uint4 *>(at + 16) = make_uint4(ip.d[4], ip.d[5], ip.d[6], ip.d[7]);
+        *reinterpret_cast<uint4 *>(at + 32) = make_uint4(ip.d[8], ip.d[9], ports, bswap16_u32(ulen) | (bswap16_u32(ck) << 16));
     }
 }
 

@@ -47,4 +47,5 @@
 #include "rns_k_pool_view.hpp"
 #include "rns_k_pool_place.hpp"
 #include "rns_k_scan.hpp"
+#include "rns_k_pool_txform.hpp"
 #include "rns_k_args.hpp"

@@ -4,7 +4,8 @@
 //   k_segment.hip, k_place.hip                            TCP segmentation offload, receive placement
 //   k_flow.hip, k_plan.hip, k_echo.hip, k_udp.hip,        the sequences of launches; each includes its own
 //   k_udp_tx.hip, k_listen.hip                            kernels header (rns_k_flow / plan / echo / udp / udp_tx / listen.hpp)
-//   (k_place, k_echo and k_udp, the pool verify's consumers, share rns_k_pool_view.hpp: view, decode, walk)
+//   (k_place, k_echo and k_udp, the pool verify's consumers, share rns_k_pool_view.hpp: view, decode, walk;
+//    k_echo and k_udp_tx, the builders into the pool transmit form, rns_k_pool_txform.hpp and launch_build_seq)
 //   k_scan.hip                                            the scan's middle launch, which those six share
 // rns_checksum.hip holds the device entry points of the C ABI, rns_pipeline.hip the host-resident
 // pipeline and the multi-GPU contexts.
@@ -119,6 +120,22 @@ inline int launch(void (*kernel)(const CsumArgs), dim3 grid, dim3 block, size_t 
         RNS_TRY(hip_status(hipGetLastError()));                                       \
     } while (0)
 
+// k_scan.hip: the scan's one-workgroup middle launch
+int launch_scan2_parts(uint2 *part, uint32_t nb, uint32_t *total2, hipStream_t st);
+
+// A builder into the pool transmit form (rns_k_pool_txform.hpp) over n items: the counts zeroed, classify(blocks),
+// the two scans of its block sums, build(blocks); both return a status.
+template <class Classify, class Build>
+int launch_build_seq(uint32_t *count, const BuildWork &w, uint64_t n, hipStream_t st, Classify classify, Build build)
+{
+    const uint32_t nb = static_cast<uint32_t>(scan_blocks(n));
+    RNS_TRY(hip_status(hipMemsetAsync(count, 0, 12, st)));
+    RNS_TRY(classify(nb));
+    RNS_TRY(launch_scan2_parts(w.part_a, nb, nullptr, st));
+    RNS_TRY(launch_scan2_parts(w.part_b, nb, nullptr, st));
+    return build(nb);
+}
+
 // k_shapes.hip: the explicit-descriptor kernels by (variant, lanes per packet, chunks in flight)
 template <bool S>
 int dispatch(const CsumArgs &a, uint32_t variant, uint32_t G, uint32_t U, uint32_t max_blocks, hipStream_t st);
@@ -153,8 +170,6 @@ int launch_rx_place(const PlaceArgs &a, bool nt, hipStream_t st);
 // k_flow.hip: TCP flow update (count, scan, scatter, walk) and ACK build (scan, build), each a sequence of launches
 int launch_flow_update(const FlowArgs &a, hipStream_t st);
 int launch_ack_build(const AckArgs &a, hipStream_t st);
-// k_scan.hip: the scan's one-workgroup middle launch
-int launch_scan2_parts(uint2 *part, uint32_t nb, uint32_t *total2, hipStream_t st);
 // k_plan.hip: TCP send planning (plan, scan, cap, finish), a sequence of launches
 int launch_tx_plan(const PlanArgs &a, hipStream_t st);
 // k_echo.hip: the ICMP echo responder (classify, two scans, build), after launch_rx_pool on the same stream

@@ -16,8 +16,9 @@ import numpy as np
 import torch
 
 from . import _lib
-from .batch import _I32, _U8, _call, _local_addrs, _nonnull, _per_packet, _require_cuda, _status, _work_bytes, _workspace
-from .pool import (_be_sum, _buf_log2, _fold, _host_datagrams, _new, _pool_batch, recv_batch_pool, send_batch_pool)
+from .batch import _I32, _U8, _call, _local_addrs, _nonnull, _per_packet, _status, _work_bytes, _workspace
+from .pool import (_be_sum, _buf_log2, _cap_and_ids, _fold, _host_datagrams, _ip_head_bytes, _new, _pool_batch, _send_built,
+                   _stage_rx, _tx_outputs, _TxFormHost, recv_batch_pool)
 
 
 def echo_work(n_pkts: int) -> int:
@@ -51,21 +52,12 @@ def rx_icmp_echo_pool(rx_pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: t
     n_free = free.numel()
     if rx_pool.data_ptr() & 15 or tx_pool.data_ptr() & 15:
         raise ValueError("the pools must start 16-byte aligned")
-    cap = n if reply_cap is None else int(reply_cap)
-    if not 0 <= cap <= _lib.RNS_CHAIN_MAX_PACKETS or not 0 <= int(ip_id_base) <= 0xFFFF:
-        raise ValueError("reply_cap must be a datagram count and ip_id_base a u16")
+    cap = _cap_and_ids(reply_cap, n, ip_id_base, ip_id_add, dev, "reply_cap must be a datagram count")
     ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
-    if ip_id_add is not None:
-        _require_cuda(ip_id_add, "ip_id_add", _I32)
-        if ip_id_add.numel() < 1 or ip_id_add.device != dev:
-            raise ValueError(f"ip_id_add must be an int32 tensor (at least 1 entry) on {dev}")
     status = _status(status, n, dev)
     echo = _new(echo, "echo", n, torch.uint8, dev)
-    tx_blk_first = _new(tx_blk_first, "tx_blk_first", (cap + 63) // 64, torch.int32, dev)
-    tx_head_len8 = _new(tx_head_len8, "tx_head_len8", cap, torch.uint8, dev)
-    tx_pay_len16 = _new(tx_pay_len16, "tx_pay_len16", cap, torch.uint16, dev)
-    tx_src = _new(tx_src, "tx_src", cap, torch.int32, dev)
-    count = _new(count, "count", 3, torch.int32, dev)
+    tx_blk_first, tx_head_len8, tx_pay_len16, tx_src, count = _tx_outputs(cap, dev, tx_blk_first, tx_head_len8, tx_pay_len16,
+                                                                          tx_src, count)
     need = echo_work(n)
     work = _workspace(work, need, dev, torch.int64, f"work needs {need} bytes (echo_work) on {dev}")
     ptr = _nonnull(dev)
@@ -91,65 +83,24 @@ def echo_host(rx_pool: np.ndarray, buf_idx, blk_first, len16, local_ipv4: bytes,
     B = int(buf_bytes)
     log2 = _buf_log2(B, 256)
     ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
-    free = np.asarray(free, dtype=np.uint32).astype(np.int64)
-    n, n_free = len(len16), len(free)
-    cap = n if reply_cap is None else int(reply_cap)
-    tx_bufs = tx_pool.size >> log2
+    n = len(len16)
+    tx = _TxFormHost(tx_pool, free, B, n if reply_cap is None else int(reply_cap), ip_id_base, ip_id_add)
     status, l4_sum, echo = np.zeros(n, np.uint8), np.zeros(n, np.uint16), np.zeros(n, np.uint8)
-    heads, pays, srcs, firsts = [], [], [], []
-    R = F = V = 0
-    full = False
     for i, T, d, st, l4, h, v6 in _host_datagrams(rx_pool, buf_idx, blk_first, len16, ip4, ip6, B, log2):
         status[i], l4_sum[i] = st, l4
         if not (st & _lib.RNS_RX_ACCEPT) or T - h < 4 or (d[6] if v6 else d[9]) != (58 if v6 else 1) or \
                 d[h] != (128 if v6 else 8):
             continue
         pay = d[h + 4:]
-        nfr = 1 + -(-len(pay) // B)
-        R, F = R + 1, F + nfr
-        if full or R > cap or F > n_free:
-            full = True  # (both counts are monotone: every later request is past them too)
-            echo[i] = _lib.RNS_ECHO_REQUEST | _lib.RNS_ECHO_NOBUF
+        echo[i], bufs, ident = tx.take(len(pay), not v6, i)
+        if bufs is None:
             continue
-        bufs = free[F - nfr:F]
-        if (R - 1) % 64 == 0:
-            firsts.append(F - nfr)
-        pays.append(len(pay))
-        srcs.append(i)
-        if (bufs >= tx_bufs).any():
-            echo[i] = _lib.RNS_ECHO_REQUEST | _lib.RNS_ECHO_BADBUF
-            heads.append(0)
-            V += 0 if v6 else 1
-            continue
-        echo[i] = _lib.RNS_ECHO_REQUEST | _lib.RNS_ECHO_BUILT
-        if v6:
-            peer = d[8:24]
-            icmp = bytearray([129, 0, 0, 0])
-            seed = _fold(_be_sum(ip6) + _be_sum(peer) + 4 + len(pay) + 58)
-            ip = bytes([0x60, 0, 0, 0]) + (4 + len(pay)).to_bytes(2, "big") + bytes([58, 64]) + ip6 + peer
-        else:
-            peer = d[12:16]
-            icmp = bytearray(4)
-            seed = 0
-            ipb = bytearray([0x45, 0]) + ((24 + len(pay)) & 0xFFFF).to_bytes(2, "big") + \
-                ((int(ip_id_base) + int(ip_id_add) + V) & 0xFFFF).to_bytes(2, "big") + bytes([0, 0, 64, 1, 0, 0]) + ip4 + peer
-            ipb[10:12] = (_fold(_be_sum(ipb)) ^ 0xFFFF).to_bytes(2, "big")
-            ip = bytes(ipb)
-            V += 1
+        src, peer = (ip6, d[8:24]) if v6 else (ip4, d[12:16])
+        icmp = bytearray([129 if v6 else 0, 0, 0, 0])
+        seed = _fold(_be_sum(ip6) + _be_sum(peer) + 4 + len(pay) + 58) if v6 else 0
         icmp[2:4] = (_fold(seed + _be_sum(icmp) + _be_sum(pay)) ^ 0xFFFF).to_bytes(2, "big")
-        head = ip + bytes(icmp)
-        heads.append(len(head))
-        at = (int(bufs[0]) << log2) + B - len(head)
-        tx_pool[at:at + len(head)] = np.frombuffer(head, dtype=np.uint8)
-        for j in range(nfr - 1):
-            part = pay[j * B:(j + 1) * B]
-            at = int(bufs[1 + j]) << log2
-            tx_pool[at:at + len(part)] = np.frombuffer(part, dtype=np.uint8)
-    # the counts: the answered requests are a prefix of the requests
-    nrep = len(pays)
-    nbuf = int(sum(1 + -(-p // B) for p in pays))
-    return (status, l4_sum, echo, np.array(firsts, dtype=np.uint32), np.array(heads, dtype=np.uint8),
-            np.array(pays, dtype=np.uint16), np.array(srcs, dtype=np.uint32), np.array([nrep, nbuf, V], dtype=np.uint32))
+        tx.place(bufs, _ip_head_bytes(6 if v6 else 4, 58 if v6 else 1, 4 + len(pay), src, peer, ident) + bytes(icmp), pay)
+    return (status, l4_sum, echo) + tx.result()
 
 
 def echo_respond(fd_in: int, fd_out: int, rx_pool: np.ndarray, rx_free: np.ndarray, tx_pool: np.ndarray, tx_free: np.ndarray,
@@ -165,22 +116,9 @@ def echo_respond(fd_in: int, fd_out: int, rx_pool: np.ndarray, rx_free: np.ndarr
     if n == 0:
         return 0, 0, np.zeros(0, np.uint8), np.zeros(3, np.uint32)
     dev = torch.device(device)
-    rows = rx_pool.reshape(-1, B)
-    used = torch.from_numpy(rx_free[:nf].astype(np.int64))
-    d_rx = torch.zeros(rows.shape, dtype=torch.uint8, device=dev)
-    d_rx[used.to(dev)] = torch.from_numpy(rows[rx_free[:nf]]).to(dev)  # the received buffers only
+    d_rx, d_idx, to_dev = _stage_rx(rx_pool, rx_free, nf, B, dev)
     d_tx = torch.zeros(tx_pool.size, dtype=torch.uint8, device=dev)
-    to_dev = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).to(dev)  # noqa: E731
-    out = rx_icmp_echo_pool(d_rx.reshape(-1), to_dev(rx_free[:nf].astype(np.uint32), np.int32),
-                            to_dev(blk_first.astype(np.uint32), np.int32), to_dev(len16, np.int16), local_ipv4, local_ipv6,
-                            d_tx, to_dev(tx_free.astype(np.uint32), np.int32), buf_bytes=B, ip_id_base=ip_id_base)
-    echo, tx_blk_first, tx_head_len8, tx_pay_len16, count = out[2], out[3], out[4], out[5], out[7]
-    cnt = count.cpu().numpy().view(np.uint32)  # the one synchronisation: 12 bytes
-    nrep, nbuf = int(cnt[0]), int(cnt[1])
-    sent = 0
-    if nrep:
-        taken = tx_free[:nbuf].astype(np.int64)
-        tx_pool.reshape(-1, B)[taken] = d_tx.reshape(-1, B)[torch.from_numpy(taken).to(dev)].cpu().numpy()
-        sent = send_batch_pool(fd_out, tx_pool, tx_free[:nbuf], tx_blk_first.cpu().numpy().view(np.uint32)[:(nrep + 63) // 64],
-                               tx_head_len8.cpu().numpy()[:nrep], tx_pay_len16.view(torch.int16).cpu().numpy().view(np.uint16)[:nrep], B)
-    return n, sent, echo.cpu().numpy()[:n], cnt
+    out = rx_icmp_echo_pool(d_rx, d_idx, to_dev(blk_first.astype(np.uint32), np.int32), to_dev(len16, np.int16), local_ipv4,
+                            local_ipv6, d_tx, to_dev(tx_free.astype(np.uint32), np.int32), buf_bytes=B, ip_id_base=ip_id_base)
+    sent, cnt = _send_built(fd_out, tx_pool, tx_free, d_tx, (out[3], out[4], out[5], out[7]), B)
+    return n, sent, out[2].cpu().numpy()[:n], cnt

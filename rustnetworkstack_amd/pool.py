@@ -11,7 +11,8 @@ a datagram is implied by its head length, its payload length and its buffers' in
 ``tx_pool_layout`` computes the index, ``tx_fill_pool`` finalizes on the device
 (rns_tx_fill_pool_dev) and ``send_batch_pool`` sends from that form.  The functions are re-exported
 by ``batch``, whose argument checks they use; ``_pool_batch`` and ``_host_datagrams`` are what the
-verify's consumers (``place``, ``icmp``, ``udp``) share.
+verify's consumers (``place``, ``icmp``, ``udp``) share, ``_cap_and_ids``, ``_tx_outputs``, ``_TxFormHost``,
+``_stage_rx`` and ``_send_built`` what the builders into the transmit form (``icmp``, ``udp``) share.
 """
 from __future__ import annotations
 
@@ -85,6 +86,27 @@ def _np(t, dtype):
     if isinstance(t, torch.Tensor):
         t = t.cpu().numpy()
     return np.ascontiguousarray(t).reshape(-1).view(dtype)
+
+
+def _cap_and_ids(cap, default: int, ip_id_base: int, ip_id_add, dev, what: str) -> int:
+    """A builder's cap (``default`` where None) and IPv4 id arguments, checked; ``what`` names the cap in the
+    message.  Returns the cap."""
+    cap = default if cap is None else int(cap)
+    if not 0 <= cap <= _lib.RNS_CHAIN_MAX_PACKETS or not 0 <= int(ip_id_base) <= 0xFFFF:
+        raise ValueError(f"{what} and ip_id_base a u16")
+    if ip_id_add is not None:
+        _require_cuda(ip_id_add, "ip_id_add", _I32)
+        if ip_id_add.numel() < 1 or ip_id_add.device != dev:
+            raise ValueError(f"ip_id_add must be an int32 tensor (at least 1 entry) on {dev}")
+    return cap
+
+
+def _tx_outputs(cap: int, dev, tx_blk_first, tx_head_len8, tx_pay_len16, tx_src, count):
+    """The transmit form's descriptors for ``cap`` datagrams and the three counts: the caller's tensors, or new ones."""
+    return (_new(tx_blk_first, "tx_blk_first", (cap + 63) // 64, torch.int32, dev),
+            _new(tx_head_len8, "tx_head_len8", cap, torch.uint8, dev),
+            _new(tx_pay_len16, "tx_pay_len16", cap, torch.uint16, dev),
+            _new(tx_src, "tx_src", cap, torch.int32, dev), _new(count, "count", 3, torch.int32, dev))
 
 
 def rx_verify_pool(pool: torch.Tensor, buf_idx: torch.Tensor, blk_first: torch.Tensor, len16: torch.Tensor,
@@ -188,6 +210,103 @@ def _host_datagrams(rx_pool: np.ndarray, buf_idx, blk_first, len16, ip4: bytes, 
             yield (i, T, d) + _verify_host(d, min(T, B), ip4, ip6)
         else:
             yield i, T, b"", _lib.RNS_RX_MALFORMED, 0, 0, False
+
+
+# --- the pool transmit form on the host: what echo_host and send_host are written over ---
+assert (_lib.RNS_ECHO_REQUEST, _lib.RNS_ECHO_BUILT, _lib.RNS_ECHO_NOBUF, _lib.RNS_ECHO_BADBUF) == \
+    (_lib.RNS_UDPTX_SEND, _lib.RNS_UDPTX_BUILT, _lib.RNS_UDPTX_NOBUF, _lib.RNS_UDPTX_BADBUF)
+
+
+def _ip_head_bytes(family: int, proto: int, l4_len: int, src: bytes, dst: bytes, ident: int) -> bytes:
+    """ip_output_v4 / ip_output_v6 (ip.rs:133-177) in front of ``l4_len`` bytes: the lengths as u16, hop limit 64,
+    the IPv4 header checksum filled."""
+    if family == 6:
+        return bytes([0x60, 0, 0, 0]) + (l4_len & 0xFFFF).to_bytes(2, "big") + bytes([proto, 64]) + src + dst
+    ipb = bytearray([0x45, 0]) + ((20 + l4_len) & 0xFFFF).to_bytes(2, "big") + ident.to_bytes(2, "big") + \
+        bytes([0, 0, 64, proto, 0, 0]) + src + dst
+    ipb[10:12] = (_fold(_be_sum(ipb)) ^ 0xFFFF).to_bytes(2, "big")
+    return bytes(ipb)
+
+
+class _TxFormHost:
+    """The allocation of transmit buffers from a free list under a cap, as rns_k_pool_txform.hpp's tx_alloc does
+    it, with the descriptors and counts that go with it: ``take`` per item in order, ``place`` for each built
+    one, ``result`` at the end."""
+
+    def __init__(self, tx_pool: np.ndarray, free, B: int, cap: int, ip_id_base: int = 0, ip_id_add: int = 0):
+        self.pool, self.B, self.log2, self.cap = tx_pool, B, B.bit_length() - 1, cap
+        self.tx_bufs = tx_pool.size >> self.log2
+        self.free = np.asarray(free, dtype=np.uint32).astype(np.int64)
+        self.id0 = int(ip_id_base) + int(ip_id_add)
+        self.R = self.F = self.V = 0
+        self.full = False
+        self.heads, self.pays, self.srcs, self.firsts = [], [], [], []
+
+    def take(self, payload_len: int, v4: bool, src: int):
+        """Item ``src``'s ``(status bits, buffers, IPv4 id)``: the buffers are None unless it is built (NOBUF:
+        past the cap or the free list; BADBUF: a buffer outside the pool, its descriptors kept with a head
+        length of 0 and its id taken)."""
+        nfr = 1 + -(-payload_len // self.B)
+        self.R, self.F = self.R + 1, self.F + nfr
+        if self.full or self.R > self.cap or self.F > len(self.free):
+            self.full = True  # (both counts are monotone: every later item is past them too)
+            return _lib.RNS_ECHO_REQUEST | _lib.RNS_ECHO_NOBUF, None, 0
+        bufs = self.free[self.F - nfr:self.F]
+        if (self.R - 1) % 64 == 0:
+            self.firsts.append(self.F - nfr)
+        self.pays.append(payload_len)
+        self.srcs.append(src)
+        ident = (self.id0 + self.V) & 0xFFFF
+        self.V += 1 if v4 else 0
+        if (bufs >= self.tx_bufs).any():
+            self.heads.append(0)
+            return _lib.RNS_ECHO_REQUEST | _lib.RNS_ECHO_BADBUF, None, ident
+        return _lib.RNS_ECHO_REQUEST | _lib.RNS_ECHO_BUILT, bufs, ident
+
+    def place(self, bufs, head: bytes, payload: bytes):
+        """The head at the end of the first buffer, the payload from the start of the following ones."""
+        self.heads.append(len(head))
+        at = (int(bufs[0]) << self.log2) + self.B - len(head)
+        self.pool[at:at + len(head)] = np.frombuffer(head, dtype=np.uint8)
+        for j in range(len(bufs) - 1):
+            part = payload[j * self.B:(j + 1) * self.B]
+            at = int(bufs[1 + j]) << self.log2
+            self.pool[at:at + len(part)] = np.frombuffer(part, dtype=np.uint8)
+
+    def result(self):
+        """``(tx_blk_first uint32, tx_head_len8 uint8, tx_pay_len16 uint16, tx_src uint32, count uint32 [3])``, the
+        descriptor arrays cut to the built items (a prefix of the items)."""
+        nbuf = int(sum(1 + -(-p // self.B) for p in self.pays))
+        return (np.array(self.firsts, dtype=np.uint32), np.array(self.heads, dtype=np.uint8),
+                np.array(self.pays, dtype=np.uint16), np.array(self.srcs, dtype=np.uint32),
+                np.array([len(self.pays), nbuf, self.V], dtype=np.uint32))
+
+
+def _stage_rx(rx_pool: np.ndarray, rx_free: np.ndarray, nf: int, B: int, dev):
+    """A receive's used buffers on the device: ``(a zeroed pool of rx_pool's shape with the buffers rx_free[:nf]
+    copied in, those indices as buf_idx, to_dev)``; ``to_dev(array, view dtype)`` stages a descriptor array."""
+    def to_dev(a, t):
+        return torch.from_numpy(np.ascontiguousarray(a).view(t)).to(dev)
+    rows = rx_pool.reshape(-1, B)
+    d_rx = torch.zeros(rows.shape, dtype=torch.uint8, device=dev)
+    d_rx[torch.from_numpy(rx_free[:nf].astype(np.int64)).to(dev)] = torch.from_numpy(rows[rx_free[:nf]]).to(dev)
+    return d_rx.reshape(-1), to_dev(rx_free[:nf].astype(np.uint32), np.int32), to_dev
+
+
+def _send_built(fd_out: int, tx_pool: np.ndarray, tx_free: np.ndarray, d_tx: torch.Tensor, outs, B: int):
+    """What a builder left in the device pool ``d_tx``, sent: ``outs`` = its ``(tx_blk_first, tx_head_len8,
+    tx_pay_len16, count)``; the 12-byte count read back (the one synchronisation), only the buffers
+    ``tx_free[:count[1]]`` copied back into ``tx_pool``, ``send_batch_pool`` to ``fd_out``.  Returns ``(datagrams
+    sent, count uint32 [3])``."""
+    tx_blk_first, tx_head_len8, tx_pay_len16, count = outs
+    cnt = _np(count, np.uint32)
+    nb, nbuf = int(cnt[0]), int(cnt[1])
+    if nb == 0:
+        return 0, cnt
+    taken = tx_free[:nbuf].astype(np.int64)
+    tx_pool.reshape(-1, B)[taken] = d_tx.reshape(-1, B)[torch.from_numpy(taken).to(d_tx.device)].cpu().numpy()
+    return send_batch_pool(fd_out, tx_pool, tx_free[:nbuf], _np(tx_blk_first, np.uint32)[:(nb + 63) // 64],
+                           _np(tx_head_len8, np.uint8)[:nb], _np(tx_pay_len16.view(torch.int16), np.uint16)[:nb], B), cnt
 
 
 def recv_batch_pool(fd: int, pool: np.ndarray, free: np.ndarray, buf_bytes: int = 512, mru: int = 2048,

@@ -29,7 +29,8 @@ import torch
 from . import _lib
 from .batch import (_I32, _U8, _U16, _call, _descriptors, _local_addrs, _nonnull, _per_packet, _require_cuda, _status,
                     _work_bytes, _workspace)
-from .pool import _be_sum, _buf_log2, _fold, _host_datagrams, _new, _np, _pool_batch, recv_batch_pool, send_batch_pool
+from .pool import (_be_sum, _buf_log2, _cap_and_ids, _fold, _host_datagrams, _ip_head_bytes, _new, _np, _pool_batch, _send_built,
+                   _stage_rx, _tx_outputs, _TxFormHost, recv_batch_pool, send_batch_pool)
 
 REC = np.dtype([("ip", "u1", 16), ("src", "<u4"), ("off16", "<u4"), ("sport", "<u2"), ("len", "<u2"), ("family", "u1"),
                 ("flags", "u1"), ("pad", "u1", 2)])  # rns_udp_rec
@@ -211,15 +212,9 @@ def udp_demux(fd: int, pool: np.ndarray, free: np.ndarray, ports, local_ipv4: by
         z = np.zeros(0, np.uint8)
         return 0, UdpDemux(z, np.zeros(0, np.uint16), z, np.zeros(0, np.uint32), np.zeros(0, REC),
                            np.zeros(len(ports) + 1, np.uint32), np.zeros(2, np.uint32), z)
-    dev = torch.device(device)
-    rows = pool.reshape(-1, B)
-    used = torch.from_numpy(free[:nf].astype(np.int64))
-    d_rx = torch.zeros(rows.shape, dtype=torch.uint8, device=dev)
-    d_rx[used.to(dev)] = torch.from_numpy(rows[free[:nf]]).to(dev)  # the received buffers only
-    to_dev = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).to(dev)  # noqa: E731
-    r = rx_udp_demux_pool(d_rx.reshape(-1), to_dev(free[:nf].astype(np.uint32), np.int32),
-                          to_dev(blk_first.astype(np.uint32), np.int32), to_dev(len16, np.int16), local_ipv4, local_ipv6,
-                          to_dev(port_table(ports), np.int16) if ports else None, len(ports), buf_bytes=B)
+    d_rx, d_idx, to_dev = _stage_rx(pool, free, nf, B, torch.device(device))
+    r = rx_udp_demux_pool(d_rx, d_idx, to_dev(blk_first.astype(np.uint32), np.int32), to_dev(len16, np.int16), local_ipv4,
+                          local_ipv6, to_dev(port_table(ports), np.int16) if ports else None, len(ports), buf_bytes=B)
     cnt = _np(r.count, np.uint32)  # the one synchronisation the host needs first: 8 bytes
     nrec, nunits = int(cnt[0]), int(cnt[1])
     return n, UdpDemux(_np(r.status, np.uint8), None, _np(r.udp, np.uint8)[:n], _np(r.pos, np.uint32)[:n],
@@ -279,20 +274,11 @@ def tx_udp_send_pool(data: torch.Tensor, rec: torch.Tensor, q_first: torch.Tenso
         if t.data_ptr() & 15:
             raise ValueError(f"{name} must start 16-byte aligned")
     n_free = free.numel()
-    cap = n if send_cap is None else int(send_cap)
-    if not 0 <= cap <= _lib.RNS_CHAIN_MAX_PACKETS or not 0 <= int(ip_id_base) <= 0xFFFF:
-        raise ValueError("send_cap must be a record count and ip_id_base a u16")
+    cap = _cap_and_ids(send_cap, n, ip_id_base, ip_id_add, dev, "send_cap must be a record count")
     ip4, ip6 = _local_addrs(local_ipv4, local_ipv6)
-    if ip_id_add is not None:
-        _require_cuda(ip_id_add, "ip_id_add", _I32)
-        if ip_id_add.numel() < 1 or ip_id_add.device != dev:
-            raise ValueError(f"ip_id_add must be an int32 tensor (at least 1 entry) on {dev}")
     send = _new(send, "send", n, torch.uint8, dev)
-    tx_blk_first = _new(tx_blk_first, "tx_blk_first", (cap + 63) // 64, torch.int32, dev)
-    tx_head_len8 = _new(tx_head_len8, "tx_head_len8", cap, torch.uint8, dev)
-    tx_pay_len16 = _new(tx_pay_len16, "tx_pay_len16", cap, torch.uint16, dev)
-    tx_src = _new(tx_src, "tx_src", cap, torch.int32, dev)
-    count = _new(count, "count", 3, torch.int32, dev)
+    tx_blk_first, tx_head_len8, tx_pay_len16, tx_src, count = _tx_outputs(cap, dev, tx_blk_first, tx_head_len8, tx_pay_len16,
+                                                                          tx_src, count)
     need = udp_send_work(n)
     work = _workspace(work, need, dev, torch.int64, f"work needs {need} bytes (udp_send_work) on {dev}")
     ptr = _nonnull(dev)
@@ -321,14 +307,9 @@ def send_host(data: np.ndarray, rec, q_first, sock_port, local_ipv4: bytes, loca
     n_socks = len(ports)
     if not 1 <= n_socks <= _lib.RNS_UDP_MAX_SOCKS or len(q) < n_socks + 1:
         raise ValueError(f"sock_port needs 1..{_lib.RNS_UDP_MAX_SOCKS} ports and q_first one entry more")
-    free = np.asarray(free, dtype=np.uint32).astype(np.int64)
-    n, n_free = len(rec) if n_recs is None else int(n_recs), len(free)
-    cap = n if send_cap is None else int(send_cap)
-    tx_bufs = tx_pool.size >> log2
+    n = len(rec) if n_recs is None else int(n_recs)
+    tx = _TxFormHost(tx_pool, free, B, n if send_cap is None else int(send_cap), ip_id_base, ip_id_add)
     send = np.zeros(n, np.uint8)
-    heads, pays, srcs, firsts = [], [], [], []
-    R = F = V = 0
-    full = False
     for k in range(min(n, int(q[n_socks]))):
         r = rec[k]
         fam, ln, at = int(r["family"]), int(r["len"]), 16 * int(r["off16"])
@@ -336,47 +317,16 @@ def send_host(data: np.ndarray, rec, q_first, sock_port, local_ipv4: bytes, loca
             continue
         s = max(int(np.searchsorted(q[:n_socks], k, side="right")) - 1, 0)
         pay = data[at:at + ln].tobytes()
-        nfr = 1 + -(-ln // B)
-        R, F = R + 1, F + nfr
-        if full or R > cap or F > n_free:
-            full = True  # (both counts are monotone: every later send is past them too)
-            send[k] = _lib.RNS_UDPTX_SEND | _lib.RNS_UDPTX_NOBUF
+        send[k], bufs, ident = tx.take(ln, fam == 4, k)
+        if bufs is None:
             continue
-        bufs = free[F - nfr:F]
-        if (R - 1) % 64 == 0:
-            firsts.append(F - nfr)
-        pays.append(ln)
-        srcs.append(k)
-        if (bufs >= tx_bufs).any():
-            send[k] = _lib.RNS_UDPTX_SEND | _lib.RNS_UDPTX_BADBUF
-            heads.append(0)
-            V += 1 if fam == 4 else 0
-            continue
-        send[k] = _lib.RNS_UDPTX_SEND | _lib.RNS_UDPTX_BUILT
         ulen = (8 + ln) & 0xFFFF  # udp.rs:152 `as u16`
         dst = r["ip"][:4 if fam == 4 else 16].tobytes()
         src = ip4 if fam == 4 else ip6
         udp = bytearray(int(ports[s]).to_bytes(2, "big") + int(r["sport"]).to_bytes(2, "big") + ulen.to_bytes(2, "big") + b"\0\0")
         udp[6:8] = (_fold(_be_sum(src) + _be_sum(dst) + 17 + ulen + _be_sum(udp) + _be_sum(pay)) ^ 0xFFFF).to_bytes(2, "big")
-        if fam == 6:
-            ip = bytes([0x60, 0, 0, 0]) + ulen.to_bytes(2, "big") + bytes([17, 64]) + ip6 + dst
-        else:
-            ipb = bytearray([0x45, 0]) + ((28 + ln) & 0xFFFF).to_bytes(2, "big") + \
-                ((int(ip_id_base) + int(ip_id_add) + V) & 0xFFFF).to_bytes(2, "big") + bytes([0, 0, 64, 17, 0, 0]) + ip4 + dst
-            ipb[10:12] = (_fold(_be_sum(ipb)) ^ 0xFFFF).to_bytes(2, "big")
-            ip = bytes(ipb)
-            V += 1
-        head = ip + bytes(udp)
-        heads.append(len(head))
-        at = (int(bufs[0]) << log2) + B - len(head)
-        tx_pool[at:at + len(head)] = np.frombuffer(head, dtype=np.uint8)
-        for j in range(nfr - 1):
-            part = pay[j * B:(j + 1) * B]
-            at = int(bufs[1 + j]) << log2
-            tx_pool[at:at + len(part)] = np.frombuffer(part, dtype=np.uint8)
-    nbuf = int(sum(1 + -(-p // B) for p in pays))
-    return UdpSend(send, np.array(firsts, dtype=np.uint32), np.array(heads, dtype=np.uint8), np.array(pays, dtype=np.uint16),
-                   np.array(srcs, dtype=np.uint32), np.array([len(pays), nbuf, V], dtype=np.uint32))
+        tx.place(bufs, _ip_head_bytes(fam, 17, 8 + ln, src, dst, ident) + bytes(udp), pay)
+    return UdpSend(send, *tx.result())
 
 
 def udp_echo(fd_in: int, fd_out: int, rx_pool: np.ndarray, rx_free: np.ndarray, tx_pool: np.ndarray, tx_free: np.ndarray,
@@ -399,28 +349,17 @@ def udp_echo(fd_in: int, fd_out: int, rx_pool: np.ndarray, rx_free: np.ndarray, 
     if n == 0 or not ports:
         return n, 0, np.zeros(n, np.uint8), (0, 0, 0)
     dev = torch.device(device)
-    rows = rx_pool.reshape(-1, B)
-    used = torch.from_numpy(rx_free[:nf].astype(np.int64))
-    d_rx = torch.zeros(rows.shape, dtype=torch.uint8, device=dev)
-    d_rx[used.to(dev)] = torch.from_numpy(rows[rx_free[:nf]]).to(dev)  # the received buffers only
+    d_rx, d_idx, to_dev = _stage_rx(rx_pool, rx_free, nf, B, dev)
     d_tx = torch.zeros(tx_pool.size, dtype=torch.uint8, device=dev)
-    to_dev = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).to(dev)  # noqa: E731
     cap = n if rec_cap is None else int(rec_cap)
     d_rec = torch.zeros(32 * max(cap, 1), dtype=torch.uint8, device=dev)  # zeroed: a record the cut leaves is no send
-    r = rx_udp_demux_pool(d_rx.reshape(-1), to_dev(rx_free[:nf].astype(np.uint32), np.int32),
-                          to_dev(blk_first.astype(np.uint32), np.int32), to_dev(len16, np.int16), local_ipv4, local_ipv6,
-                          to_dev(port_table(ports), np.int16), len(ports), buf_bytes=B, rec_cap=cap, rec=d_rec)
+    r = rx_udp_demux_pool(d_rx, d_idx, to_dev(blk_first.astype(np.uint32), np.int32), to_dev(len16, np.int16), local_ipv4,
+                          local_ipv6, to_dev(port_table(ports), np.int16), len(ports), buf_bytes=B, rec_cap=cap, rec=d_rec)
     s = tx_udp_send_pool(r.data, r.rec, r.q_first, to_dev(np.array(ports, dtype=np.uint16), np.int16), local_ipv4, local_ipv6,
                          d_tx, to_dev(tx_free.astype(np.uint32), np.int32), buf_bytes=B, n_recs=cap, send_cap=send_cap,
                          ip_id_base=ip_id_base)
-    cnt = _np(s.count, np.uint32)  # the one synchronisation: 12 bytes
-    nbuilt, nbuf, ids = int(cnt[0]), int(cnt[1]), int(cnt[2])
-    sent = 0
-    if nbuilt:
-        taken = tx_free[:nbuf].astype(np.int64)
-        tx_pool.reshape(-1, B)[taken] = d_tx.reshape(-1, B)[torch.from_numpy(taken).to(dev)].cpu().numpy()
-        sent = send_batch_pool(fd_out, tx_pool, tx_free[:nbuf], _np(s.tx_blk_first, np.uint32)[:(nbuilt + 63) // 64],
-                               _np(s.tx_head_len8, np.uint8)[:nbuilt], _np(s.tx_pay_len16.view(torch.int16), np.uint16)[:nbuilt], B)
+    sent, cnt = _send_built(fd_out, tx_pool, tx_free, d_tx, (s.tx_blk_first, s.tx_head_len8, s.tx_pay_len16, s.count), B)
+    nbuilt, ids = int(cnt[0]), int(cnt[2])
     udp = _np(r.udp, np.uint8)[:n]
     entries = int(_np(r.count, np.uint32)[0])
     host_built = 0

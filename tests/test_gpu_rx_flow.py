@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_guard import DEV, FILL, Guarded
 from rustnetworkstack_amd import _lib
 from rustnetworkstack_amd.flow import flow_update_work, rx_tcp_flow_update, tx_ack_build
 from rustnetworkstack_amd.place import meta_records, rx_flow_table, rx_tcp_place_pool
@@ -13,9 +14,6 @@ from rx_flow_helper import (ACK, FLOW, META, NONE, P_FLOW, P_TCP, PSH, RES, S_AC
 from rx_place_helper import L4, L6, SENTINEL, body_bytes, key_of, lay_pool, segment
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-G = 64          # guard bytes on both sides of every output
-FILL = 0xEE
 V4A, V4B = bytes([10, 1, 2, 3]), bytes([10, 9, 8, 7])
 V6A = bytes.fromhex("20010db8000000000000000000000042")
 
@@ -24,20 +22,6 @@ V6A = bytes.fromhex("20010db8000000000000000000000042")
 def gpu_present():
     if not torch.cuda.is_available() or _lib.load().rns_device_count() == 0:
         pytest.fail("gpu tests need a GPU (the HIP path has no CPU fallback)")
-
-
-class Guarded:
-    """nbytes of 0xEE on the device between two guards; `t` is the part handed to the call."""
-
-    def __init__(self, nbytes, dtype=torch.uint8):
-        self.big = torch.full((nbytes + 2 * G,), FILL, dtype=torch.uint8, device=DEV)
-        self.n = nbytes
-        self.t = self.big[G:G + nbytes].view(dtype)
-
-    def host(self, dtype):
-        b = self.big.cpu().numpy()
-        assert (b[:G] == FILL).all() and (b[G + self.n:] == FILL).all(), "written outside the array"
-        return b[G:G + self.n].copy().view(dtype)
 
 
 def dev(a):
@@ -49,7 +33,7 @@ def run_update(meta, flows, pend, cap, work=None):
     meta, flows = np.asarray(meta, dtype=META).reshape(-1), np.asarray(flows, dtype=FLOW).reshape(-1)
     n, nfl = meta.size, flows.size
     o_fl, o_seg, o_res = Guarded(40 * nfl), Guarded(8 * n), Guarded(24 * nfl)
-    o_pd = Guarded(8 * nfl * cap, torch.int32)
+    o_pd = Guarded(8 * nfl * cap, dtype=torch.int32)
     d_pend = dev(np.asarray(pend, dtype=np.uint32)).view(torch.int32) if cap else None
     d_meta, d_flows = dev(meta), dev(flows)
     rx_tcp_flow_update(d_meta, d_flows, d_pend, pend_cap=cap, flows_out=o_fl.t, pend_out=o_pd.t if cap else None,
@@ -230,7 +214,7 @@ def test_ack_build(cap_delta):
     heads, n4 = ack_heads_ref(meta, seg, fl, tm, hl, base)
     assert len(heads) == 15 and n4 == 9 and sum(h is None for _, h in heads) == 3
     cap = len(heads) + cap_delta
-    o_out, o_src, o_len, o_n = Guarded(64 * cap), Guarded(4 * cap, torch.int32), Guarded(cap), Guarded(8, torch.int32)
+    o_out, o_src, o_len, o_n = Guarded(64 * cap), Guarded(4 * cap, dtype=torch.int32), Guarded(cap), Guarded(8, dtype=torch.int32)
     d_meta, d_seg = dev(meta), dev(seg)
     work = torch.empty(flow_update_work(meta.size, 5), dtype=torch.uint8, device=DEV)
     tx_ack_build(d_meta, d_seg, dev(fl), torch.from_numpy(tmpl).to(DEV), torch.from_numpy(hl).to(DEV), base, ack_cap=cap,
@@ -300,7 +284,7 @@ def test_ack_build_scan_block_boundaries(n):
         want_out[k, :len(head)] = np.frombuffer(head, dtype=np.uint8)
     want_len = np.array([len(h) for _, h in heads], dtype=np.uint8)
     assert set(want_len[:2].tolist()) == {40, 60}
-    o_out, o_src, o_len, o_n = Guarded(64 * n), Guarded(4 * n, torch.int32), Guarded(n), Guarded(8, torch.int32)
+    o_out, o_src, o_len, o_n = Guarded(64 * n), Guarded(4 * n, dtype=torch.int32), Guarded(n), Guarded(8, dtype=torch.int32)
     tx_ack_build(dev(meta), dev(seg), dev(fl), torch.from_numpy(tmpl).to(DEV), torch.from_numpy(hl).to(DEV), base, ack_cap=n,
                  out=o_out.t, ack_src=o_src.t, ack_len8=o_len.t, n_acks=o_n.t)
     torch.cuda.synchronize()

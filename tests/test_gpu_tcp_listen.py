@@ -8,6 +8,7 @@ import torch
 
 import rx_place_helper as P
 import tcp_listen_helper as H
+from gpu_guard import DEV, Guarded
 from rustnetworkstack_amd import _lib, batch
 from rustnetworkstack_amd.flow import FLOW_DTYPE
 from rustnetworkstack_amd.listen import (ACCEPT_DTYPE, accept_merge, key_hash, listen_host, listen_slots, listen_work, tcp_listen)
@@ -15,8 +16,7 @@ from rustnetworkstack_amd.place import meta_records, rx_flow_table, rx_tcp_place
 from rustnetworkstack_amd.udp import port_table
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-G, FILL, SENT = 64, 0xEE, H.SENTINEL
+SENT = H.SENTINEL
 U, B_ = H.C_UNMATCHED, H.C_BUILT
 
 
@@ -24,24 +24,6 @@ U, B_ = H.C_UNMATCHED, H.C_BUILT
 def gpu_present():
     if not torch.cuda.is_available() or _lib.load().rns_device_count() == 0:
         pytest.fail("gpu tests need a GPU (the HIP path has no CPU fallback)")
-
-
-class Guarded:
-    """nbytes on the device between two guards of 0xEE; `t` is the part handed to the call."""
-
-    def __init__(self, nbytes, init=None, fill=FILL):
-        self.big = torch.full((nbytes + 2 * G,), FILL, dtype=torch.uint8, device=DEV)
-        self.n = nbytes
-        self.t = self.big[G:G + nbytes]
-        if init is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(init).view(np.uint8).reshape(-1)))
-        elif fill != FILL:
-            self.t.fill_(fill)
-
-    def host(self, dtype=np.uint8):
-        b = self.big.cpu().numpy()
-        assert (b[:G] == FILL).all() and (b[G + self.n:] == FILL).all(), "written outside the array"
-        return b[G:G + self.n].copy().view(dtype)
 
 
 def i32(a):

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_guard import DEV, Guarded
 from rustnetworkstack_amd import _lib, batch
 from rustnetworkstack_amd.send import tx_plan_work, tx_tcp_plan, tx_tcp_send
 from tx_plan_helper import (FILL, KEYS, PLAN_CAP, RES, chains_of, edge_specs, heads_ref, mixed_specs, mk, ref_of,
@@ -14,8 +15,6 @@ from rx_flow_helper import FLOW
 from tx_segment_helper import head
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-G = 64          # guard bytes on both sides of every output
 EDGES = edge_specs()
 OUT_DTYPES = {"tmpl": np.uint8, "head_len8": np.uint8, "pay_off": np.uint64, "pay_len": np.uint32, "mss": np.uint16,
               "head_off": np.uint64, "seg_first": np.uint32, "blk_flow": np.uint32, "n": np.uint32, "res": RES,
@@ -27,20 +26,6 @@ IN_KEYS = ("flows", "sq_off", "sq_seq", "sq_len", "mss", "tmpl", "head_len8")
 def gpu_present():
     if not torch.cuda.is_available() or _lib.load().rns_device_count() == 0:
         pytest.fail("gpu tests need a GPU (the HIP path has no CPU fallback)")
-
-
-class Guarded:
-    """nbytes of 0xEE on the device between two guards; `t` is the part handed to the call."""
-
-    def __init__(self, nbytes):
-        self.big = torch.full((nbytes + 2 * G,), FILL, dtype=torch.uint8, device=DEV)
-        self.n = nbytes
-        self.t = self.big[G:G + nbytes]
-
-    def host(self, dtype):
-        b = self.big.cpu().numpy()
-        assert (b[:G] == FILL).all() and (b[G + self.n:] == FILL).all(), "written outside the array"
-        return b[G:G + self.n].copy().view(dtype)
 
 
 def dev(a):

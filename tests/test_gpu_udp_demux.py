@@ -9,12 +9,12 @@ import pytest
 import torch
 
 import udp_demux_helper as H
+from gpu_guard import DEV, FILL, Guarded
 from rustnetworkstack_amd import _lib, batch
 from rustnetworkstack_amd.udp import NO_POS, REC, UdpDemux, demux_host, demux_work, drain, port_table, rx_udp_demux_pool, udp_demux
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-G, FILL, DATAFILL, RECFILL = 64, 0xEE, 0xA5, 0x5A
+DATAFILL, RECFILL = 0xA5, 0x5A
 DGRAM, SOCK, QUEUED, NOROOM = _lib.RNS_UDP_DGRAM, _lib.RNS_UDP_SOCK, _lib.RNS_UDP_QUEUED, _lib.RNS_UDP_NOROOM
 
 
@@ -22,24 +22,6 @@ DGRAM, SOCK, QUEUED, NOROOM = _lib.RNS_UDP_DGRAM, _lib.RNS_UDP_SOCK, _lib.RNS_UD
 def gpu_present():
     if not torch.cuda.is_available() or _lib.load().rns_device_count() == 0:
         pytest.fail("gpu tests need a GPU (the HIP path has no CPU fallback)")
-
-
-class Guarded:
-    """nbytes on the device between two guards of 0xEE; `t` is the part handed to the call."""
-
-    def __init__(self, nbytes, init=None, fill=FILL):
-        self.big = torch.full((nbytes + 2 * G,), FILL, dtype=torch.uint8, device=DEV)
-        self.n = nbytes
-        self.t = self.big[G:G + nbytes]
-        if init is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(init).view(np.uint8).reshape(-1)))
-        elif fill != FILL:
-            self.t.fill_(fill)
-
-    def host(self, dtype=np.uint8):
-        b = self.big.cpu().numpy()
-        assert (b[:G] == FILL).all() and (b[G + self.n:] == FILL).all(), "written outside the array"
-        return b[G:G + self.n].copy().view(dtype)
 
 
 def mask_slack(data, ref, r):

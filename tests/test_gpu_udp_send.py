@@ -11,12 +11,13 @@ import torch
 
 import udp_demux_helper as D
 import udp_send_helper as H
+from gpu_guard import DEV, FILL, Guarded
 from rustnetworkstack_amd import _lib, batch
 from rustnetworkstack_amd.udp import REC, port_table, rx_udp_demux_pool, send_host, tx_udp_send_pool, udp_echo, udp_send_work
+from tx_pool_helper import mask_slack
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
-G, FILL, TXFILL = 64, 0xEE, 0xA5
+TXFILL = 0xA5
 SEND, BUILT, NOBUF, BADBUF = _lib.RNS_UDPTX_SEND, _lib.RNS_UDPTX_BUILT, _lib.RNS_UDPTX_NOBUF, _lib.RNS_UDPTX_BADBUF
 
 
@@ -24,31 +25,6 @@ SEND, BUILT, NOBUF, BADBUF = _lib.RNS_UDPTX_SEND, _lib.RNS_UDPTX_BUILT, _lib.RNS
 def gpu_present():
     if not torch.cuda.is_available() or _lib.load().rns_device_count() == 0:
         pytest.fail("gpu tests need a GPU (the HIP path has no CPU fallback)")
-
-
-class Guarded:
-    """nbytes on the device between two guards of 0xEE; `t` is the part handed to the call."""
-
-    def __init__(self, nbytes, init=None):
-        self.big = torch.full((nbytes + 2 * G,), FILL, dtype=torch.uint8, device=DEV)
-        self.n = nbytes
-        self.t = self.big[G:G + nbytes]
-        if init is not None:
-            self.t.copy_(torch.from_numpy(np.ascontiguousarray(init).view(np.uint8).reshape(-1)))
-
-    def host(self, dtype=np.uint8):
-        b = self.big.cpu().numpy()
-        assert (b[:G] == FILL).all() and (b[G + self.n:] == FILL).all(), "written outside the array"
-        return b[G:G + self.n].copy().view(dtype)
-
-
-def mask_slack(pool, ref, free, blk_first, head_len8, pay_len16, B):
-    """The bytes a datagram may leave unspecified — from its payload's end to the next 16-byte boundary of its
-    last buffer — copied from ref into pool."""
-    for fr, hl in zip(H.expand_replies(free, blk_first, head_len8, pay_len16, B), head_len8):
-        if hl and len(fr) > 1 and fr[-1][2] % 16:
-            k, _, e = fr[-1]
-            pool[k * B + e:k * B + ((e + 15) & ~15)] = ref[k * B + e:k * B + ((e + 15) & ~15)]
 
 
 def run(b, B, *, rec=None, data=None, q_first=None, send_cap=None, n_free=None, bad_at=None, ip_id_base=0, add=0,

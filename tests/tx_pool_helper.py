@@ -61,3 +61,13 @@ def expand(idx, blk_first, hl, pl, buf, n_frags=None):
     ln[head] = hl.astype(np.int64)[owner][head]
     off[head] += (buf - hl.astype(np.int64)[owner][head]).astype(np.uint64)
     return off, ln.astype(np.uint32), first.astype(np.uint32)
+
+
+def mask_slack(pool, ref, free, blk_first, head_len8, pay_len16, B):
+    """The bytes a builder into the transmit form may leave unspecified — from a payload's end to the next
+    16-byte boundary of its last buffer — copied from ref into pool."""
+    from icmp_echo_helper import expand_replies
+    for fr, hl in zip(expand_replies(free, blk_first, head_len8, pay_len16, B), head_len8):
+        if hl and len(fr) > 1 and fr[-1][2] % 16:
+            k, _, e = fr[-1]
+            pool[k * B + e:k * B + ((e + 15) & ~15)] = ref[k * B + e:k * B + ((e + 15) & ~15)]
