@@ -974,6 +974,149 @@ int rns_rx_tcp_listen_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint3
  * NULL bytes or n_pkts > RNS_CHAIN_MAX_PACKETS is RNS_E_INVALID. */
 int rns_rx_tcp_listen_work(uint32_t n_pkts, uint64_t *bytes);
 
+/* TCP connection update: tcp_input for an existing socket in any state the device takes (tcp.rs:622-835)
+ * — the RST hack, the data branch of a socket that is not Established, the ACK field and the state
+ * machine — per flow in batch order.  It is rns_rx_tcp_flow_update_dev with a wider step: the arguments
+ * d_meta, d_flow_in / d_flow_out, d_pend_in / d_pend_out, pend_cap, d_res and d_work, the membership rule
+ * (RNS_PLACE_FLOW and flow < n_flows, ascending datagram index), the overlap and alignment rules (d_ctl:
+ * 4-byte aligned), the behaviour for n_pkts == 0 and n_flows == 0, the argument errors and the guarantee
+ * that nothing outside the arguments is touched are that entry's, with rns_tcp_ctl *d_ctl (n_pkts
+ * records, all written on every call) in place of d_seg.  A flow record of rns_rx_tcp_listen_pool_dev's
+ * accept (RNS_TCP_SYN_RECEIVED) goes in as it is, so accept -> handshake -> request -> close is one
+ * stream of launches.
+ *   Records: a datagram that is no member gets an all-zero record; so do the segment that stops a flow
+ *     and every later segment of that flow.  A consumed segment's record has flow = its flow, act with
+ *     RNS_CTL_CONSUMED and, with RNS_CTL_SEND, the segment send_packet built at that moment: seq (the
+ *     flow's snd_nxt THEN: a SynReceived socket that gets data on its third segment ACKs it before the
+ *     + 1 of tcp.rs:771), ack_num, window, flags; without RNS_CTL_SEND these four are 0.
+ *   Stops, tested before each segment in this order:
+ *     RNS_STOP_MANY     as in the flow update.
+ *     RNS_STOP_STATE    n_pend > pend_cap on input, or the flow's current state is RNS_TCP_SYN_SENT,
+ *                       RNS_TCP_LISTEN or above 10.
+ *     RNS_STOP_OPTIONS  tcp_hdr != 20 (tcp.rs:622-625 needs parse_options).
+ *     (RST set: no further stop; the segment is consumed by step A whatever else it carries.)
+ *     RNS_STOP_FLAGS    SYN set and pay_len > 0: the reference would queue that payload, the placement
+ *                       does not place a SYN's.  A SYN without payload is no stop: the reference never
+ *                       looks at SYN on an existing socket.
+ *     RNS_STOP_OUTSIDE, RNS_STOP_PEND  as in the flow update.
+ *     RNS_STOP_TWICE    pay_len > 0 with FIN in state FIN_WAIT2, or in FIN_WAIT1 unless ACK is set and
+ *                       ack == snd_nxt + 1: the reference sends the data branch's ACK and then the
+ *                       arm's, and a record holds one send.
+ *   Step of a consumed segment; st = the state before it, and the state changes only in A and D:
+ *     A. RST (tcp.rs:635-640): state = CLOSED, act = CONSUMED | RESET | STATE, nothing else of the
+ *        segment is processed: its payload is dropped and its sequence number not checked.  Later
+ *        segments of the flow go on against the Closed socket, as the reference's would.
+ *     B. Data (tcp.rs:642-696), pay_len > 0: rcv_max, add_packet over the pending list, rq_len and
+ *        readable exactly as in the flow update.  st == ESTABLISHED: the flow update's delayed-ACK
+ *        branch, where FIN also forces the immediate ACK (tcp.rs:656); RNS_CTL_ACK_TIMER is
+ *        RNS_SEG_TIMER.  Every other state: ack_timer = 0, delayed_acks untouched, and a send.
+ *        A send is send_packet(FLAG_ACK) (tcp.rs:402-447): RNS_CTL_SEND, flags = 0x10, seq = snd_nxt as
+ *        it is now, ack_num = rcv_nxt, + 1 (wrapping) iff the state at the send is FIN_WAIT1, FIN_WAIT2,
+ *        CLOSING or CLOSE_WAIT and rcv_max == rcv_nxt (tcp.rs:408-417), window as in the flow update,
+ *        n_acks += 1.
+ *     C. ACK field (tcp.rs:698-740), when flags & 0x10 and st is neither CLOSED nor TIME_WAIT: the
+ *        flow update's block unchanged.
+ *     D. The arms (tcp.rs:742-835):
+ *          SYN_RECEIVED  ACK: state ESTABLISHED, snd_nxt += 1, snd_una = ack (unconditional).
+ *          ESTABLISHED   FIN: state CLOSE_WAIT, no send.
+ *          LAST_ACK      ACK (any number): state CLOSED.
+ *          FIN_WAIT1     ACK, FIN and ack == snd_nxt + 1: state TIME_WAIT, RNS_CTL_TIMEWAIT;
+ *                        else FIN: state CLOSING, then a send (the + 1 rule sees CLOSING), RNS_CTL_RESP_TIMER;
+ *                        else ACK and ack == snd_nxt + 1: state FIN_WAIT2.
+ *          FIN_WAIT2     FIN: a send (state still FIN_WAIT2), RNS_CTL_RESP_TIMER, state TIME_WAIT,
+ *                        RNS_CTL_TIMEWAIT.
+ *          CLOSING       ACK: state TIME_WAIT, RNS_CTL_TIMEWAIT.
+ *          CLOSED, CLOSE_WAIT, TIME_WAIT: nothing.
+ *        Every state change sets RNS_CTL_STATE on the record (set_state ran: the host zeroes
+ *        request_retry_count) and RNS_EV_STATE on the flow.
+ *   d_res is rns_tcp_flow_res: n_acks counts the segments sent.  Timers stay the host's, derived from
+ *   the act bits and ack_timer.
+ *   The reference's oddities are pinned, not corrected: a bare FIN to an Established socket gets no ACK
+ *   at all; a FIN with payload there is ACKed without the FIN's + 1; the peer's ACK of our FIN fails
+ *   seq_le(ack, snd_nxt) (snd_nxt is not advanced over the FIN), so it neither trims nor updates the
+ *   window.  SYN_SENT (tcp_open is a blocking application call, and a peer's SYN|ACK carries options)
+ *   and LISTEN (a listen socket is never a flow) are named but the host's.
+ *   Unpinned: trim_head's assert (buf.rs:297), which the reference trips when acked exceeds the
+ *   retransmit queue — reachable through the SynReceived record's snd_una, which holds the peer's
+ *   sequence number; the device just counts acked.  And what the flow update leaves unpinned.
+ * d_work / work_bytes: what rns_rx_tcp_conn_update_work gives for (n_pkts, n_flows). */
+#define RNS_TCP_CLOSED     0u
+#define RNS_TCP_CLOSE_WAIT 3u
+#define RNS_TCP_LAST_ACK   4u
+#define RNS_TCP_FIN_WAIT1  5u
+#define RNS_TCP_FIN_WAIT2  6u
+#define RNS_TCP_CLOSING    7u
+#define RNS_TCP_TIME_WAIT  8u
+#define RNS_TCP_SYN_SENT   9u
+#define RNS_TCP_LISTEN     10u
+typedef struct rns_tcp_ctl {   /* 16 bytes, host byte order */
+    uint32_t flow;             /* whose template the segment is built from */
+    uint32_t seq, ack_num;     /* as send_packet gives them at the moment of the send */
+    uint16_t window;
+    uint8_t  flags;            /* the TCP flags byte of the segment to send */
+    uint8_t  act;              /* RNS_CTL_* */
+} rns_tcp_ctl;
+#define RNS_CTL_CONSUMED   1u   /* the segment was processed (== RNS_SEG_CONSUMED) */
+#define RNS_CTL_SEND       2u   /* a segment is to be sent (== RNS_SEG_ACK) */
+#define RNS_CTL_ACK_TIMER  4u   /* the delayed-ACK timer was started (== RNS_SEG_TIMER) */
+#define RNS_CTL_RESP_TIMER 8u   /* set_response_timer was called */
+#define RNS_CTL_TIMEWAIT   16u  /* the TIME_WAIT timer was set */
+#define RNS_CTL_RESET      32u  /* an RST closed the socket */
+#define RNS_CTL_STATE      64u  /* set_state ran */
+#define RNS_EV_STATE       2u   /* rns_tcp_flow_res.events: the state changed */
+#define RNS_STOP_TWICE     7u
+int rns_rx_tcp_conn_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,
+                               const rns_tcp_flow *d_flow_in, const uint32_t *d_pend_in, uint32_t pend_cap,
+                               rns_tcp_flow *d_flow_out, uint32_t *d_pend_out,
+                               rns_tcp_ctl *d_ctl,          /* n_pkts */
+                               rns_tcp_flow_res *d_res,     /* n_flows */
+                               void *d_work, uint64_t work_bytes, void *stream);
+
+/* The workspace of rns_rx_tcp_conn_update_dev (CPU only): the flow update's value and rules. */
+int rns_rx_tcp_conn_update_work(uint32_t n_pkts, uint32_t n_flows, uint64_t *bytes);
+
+/* Control-segment build: rns_tx_ack_build_dev's contract restated over rns_tcp_ctl records, whatever
+ * wrote them (the connection update, the close step, a host that writes records for
+ * response_timeout).  Control segment k is the k-th record i in ascending i with act & RNS_CTL_SEND and
+ * f = flow < n_flows.  Its head, hl = d_head_len8[f] bytes at d_out + 64 * k, is the flow's template
+ * verbatim except TCP [4..8] = seq, [8..12] = ack_num, [12] = 0x50, [13] = flags, [14..16] = window,
+ * [16..18] = the checksum; IPv4: [2..4] = 40, [4..6] = ip_id_base + *d_ip_id_add (0 without it) + the
+ * IPv4 segments among 0..k-1, mod 2^16, [10..12] = the header checksum; IPv6: [4..6] = 20.  For the
+ * same ACKs the bytes are rns_tx_ack_build_dev's.  d_src[k] = i, d_len8[k] = hl, d_count = (segments,
+ * IPv4 ones), always written.  The caps (out_cap), the counting-only mode (out_cap == 0 allows NULL
+ * d_out / d_src / d_len8) and the malformed-template rule are the ACK build's; a record whose flags
+ * carry SYN (0x02) is treated like a malformed template — slot and id kept, d_len8[k] = 0, nothing
+ * written: a SYN needs the MSS option, which this form does not carry.
+ * A NULL d_count; with n_ctl > 0 a NULL d_ctl / d_work, work_bytes below rns_tx_tcp_ctl_build_work's
+ * or, with n_flows > 0, a NULL d_tmpl / d_head_len8 or tmpl_stride == 0; with out_cap > 0 a NULL d_out
+ * / d_src / d_len8; a d_ctl / d_ip_id_add / d_out / d_src / d_count that is not 4-byte aligned or a
+ * d_work that is not 8-byte aligned; or n_ctl > RNS_CHAIN_MAX_PACKETS is RNS_E_INVALID, all before the
+ * device is touched. */
+int rns_tx_tcp_ctl_build_dev(const rns_tcp_ctl *d_ctl, uint32_t n_ctl, uint32_t n_flows,
+                             const uint8_t *d_tmpl, uint32_t tmpl_stride, const uint8_t *d_head_len8,
+                             uint16_t ip_id_base, const uint32_t *d_ip_id_add /* optional device dword */,
+                             void *d_work, uint64_t work_bytes,
+                             uint8_t *d_out, uint32_t out_cap, uint32_t *d_src, uint8_t *d_len8,
+                             uint32_t *d_count /* 2 */, void *stream);
+
+/* The build's workspace in bytes for n_ctl records (CPU only): non-zero and monotone in n_ctl.
+ * RNS_E_INVALID for a NULL bytes or n_ctl > RNS_CHAIN_MAX_PACKETS. */
+int rns_tx_tcp_ctl_build_work(uint32_t n_ctl, uint64_t *bytes);
+
+/* tcp_close (tcp.rs:195-224) for a batch of sockets, a lane per flow, no workspace.  d_op[f]: 0 none, 1
+ * close.  For op 1 the state decides: ESTABLISHED sends and becomes FIN_WAIT1, CLOSE_WAIT sends and
+ * becomes LAST_ACK, every other state (LISTEN too: its PORT_MAP removal is the host's) neither sends nor
+ * changes.  A flow that sends gets d_ctl[f] = send_packet(FIN | ACK) computed BEFORE the state change,
+ * as tcp.rs:211-219 orders it — flow = f, seq = snd_nxt, ack_num = rcv_nxt (+ 1 in CLOSE_WAIT when
+ * rcv_max == rcv_nxt, never in ESTABLISHED), the window as in the flow update, flags = 0x11, act =
+ * RNS_CTL_SEND | RNS_CTL_RESP_TIMER | RNS_CTL_STATE — and snd_nxt is not advanced (the reference does
+ * not).  Every other flow (op 0, op 1 in a state that does not send, any other op) is copied and its
+ * record is all zero.  d_flow_in == d_flow_out is allowed (any other overlap is not).  n_flows == 0 is
+ * RNS_OK.  With n_flows > 0 a NULL d_flow_in / d_flow_out / d_op / d_ctl, a d_flow_in / d_flow_out /
+ * d_ctl that is not 4-byte aligned, or n_flows >= 2^31 is RNS_E_INVALID, before the device is touched. */
+int rns_tx_tcp_close_dev(const rns_tcp_flow *d_flow_in, rns_tcp_flow *d_flow_out, uint32_t n_flows,
+                         const uint8_t *d_op, rns_tcp_ctl *d_ctl /* n_flows */, void *stream);
+
 /* TCP send planning: tcp_write's window gate (tcp.rs:256-292) and retransmit (tcp.rs:329-348) on the
  * device, with the head fields send_packet sets (tcp.rs:402-447).  It reads the flow records where
  * rns_rx_tcp_flow_update_dev left them and writes exactly the descriptor set rns_tx_segment_dev takes,

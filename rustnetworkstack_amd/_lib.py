@@ -63,6 +63,13 @@ RNS_CONN_NOBUF = 0x20
 RNS_CONN_HOST = 0x40
 RNS_TCP_SYN_RECEIVED = 2  # rns_tcp_flow.state of a connection the listen responder accepted
 RNS_TCP_ESTABLISHED = 1  # rns_tcp_flow.state: the only one the flow update's fast path takes
+# ... and the states the connection update (rns_rx_tcp_conn_update_dev) adds
+RNS_TCP_CLOSED, RNS_TCP_CLOSE_WAIT, RNS_TCP_LAST_ACK, RNS_TCP_FIN_WAIT1, RNS_TCP_FIN_WAIT2 = 0, 3, 4, 5, 6
+RNS_TCP_CLOSING, RNS_TCP_TIME_WAIT, RNS_TCP_SYN_SENT, RNS_TCP_LISTEN = 7, 8, 9, 10
+RNS_CTL_CONSUMED, RNS_CTL_SEND, RNS_CTL_ACK_TIMER, RNS_CTL_RESP_TIMER = 1, 2, 4, 8  # rns_tcp_ctl.act
+RNS_CTL_TIMEWAIT, RNS_CTL_RESET, RNS_CTL_STATE = 16, 32, 64
+RNS_EV_STATE = 0x02
+RNS_STOP_TWICE = 7
 RNS_FLOW_MAX_SEGS = 1024  # a flow's datagrams per flow-update call
 RNS_SEG_CONSUMED = 0x01
 RNS_SEG_ACK = 0x02
@@ -112,6 +119,11 @@ EXPORTED_SYMBOLS = (
     "rns_tx_ack_build_dev",
     "rns_rx_tcp_listen_pool_dev",
     "rns_rx_tcp_listen_work",
+    "rns_rx_tcp_conn_update_dev",
+    "rns_rx_tcp_conn_update_work",
+    "rns_tx_tcp_ctl_build_dev",
+    "rns_tx_tcp_ctl_build_work",
+    "rns_tx_tcp_close_dev",
     "rns_tx_tcp_plan_dev",
     "rns_tx_tcp_plan_work",
     "rns_tx_fill_dev",
@@ -226,6 +238,11 @@ _SIGNATURES = {
     "rns_rx_tcp_listen_pool_dev": (_int, [_vp, _u64, _u32, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _u16, _vp,
                                           _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "rns_rx_tcp_listen_work": (_int, [_u32, ctypes.POINTER(_u64)]),
+    "rns_rx_tcp_conn_update_dev": (_int, [_vp, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
+    "rns_rx_tcp_conn_update_work": (_int, [_u32, _u32, ctypes.POINTER(_u64)]),
+    "rns_tx_tcp_ctl_build_dev": (_int, [_vp, _u32, _u32, _vp, _u32, _vp, _u16, _vp, _vp, _u64, _vp, _u32, _vp, _vp, _vp, _vp]),
+    "rns_tx_tcp_ctl_build_work": (_int, [_u32, ctypes.POINTER(_u64)]),
+    "rns_tx_tcp_close_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _vp]),
     "rns_tx_tcp_plan_dev": (_int, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp, _u16, _vp, _u64, _u32, _vp, _vp,
                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u64, _vp]),
     "rns_tx_tcp_plan_work": (_int, [_u32, ctypes.POINTER(_u64)]),

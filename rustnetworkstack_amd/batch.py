@@ -866,6 +866,11 @@ _UDP_API = ("demux_host", "demux_work", "drain", "port_table", "rx_udp_demux_poo
 # and the TCP listen responder (listen.py): batch.rx_tcp_listen_pool, batch.listen_host, batch.listen_work,
 # batch.tcp_listen, batch.accept_merge, batch.TcpListen.
 _LISTEN_API = ("TcpListen", "accept_merge", "listen_host", "listen_work", "rx_tcp_listen_pool", "tcp_listen")
+# and the TCP connection update, control-segment build and close step (conn.py): batch.rx_tcp_conn_update,
+# batch.tx_tcp_ctl_build, batch.tx_tcp_close, batch.conn_work, batch.conn_update_host, batch.ctl_heads_host,
+# batch.close_host, batch.tcp_conn, batch.CTL_DTYPE.
+_CONN_API = ("CTL_DTYPE", "close_host", "conn_update_host", "conn_work", "ctl_heads_host", "rx_tcp_conn_update", "tcp_conn",
+             "tx_tcp_close", "tx_tcp_ctl_build")
 
 
 def __getattr__(name):
@@ -893,4 +898,7 @@ def __getattr__(name):
     if name in _LISTEN_API:
         from . import listen
         return getattr(listen, name)
+    if name in _CONN_API:
+        from . import conn
+        return getattr(conn, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

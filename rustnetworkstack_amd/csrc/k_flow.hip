@@ -8,22 +8,36 @@ namespace rns {
 
 static uint32_t blocks_of(uint64_t n) { return static_cast<uint32_t>(scan_blocks(n)); }
 
-int launch_flow_update(const FlowArgs &a, hipStream_t st)
+// The launches before the walks: cnt, cursor (moved to each list's end), longs and list are filled, and every
+// datagram that is no flow's has its zero record of rec_dw dwords: d_seg's 2, or d_ctl's 4.  The connection update
+// (k_conn.hip) starts with the same launches.
+int launch_flow_lists(const FlowArgs &a, uint32_t rec_dw, hipStream_t st)
 {
+    if (rec_dw != 2 && rec_dw != 4)
+        return RNS_E_INVALID;
+    const auto count = rec_dw == 2 ? flow_count_kernel : flow_count4_kernel;
     if (a.n_flows == 0) {  // every datagram's record is zero
-        RNS_LAUNCH(flow_count_kernel, blocks_of(a.n_pkts), kScanBlock, st, a);
+        RNS_LAUNCH(count, blocks_of(a.n_pkts), kScanBlock, st, a);
         return RNS_OK;
     }
     RNS_TRY(hip_status(hipMemsetAsync(a.cnt, 0, 4ull * a.n_flows, st)));
     if (a.n_pkts) {
         const uint32_t nb = blocks_of(a.n_flows);
-        RNS_LAUNCH(flow_count_kernel, blocks_of(a.n_pkts), kScanBlock, st, a);
+        RNS_LAUNCH(count, blocks_of(a.n_pkts), kScanBlock, st, a);
         RNS_LAUNCH((scan2_reduce_kernel<FlowCountValue, FlowArgs>), nb, kScanBlock, st, a, static_cast<uint64_t>(a.n_flows),
                    a.part);
         RNS_TRY(launch_scan2_parts(a.part, nb, nullptr, st));
         RNS_LAUNCH(flow_cursor_kernel, nb, kScanBlock, st, a);
         RNS_LAUNCH(flow_scatter_kernel, blocks_of(a.n_pkts), kScanBlock, st, a);
     }
+    return RNS_OK;
+}
+
+int launch_flow_update(const FlowArgs &a, hipStream_t st)
+{
+    RNS_TRY(launch_flow_lists(a, 2, st));
+    if (a.n_flows == 0)
+        return RNS_OK;
     RNS_LAUNCH(flow_walk_lane_kernel, blocks_of(a.n_flows), kScanBlock, st, a);
     if (a.n_pkts >= 2)  // a flow with two datagrams exists only then, and at most n_pkts / 2 of them
         RNS_LAUNCH(flow_walk_wave_kernel, std::min({a.n_flows, a.n_pkts / 2, kFlowWaveGrid}), 64, st, a);

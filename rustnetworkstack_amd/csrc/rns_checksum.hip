@@ -661,31 +661,28 @@ int rns_tx_udp_send_pool_dev(const uint8_t *d_data, uint64_t data_bytes, const r
     return launch_tx_udp(a, static_cast<hipStream_t>(stream));
 }
 
-int rns_rx_tcp_flow_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,
-                               const rns_tcp_flow *d_flow_in, const uint32_t *d_pend_in, uint32_t pend_cap,
-                               rns_tcp_flow *d_flow_out, uint32_t *d_pend_out, rns_rx_tcp_seg *d_seg,
-                               rns_tcp_flow_res *d_res, void *d_work, uint64_t work_bytes, void *stream)
+// The flow update's and the connection update's one validation and marshalling: d_rec = d_seg or d_ctl.
+static int flow_walk_args(FlowArgs &a, const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,
+                          const rns_tcp_flow *d_flow_in, const uint32_t *d_pend_in, uint32_t pend_cap, rns_tcp_flow *d_flow_out,
+                          uint32_t *d_pend_out, void *d_rec, rns_tcp_flow_res *d_res, void *d_work, uint64_t work_bytes)
 {
-    static_assert(sizeof(rns_tcp_flow) == 4 * kFlowDw && sizeof(rns_rx_tcp_seg) == 8 &&
+    static_assert(sizeof(rns_tcp_flow) == 4 * kFlowDw && sizeof(rns_rx_tcp_seg) == 8 && sizeof(rns_tcp_ctl) == 4 * kCtlDw &&
                       sizeof(rns_tcp_flow_res) == 4 * kFlowResDw,
                   "rns_k_args.hpp");
-    if (n_pkts == 0 && n_flows == 0)
-        return RNS_OK;
     const bool pend = n_flows && pend_cap;
-    if (n_pkts > RNS_CHAIN_MAX_PACKETS || n_flows > kFlowMaxFlows || (n_pkts && (!d_meta || !d_seg)) ||
+    if (n_pkts > RNS_CHAIN_MAX_PACKETS || n_flows > kFlowMaxFlows || (n_pkts && (!d_meta || !d_rec)) ||
         (n_flows && (!d_flow_in || !d_flow_out || !d_res)) || (pend && (!d_pend_in || !d_pend_out)) || !d_work ||
-        misaligned(d_meta, 3) || misaligned(d_seg, 3) || misaligned(d_flow_in, 3) || misaligned(d_flow_out, 3) ||
+        misaligned(d_meta, 3) || misaligned(d_rec, 3) || misaligned(d_flow_in, 3) || misaligned(d_flow_out, 3) ||
         misaligned(d_res, 3) || (pend && (misaligned(d_pend_in, 3) || misaligned(d_pend_out, 3))) || misaligned(d_work, 7) ||
         work_bytes < flow_work_bytes(n_pkts, n_flows))
         return RNS_E_INVALID;
     RNS_TRY(check_device());
-    FlowArgs a{};
     a.meta = reinterpret_cast<const uint32_t *>(d_meta);
     a.flow_in = reinterpret_cast<const uint32_t *>(d_flow_in);
     a.pend_in = d_pend_in;
     a.flow_out = reinterpret_cast<uint32_t *>(d_flow_out);
     a.pend_out = d_pend_out;
-    a.seg = reinterpret_cast<uint32_t *>(d_seg);
+    a.rec = static_cast<uint32_t *>(d_rec);
     a.res = reinterpret_cast<uint32_t *>(d_res);
     a.part = static_cast<uint2 *>(d_work);
     a.cnt = static_cast<uint32_t *>(d_work) + 2 * (scan_blocks(n_flows) + 1);
@@ -695,7 +692,76 @@ int rns_rx_tcp_flow_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, u
     a.n_pkts = n_pkts;
     a.n_flows = n_flows;
     a.pend_cap = pend_cap;
+    return RNS_OK;
+}
+
+int rns_rx_tcp_flow_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,
+                               const rns_tcp_flow *d_flow_in, const uint32_t *d_pend_in, uint32_t pend_cap,
+                               rns_tcp_flow *d_flow_out, uint32_t *d_pend_out, rns_rx_tcp_seg *d_seg,
+                               rns_tcp_flow_res *d_res, void *d_work, uint64_t work_bytes, void *stream)
+{
+    if (n_pkts == 0 && n_flows == 0)
+        return RNS_OK;
+    FlowArgs a{};
+    RNS_TRY(flow_walk_args(a, d_meta, n_pkts, n_flows, d_flow_in, d_pend_in, pend_cap, d_flow_out, d_pend_out, d_seg, d_res, d_work,
+                           work_bytes));
     return launch_flow_update(a, static_cast<hipStream_t>(stream));
+}
+
+int rns_rx_tcp_conn_update_dev(const rns_rx_tcp_meta *d_meta, uint32_t n_pkts, uint32_t n_flows,
+                               const rns_tcp_flow *d_flow_in, const uint32_t *d_pend_in, uint32_t pend_cap,
+                               rns_tcp_flow *d_flow_out, uint32_t *d_pend_out, rns_tcp_ctl *d_ctl, rns_tcp_flow_res *d_res,
+                               void *d_work, uint64_t work_bytes, void *stream)
+{
+    if (n_pkts == 0 && n_flows == 0)
+        return RNS_OK;
+    FlowArgs a{};
+    RNS_TRY(flow_walk_args(a, d_meta, n_pkts, n_flows, d_flow_in, d_pend_in, pend_cap, d_flow_out, d_pend_out, d_ctl, d_res, d_work,
+                           work_bytes));
+    return launch_conn_update(a, static_cast<hipStream_t>(stream));
+}
+
+int rns_tx_tcp_ctl_build_dev(const rns_tcp_ctl *d_ctl, uint32_t n_ctl, uint32_t n_flows, const uint8_t *d_tmpl,
+                             uint32_t tmpl_stride, const uint8_t *d_head_len8, uint16_t ip_id_base, const uint32_t *d_ip_id_add,
+                             void *d_work, uint64_t work_bytes, uint8_t *d_out, uint32_t out_cap, uint32_t *d_src,
+                             uint8_t *d_len8, uint32_t *d_count, void *stream)
+{
+    if (!d_count || n_ctl > RNS_CHAIN_MAX_PACKETS || (n_ctl && (!d_ctl || !d_work || work_bytes < ctl_work_bytes(n_ctl))) ||
+        (n_ctl && n_flows && (!d_tmpl || !d_head_len8 || !tmpl_stride)) || (out_cap && (!d_out || !d_src || !d_len8)) ||
+        misaligned(d_ctl, 3) || misaligned(d_ip_id_add, 3) || misaligned(d_out, 3) || misaligned(d_src, 3) ||
+        misaligned(d_count, 3) || misaligned(d_work, 7))
+        return RNS_E_INVALID;
+    RNS_TRY(check_device());
+    CtlArgs a{};
+    a.ctl = reinterpret_cast<const uint32_t *>(d_ctl);
+    a.tmpl = d_tmpl;
+    a.head_len8 = d_head_len8;
+    a.ip_id_add = d_ip_id_add;
+    a.out = d_out;
+    a.src = d_src;
+    a.len8 = d_len8;
+    a.count = d_count;
+    a.part = static_cast<uint2 *>(d_work);
+    a.n_ctl = n_ctl;
+    a.n_flows = n_flows;
+    a.tmpl_stride = tmpl_stride;
+    a.ip_id_base = ip_id_base;
+    a.out_cap = out_cap;
+    return launch_ctl_build(a, static_cast<hipStream_t>(stream));
+}
+
+int rns_tx_tcp_close_dev(const rns_tcp_flow *d_flow_in, rns_tcp_flow *d_flow_out, uint32_t n_flows, const uint8_t *d_op,
+                         rns_tcp_ctl *d_ctl, void *stream)
+{
+    if (n_flows == 0)
+        return RNS_OK;
+    if (n_flows > kFlowMaxFlows || !d_flow_in || !d_flow_out || !d_op || !d_ctl || misaligned(d_flow_in, 3) ||
+        misaligned(d_flow_out, 3) || misaligned(d_ctl, 3))
+        return RNS_E_INVALID;
+    RNS_TRY(check_device());
+    const CloseArgs a{reinterpret_cast<const uint32_t *>(d_flow_in), reinterpret_cast<uint32_t *>(d_flow_out), d_op,
+                      reinterpret_cast<uint32_t *>(d_ctl), n_flows};
+    return launch_conn_close(a, static_cast<hipStream_t>(stream));
 }
 
 int rns_tx_ack_build_dev(const rns_rx_tcp_meta *d_meta, const rns_rx_tcp_seg *d_seg, uint32_t n_pkts,

@@ -1,10 +1,11 @@
 // What every translation unit sees of the entry points that are sequences of launches: their kernel
 // arguments, constants and workspace sizes.  Their kernels are no templates, so each family's header is
 // included by the one translation unit that launches it (k_flow.hip, k_plan.hip, k_echo.hip, k_udp.hip,
-// k_udp_tx.hip, k_listen.hip).
+// k_udp_tx.hip, k_listen.hip, k_conn.hip).
 // (One part of rns_kernels.hpp: the parts are included in order, each after the one it builds on.)
 #pragma once
 
+#include "rns_k_flow_step.hpp"
 #include "rns_k_pool_place.hpp"
 #include "rns_k_pool_txform.hpp"
 #include "rns_k_scan.hpp"
@@ -12,19 +13,13 @@
 namespace rns {
 
 // --- the flow update and the ACK build (rns_k_flow.hpp) ---
-constexpr uint32_t kFlowDw = 10, kFlowResDw = 6, kFlowMaxFlows = 0x7fffffffu;  // (flow indices stay below 2^31)
-constexpr uint32_t kStopNone = 0, kStopMany = 1, kStopState = 2, kStopFlags = 3, kStopOptions = 4, kStopOutside = 5,
-                   kStopPend = 6;
-static_assert(kStopMany == RNS_STOP_MANY && kStopState == RNS_STOP_STATE && kStopFlags == RNS_STOP_FLAGS &&
-                  kStopOptions == RNS_STOP_OPTIONS && kStopOutside == RNS_STOP_OUTSIDE && kStopPend == RNS_STOP_PEND,
-              "rns_checksum.h's stop reasons");
-
+// (kFlowDw, kFlowResDw, kFlowMaxFlows and the stop reasons: rns_k_flow_step.hpp)
 struct FlowArgs {
     const uint32_t *meta;     // 6 dwords per datagram
     const uint32_t *flow_in;  // 10 dwords per flow
     const uint32_t *pend_in;  // pend_cap (seq, len) pairs per flow
     uint32_t *flow_out, *pend_out;
-    uint32_t *seg;            // 2 dwords per datagram
+    uint32_t *rec;            // a record per datagram: d_seg's 2 dwords, or the connection update's d_ctl's 4 (the step's kRecDw)
     uint32_t *res;            // 6 dwords per flow
     uint32_t *cnt, *cursor;   // workspace: n_flows each
     uint32_t *longs;          // workspace: n_flows, the flows with two datagrams or more
@@ -52,6 +47,32 @@ struct AckArgs {
     uint32_t *n_acks;
     uint2 *part;
     uint32_t n_pkts, n_flows, tmpl_stride, ip_id_base, ack_cap;
+};
+
+// --- the connection update, the control-segment build and the close step (rns_k_conn.hpp) ---
+// (The update takes FlowArgs with rec = d_ctl and the flow update's workspace.)
+constexpr uint32_t kCtlDw = 4;
+
+struct CtlArgs {
+    const uint32_t *ctl;       // 4 dwords per record
+    const uint8_t *tmpl, *head_len8;
+    const uint32_t *ip_id_add;
+    uint8_t *out;
+    uint32_t *src;
+    uint8_t *len8;
+    uint32_t *count;
+    uint2 *part;               // workspace: the scan's block sums, blocks + 1
+    uint32_t n_ctl, n_flows, tmpl_stride, ip_id_base, out_cap;
+};
+
+inline uint64_t ctl_work_bytes(uint64_t n_ctl) { return 8ull * (scan_blocks(n_ctl) + 1); }
+
+struct CloseArgs {
+    const uint32_t *flow_in;   // 10 dwords per flow
+    uint32_t *flow_out;
+    const uint8_t *op;
+    uint32_t *ctl;             // 4 dwords per flow
+    uint32_t n_flows;
 };
 
 // --- the send planning (rns_k_plan.hpp) ---

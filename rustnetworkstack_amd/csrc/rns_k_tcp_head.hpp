@@ -1,5 +1,6 @@
 // The byte-order helpers and the one builder of a TCP/IPv4 or TCP/IPv6 head out of a per-flow template
-// (rule, patch, checksum sums, store) that the segmentation, the ACK build and the send planning share.
+// (rule, patch, checksum sums, store) that the segmentation, the ACK build, the control-segment build and the
+// send planning share.
 // Plain integer C++, no wave intrinsics, no LDS: a host compiler takes it (tests/cpp/test_tcp_head.cpp).
 // (The first part of rns_kernels.hpp: it builds on nothing.)
 #pragma once
@@ -91,6 +92,33 @@ struct TcpHeadSum {
         return (t1 & 0xffffu) + (t1 >> 16);
     }
 };
+
+// A final control segment's head (no options, no payload: a pure ACK, a FIN, an RST) out of the template t
+// that tcp_tmpl_ok passed, to the 4-byte aligned o: hl = 40 (v4) / 60 bytes, both checksums filled (tcp.rs:957-973,
+// ip.rs:158-159).  One pass: every dword but the two that hold a checksum is stored as it is summed.
+RNS_HD void tcp_ctl_head_store(uint32_t *o, const uint8_t *t, bool v4, uint32_t hl, uint32_t id, uint32_t seq, uint32_t ack, uint32_t window,
+                               uint32_t flags)
+{
+    const uint32_t ipd = v4 ? 5u : 10u, nd = hl >> 2;
+    const uint32_t kip = v4 ? 2u : ~0u, kl4 = ipd + 4u;
+    uint32_t dip = 0, dl4 = 0;
+    TcpHeadSum hs;
+    for (uint32_t j = 0; j < nd; ++j) {
+        uint32_t d;
+        __builtin_memcpy(&d, t + 4u * j, 4);
+        d = tcp_head_patch(j, d, v4, ipd, id, seq, ack, window, flags, true);
+        hs.add(j, d, v4, ipd);
+        if (j == kip)
+            dip = d;
+        else if (j == kl4)
+            dl4 = d;
+        else
+            o[j] = d;
+    }
+    if (v4)
+        o[2] = dip | (bswap16_u32(hs.ip_csum()) << 16);
+    o[kl4] = dl4 | bswap16_u32(hs.l4_head(20u) ^ 0xffffu);
+}
 
 // Dword d to o at any alignment: one dword store when o is 4-byte aligned (al4), bytes otherwise.  (The
 // segmentation's per-lane write-back keeps its own two loops: through this function the hot kernel's

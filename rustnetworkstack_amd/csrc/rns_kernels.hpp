@@ -27,9 +27,10 @@
 
 // The device code, by kernel family (each part includes the ones it builds on): first the byte-order
 // helpers and the TCP head builder, last the scan and the arguments of the multi-launch entry points.
-// rns_k_flow.hpp, rns_k_plan.hpp, rns_k_echo.hpp, rns_k_udp.hpp, rns_k_udp_tx.hpp and rns_k_listen.hpp hold kernels
-// that are no templates and are not listed: k_flow.hip, k_plan.hip, k_echo.hip, k_udp.hip, k_udp_tx.hip and
-// k_listen.hip, which launch them, include them.
+// rns_k_flow.hpp, rns_k_conn.hpp, rns_k_plan.hpp, rns_k_echo.hpp, rns_k_udp.hpp, rns_k_udp_tx.hpp and rns_k_listen.hpp
+// hold kernels that are no templates and are not listed: k_flow.hip, k_conn.hip, k_plan.hip, k_echo.hip, k_udp.hip,
+// k_udp_tx.hip and k_listen.hip, which launch them, include them (k_flow and k_conn share the lists' launches and the
+// state and step blocks of rns_k_flow_step.hpp; k_conn's walk frames are rns_k_flow_walk.hpp).
 #include "rns_k_tcp_head.hpp"
 #include "rns_k_common.hpp"
 #include "rns_k_rounds.hpp"

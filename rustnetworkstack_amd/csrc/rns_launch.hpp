@@ -2,11 +2,11 @@
 // kernel family so the build compiles them in parallel (the declarations below say what each holds):
 //   k_shapes.hip, k_packed.hip, k_chain.hip, k_stash.hip  the checksum, fill, verify and finalize forms
 //   k_segment.hip, k_place.hip                            TCP segmentation offload, receive placement
-//   k_flow.hip, k_plan.hip, k_echo.hip, k_udp.hip,        the sequences of launches; each includes its own
-//   k_udp_tx.hip, k_listen.hip                            kernels header (rns_k_flow / plan / echo / udp / udp_tx / listen.hpp)
+//   k_flow.hip, k_conn.hip, k_plan.hip, k_echo.hip,       the sequences of launches; each includes its own kernels
+//   k_udp.hip, k_udp_tx.hip, k_listen.hip                 header (rns_k_flow / conn / plan / echo / udp / udp_tx / listen.hpp)
 //   (k_place, k_echo and k_udp, the pool verify's consumers, share rns_k_pool_view.hpp: view, decode, walk;
 //    k_echo and k_udp_tx, the builders into the pool transmit form, rns_k_pool_txform.hpp and launch_build_seq)
-//   k_scan.hip                                            the scan's middle launch, which those six share
+//   k_scan.hip                                            the scan's middle launch, which those seven share
 // rns_checksum.hip holds the device entry points of the C ABI, rns_pipeline.hip the host-resident
 // pipeline and the multi-GPU contexts.
 #pragma once
@@ -170,6 +170,11 @@ int launch_rx_place(const PlaceArgs &a, bool nt, hipStream_t st);
 // k_flow.hip: TCP flow update (count, scan, scatter, walk) and ACK build (scan, build), each a sequence of launches
 int launch_flow_update(const FlowArgs &a, hipStream_t st);
 int launch_ack_build(const AckArgs &a, hipStream_t st);
+int launch_flow_lists(const FlowArgs &a, uint32_t rec_dw, hipStream_t st);  // every flow's datagrams listed (rec_dw: d_seg's 2, d_ctl's 4)
+// k_conn.hip: TCP connection update (the flow update's lists, its own walks), control-segment build (scan, build), close step
+int launch_conn_update(const FlowArgs &a, hipStream_t st);
+int launch_ctl_build(const CtlArgs &a, hipStream_t st);
+int launch_conn_close(const CloseArgs &a, hipStream_t st);
 // k_plan.hip: TCP send planning (plan, scan, cap, finish), a sequence of launches
 int launch_tx_plan(const PlanArgs &a, hipStream_t st);
 // k_echo.hip: the ICMP echo responder (classify, two scans, build), after launch_rx_pool on the same stream

@@ -283,8 +283,8 @@ def accept_merge(accept, keys=None, flows=None, next_seq=None, win_off=None, win
     host already has: returns ``(keys, flows, next_seq, win_off, win_len)`` — ``KEY_DTYPE``, ``FLOW_DTYPE``, uint32,
     uint64, uint32 — with new flow ``len(keys) + a`` = accept a: its key, its state, next_seq = its rcv_nxt and the
     window ``new_win_off[a]`` (default 0) of ``new_win_len`` bytes.  ``place.rx_flow_table(keys)`` is then the next
-    batch's table, in which the new connections' segments match; their state is RNS_TCP_SYN_RECEIVED, so the flow
-    update stops them with RNS_STOP_STATE: the handshake's completion is the host's."""
+    batch's table, in which the new connections' segments match; their state is RNS_TCP_SYN_RECEIVED: the flow
+    update stops them with RNS_STOP_STATE, ``conn.rx_tcp_conn_update`` completes their handshake on the device."""
     acc = _np(accept, np.uint8).view(ACCEPT_DTYPE)
     k0 = _keys([] if keys is None else keys)  # (a KEY_DTYPE array or (address, sport, dport) tuples, as rx_flow_table takes them)
     f0 = np.zeros(0, FLOW_DTYPE) if flows is None else _np(flows, np.uint8).view(FLOW_DTYPE)

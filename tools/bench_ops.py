@@ -95,6 +95,13 @@ batch checksum, on the headline batch (2^20 x 1500 B) and on IMIX:
              over the same number of heads — the floor that classifies nothing; counts, d_conn and the replies and
              accept records of the first 4096 datagrams are compared with listen_host before timing.  Timed once per
              run, whatever --configs names
+* rx_conn  — rns_rx_tcp_conn_update_dev against rns_rx_tcp_flow_update_dev, and the close lifecycle: (a) rx_flow's
+             own bulk shape (behind the placement) and its 2^20-flows shape through both updates in alternating
+             rounds: the cost of the wider step on traffic that needs none of it; (b) 2^20 SynReceived flows, one
+             handshake-completing ACK each (the lane path); (c) 2^18 flows x 4 segments — ACK, request, FIN|ACK,
+             and after rns_tx_tcp_close_dev the last ACK in a second call — followed by rns_tx_tcp_ctl_build_dev.
+             The records, flows and results of a sample are compared with conn_update_host before timing.  Timed
+             once per run, whatever --configs names
 
 Timing: one pair of HIP events around K back-to-back launches on the launch stream,
 median of R rounds.  GB/s counts algorithmic bytes (payload read + result bytes
@@ -241,6 +248,11 @@ def main():
             for shape in args.place_shapes.split(","):
                 r.update(bench_rx_flow(shape, dev, args))
             r.update(bench_rx_flow_wide(dev, args))
+        if "rx_conn" in ops and cfg == args.configs.split(",")[0]:
+            r.update(bench_rx_conn_bulk(dev, args))
+            r.update(bench_rx_conn_wide(dev, args))
+            r.update(bench_rx_conn_handshake(dev, args))
+            r.update(bench_rx_conn_lifecycle(dev, args))
         if "tx_plan" in ops and cfg == args.configs.split(",")[0]:
             for nfl, k in ((1024, 44), (1 << 20, 1)):
                 r.update(bench_tx_plan(nfl, k, dev, args))
@@ -876,6 +888,178 @@ def bench_rx_flow_wide(dev, args, nfl=1 << 20):
     row.update({"consumed": int(r["consumed"].sum()), "acks": int(n_acks[0].item()),
                 "update_GBps_of_floor": round(32 * nfl / med["update"] / 1e6, 1)})
     return {"rx_flow_1M_flows_x1": row}
+
+
+def _conn_sample_check(m, fl, cap, got_fl, got_ctl, got_res, flows):
+    """The device's out records of the flows `flows` (and their datagrams' control records) against conn_update_host
+    over those flows' datagrams alone."""
+    from rustnetworkstack_amd.conn import CTL_DTYPE, conn_update_host
+    from rustnetworkstack_amd.flow import FLOW_DTYPE, RES_DTYPE
+    flows = np.asarray(flows)
+    idx = np.flatnonzero(np.isin(m["flow"], flows))
+    sub = m[idx].copy()
+    sub["flow"] = np.searchsorted(flows, sub["flow"])
+    w_fl, _, w_ctl, w_res = conn_update_host(sub, fl[flows], np.zeros((len(flows), cap, 2), np.uint32) if cap else None, cap)
+    g_ctl = got_ctl.cpu().numpy().reshape(-1).view(CTL_DTYPE)[idx].copy()
+    g_ctl["flow"] = np.where(g_ctl["act"] != 0, np.searchsorted(flows, g_ctl["flow"]), 0)
+    g_res = got_res.cpu().numpy().reshape(-1).view(RES_DTYPE)[flows].copy()
+    stop = g_res["stop"] != 0xFFFFFFFF
+    g_res["stop"][stop] = np.searchsorted(idx, g_res["stop"][stop])
+    assert got_fl.cpu().numpy().reshape(-1).view(FLOW_DTYPE)[flows].tobytes() == w_fl.tobytes(), "rx_conn: flows differ from conn_update_host"
+    assert g_ctl.tobytes() == w_ctl.tobytes() and g_res.tobytes() == w_res.tobytes(), "rx_conn: records differ from conn_update_host"
+
+
+def bench_rx_conn_bulk(dev, args):
+    """rx_flow's bulk shape behind the placement, through the flow update and the connection update."""
+    from rustnetworkstack_amd import _lib
+    from rustnetworkstack_amd.batch import rx_tcp_place_pool
+    from rustnetworkstack_amd.conn import rx_tcp_conn_update
+    from rustnetworkstack_amd.flow import FLOW_DTYPE, RES_DTYPE, flow_update_work, rx_tcp_flow_update
+    from rustnetworkstack_amd.place import META_DTYPE
+    from rustnetworkstack_amd.workloads import LOCAL4, LOCAL6
+    n, nfl, cap = args.place_n or 1 << 20, args.place_flows, 4
+    rb = RxPlaceBatch("bulk", dev, n, nfl, False)
+    rx_tcp_place_pool(rb.pool, rb.d_buf_idx, rb.d_blk_first, rb.d_len16, LOCAL4, LOCAL6, rb.d_table, rb.d_next_seq, rb.d_win_off,
+                      rb.d_win_len, rb.stream, status=rb.status, l4_sum=rb.l4_sum, meta=rb.meta)
+    chunk = min(n, nfl * _lib.RNS_FLOW_MAX_SEGS)
+    meta = rb.meta.reshape(-1)[:24 * chunk]
+    fl0 = np.zeros(nfl, dtype=FLOW_DTYPE)
+    fl0["rcv_nxt"] = fl0["rcv_max"] = rb.d_next_seq.cpu().numpy().view(np.uint32)
+    fl0["snd_wl1"], fl0["state"] = (fl0["rcv_nxt"] - 1) & 0xFFFFFFFF, _lib.RNS_TCP_ESTABLISHED
+    d_fl = torch.from_numpy(fl0.view(np.uint8)).to(dev)
+    d_pd = torch.zeros(nfl * cap * 2, dtype=torch.int32, device=dev)
+    outs = [(torch.empty_like(d_fl), torch.empty_like(d_pd), torch.empty(chunk * w, dtype=torch.uint8, device=dev),
+             torch.empty(nfl * 24, dtype=torch.uint8, device=dev)) for w in (8, 16)]
+    work = torch.empty(flow_update_work(chunk, nfl), dtype=torch.uint8, device=dev)
+    flow = lambda: rx_tcp_flow_update(meta, d_fl, d_pd, pend_cap=cap, flows_out=outs[0][0], pend_out=outs[0][1],  # noqa: E731
+                                      seg=outs[0][2], res=outs[0][3], work=work)
+    conn = lambda: rx_tcp_conn_update(meta, d_fl, d_pd, pend_cap=cap, flows_out=outs[1][0], pend_out=outs[1][1],  # noqa: E731
+                                      ctl=outs[1][2], res=outs[1][3], work=work)
+    flow()
+    conn()
+    torch.cuda.synchronize()
+    assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][3], outs[1][3]), "rx_conn: the two updates differ"
+    _conn_sample_check(meta.cpu().numpy().view(META_DTYPE), fl0, cap, outs[1][0], outs[1][2], outs[1][3], [0, 1, nfl - 1])
+    r = outs[1][3].cpu().numpy().view(RES_DTYPE)
+    row, med = _flow_rows(chunk, nfl, timed_rounds([flow, conn], args.steps, args.rounds), ("flow_update", "conn_update"))
+    row.update({"consumed": int(r["consumed"].sum()), "sends": int(r["n_acks"].sum()),
+                "conn_over_flow": round(med["conn_update"] / med["flow_update"], 4)})
+    del rb
+    torch.cuda.empty_cache()
+    return {"rx_conn_bulk": row}
+
+
+def _conn_wide(dev, args, nfl, state, pay, flags, both, name):
+    from rustnetworkstack_amd.conn import rx_tcp_conn_update
+    from rustnetworkstack_amd.flow import FLOW_DTYPE, RES_DTYPE, flow_update_work, rx_tcp_flow_update
+    from rustnetworkstack_amd.place import META_DTYPE
+    order = np.random.default_rng(20).permutation(nfl).astype(np.uint32)
+    m = np.zeros(nfl, dtype=META_DTYPE)
+    m["flow"], m["seq"], m["pay_len"], m["flags"], m["ip_hdr"], m["tcp_hdr"] = order, 7 * order, pay, flags, 20, 20
+    m["ack"], m["place"] = 5 * order + 1, 7 if pay else 3
+    fl = np.zeros(nfl, dtype=FLOW_DTYPE)
+    f = np.arange(nfl, dtype=np.uint32)
+    fl["rcv_nxt"] = fl["rcv_max"] = 7 * f
+    fl["snd_nxt"], fl["snd_una"], fl["snd_wl1"] = 5 * f, 7 * f - 1, 7 * f - 1
+    fl["delayed_acks"], fl["state"] = f % 5, state
+    t = lambda a: torch.from_numpy(a.view(np.uint8)).to(dev)  # noqa: E731
+    meta, d_fl = t(m), t(fl)
+    outs = [(torch.empty_like(d_fl), torch.empty(nfl * w, dtype=torch.uint8, device=dev), torch.empty(nfl * 24, dtype=torch.uint8, device=dev))
+            for w in (8, 16)]
+    work = torch.empty(flow_update_work(nfl, nfl), dtype=torch.uint8, device=dev)
+    flow = lambda: rx_tcp_flow_update(meta, d_fl, None, pend_cap=0, flows_out=outs[0][0], seg=outs[0][1], res=outs[0][2], work=work)  # noqa: E731
+    conn = lambda: rx_tcp_conn_update(meta, d_fl, None, pend_cap=0, flows_out=outs[1][0], ctl=outs[1][1], res=outs[1][2], work=work)  # noqa: E731
+    conn()
+    torch.cuda.synchronize()
+    _conn_sample_check(m, fl, 0, outs[1][0], outs[1][1], outs[1][2], np.arange(0, nfl, nfl // 997))
+    fns, names = ([flow, conn], ("flow_update", "conn_update")) if both else ([conn], ("conn_update",))
+    if both:
+        flow()
+        torch.cuda.synchronize()
+        assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][2], outs[1][2]), "rx_conn: the two updates differ"
+    r = outs[1][2].cpu().numpy().view(RES_DTYPE)
+    row, med = _flow_rows(nfl, nfl, timed_rounds(fns, args.steps, args.rounds), names)
+    st = outs[1][0].cpu().numpy().view(FLOW_DTYPE)["state"]
+    row.update({"consumed": int(r["consumed"].sum()), "sends": int(r["n_acks"].sum()), "states": np.bincount(st, minlength=11).tolist(),
+                "update_GBps_of_floor": round((24 + 16 + 80 + 24) * nfl / med["conn_update"] / 1e6, 1)})
+    if both:
+        row["conn_over_flow"] = round(med["conn_update"] / med["flow_update"], 4)
+    return {name: row}
+
+
+def bench_rx_conn_wide(dev, args, nfl=1 << 20):
+    """rx_flow's 2^20-flows shape (one in-order 1460-byte segment each) through both updates."""
+    from rustnetworkstack_amd import _lib
+    return _conn_wide(dev, args, nfl, _lib.RNS_TCP_ESTABLISHED, 1460, 0x18, True, "rx_conn_1M_flows_x1")
+
+
+def bench_rx_conn_handshake(dev, args, nfl=1 << 20):
+    """2^20 SynReceived flows, each with its handshake-completing ACK: the lane path."""
+    from rustnetworkstack_amd import _lib
+    return _conn_wide(dev, args, nfl, _lib.RNS_TCP_SYN_RECEIVED, 0, 0x10, False, "rx_conn_1M_handshakes")
+
+
+def bench_rx_conn_lifecycle(dev, args, nfl=1 << 18):
+    """2^18 connections: ACK, request, FIN|ACK in one call, then our close and the last ACK in a second, and the control build."""
+    from rustnetworkstack_amd import _lib
+    from rustnetworkstack_amd.conn import CTL_DTYPE, rx_tcp_conn_update, tx_tcp_close, tx_tcp_ctl_build
+    from rustnetworkstack_amd.flow import FLOW_DTYPE, RES_DTYPE, flow_update_work
+    from rustnetworkstack_amd.place import META_DTYPE
+    rng = np.random.default_rng(21)
+    f = np.arange(nfl, dtype=np.uint32)
+    fl = np.zeros(nfl, dtype=FLOW_DTYPE)
+    fl["rcv_nxt"] = fl["rcv_max"] = 11 * f + 1
+    fl["snd_una"], fl["snd_nxt"], fl["snd_wl1"], fl["state"] = 11 * f, 3 * f, 11 * f, _lib.RNS_TCP_SYN_RECEIVED
+    slot = np.repeat(f, 3)
+    rng.shuffle(slot)                                                   # the connections interleaved; a flow's own order kept
+    rank = np.zeros(3 * nfl, dtype=np.int64)
+    o = np.argsort(slot, kind="stable")
+    rank[o] = np.tile(np.arange(3), nfl)
+    m = np.zeros(3 * nfl, dtype=META_DTYPE)
+    m["flow"], m["ack"], m["ip_hdr"], m["tcp_hdr"], m["window"] = slot, 3 * slot + 1, 20, 20, 0x2000
+    m["seq"] = 11 * slot + 1 + np.where(rank == 2, 100, 0)
+    m["pay_len"], m["flags"] = np.where(rank == 1, 100, 0), np.choose(rank, [0x10, 0x18, 0x11])
+    m["place"] = np.where(rank == 1, 7, 3)
+    m2 = np.zeros(nfl, dtype=META_DTYPE)
+    o2 = rng.permutation(nfl).astype(np.uint32)
+    m2["flow"], m2["seq"], m2["ack"], m2["flags"], m2["ip_hdr"], m2["tcp_hdr"], m2["place"] = o2, 11 * o2 + 102, 3 * o2 + 2, 0x10, 20, 20, 3
+    t = lambda a: torch.from_numpy(a.view(np.uint8)).to(dev)  # noqa: E731
+    d_m, d_m2, d_fl = t(m), t(m2), t(fl)
+    fl1, fl2, fl3 = (torch.empty_like(d_fl) for _ in range(3))
+    ctl1, ctl2 = torch.empty(3 * nfl * 16, dtype=torch.uint8, device=dev), torch.empty(nfl * 16, dtype=torch.uint8, device=dev)
+    cctl = torch.empty(nfl * 16, dtype=torch.uint8, device=dev)
+    res1, res2 = (torch.empty(nfl * 24, dtype=torch.uint8, device=dev) for _ in range(2))
+    op = torch.ones(nfl, dtype=torch.uint8, device=dev)
+    work = torch.empty(flow_update_work(3 * nfl, nfl), dtype=torch.uint8, device=dev)
+    tmpl, hl8 = _flow_templates(nfl, dev)
+    out = torch.empty((nfl, 64), dtype=torch.uint8, device=dev)
+    src, ln8 = torch.empty(nfl, dtype=torch.int32, device=dev), torch.empty(nfl, dtype=torch.uint8, device=dev)
+    cnt = torch.empty(2, dtype=torch.int32, device=dev)
+    first = lambda: rx_tcp_conn_update(d_m, d_fl, None, pend_cap=0, flows_out=fl1, ctl=ctl1, res=res1, work=work)  # noqa: E731
+    close = lambda: tx_tcp_close(fl1, op, flows_out=fl2, ctl=cctl)  # noqa: E731
+    build = lambda: tx_tcp_ctl_build(cctl, nfl, tmpl, hl8, 1, out_cap=nfl, out=out, src=src, len8=ln8, count=cnt, work=work)  # noqa: E731
+    last = lambda: rx_tcp_conn_update(d_m2, fl2, None, pend_cap=0, flows_out=fl3, ctl=ctl2, res=res2, work=work)  # noqa: E731
+
+    def whole():
+        first()
+        close()
+        build()
+        last()
+
+    whole()
+    torch.cuda.synchronize()
+    sample = np.arange(0, nfl, nfl // 499)
+    _conn_sample_check(m, fl, 0, fl1, ctl1, res1, sample)
+    _conn_sample_check(m2, fl2.cpu().numpy().view(FLOW_DTYPE), 0, fl3, ctl2, res2, sample)
+    st = fl3.cpu().numpy().view(FLOW_DTYPE)["state"]
+    assert (st == _lib.RNS_TCP_CLOSED).all() and int(cnt[0].item()) == nfl, "rx_conn: the lifecycle did not close every connection"
+    assert (cctl.cpu().numpy().view(CTL_DTYPE)["flags"] == 0x11).all()
+    r1 = res1.cpu().numpy().view(RES_DTYPE)
+    row, med = _flow_rows(4 * nfl, nfl, timed_rounds([first, close, build, last, whole], args.steps, args.rounds),
+                          ("update_3seg", "close", "ctl_build", "update_last_ack", "whole"))
+    row.update({"consumed": int(r1["consumed"].sum()) + nfl, "sends_first_call": int(r1["n_acks"].sum()), "fins_built": int(cnt[0].item()),
+                "whole_Msegs_per_s": round(4 * nfl / med["whole"] / 1e3, 1)})
+    return {"rx_conn_256k_lifecycles": row}
 
 
 def bench_tx_plan(nfl, k, dev, args, mss=1460):
