@@ -98,6 +98,26 @@ int32_t rns_compute_pseudo_header_checksum(const rns_ipaddr *source_ip, const rn
  * 2. Batch calls (HIP kernels for gfx950)
  * ====================================================================== */
 
+/* What a device entry (every rns_*_dev call below) does with `stream`.
+ *   - Every kernel launch of the call is issued on `stream`, and so is everything the call clears first: a
+ *     sequence of launches zeroes its counters and clears its tables with a kernel of its own, never with a
+ *     memset (a memset node of a captured graph did not repeat its pattern on later replays).
+ *   - The call neither synchronises nor reads device memory on the host: counts, ranks and ids that one launch
+ *     needs from another stay on the device, and a grid is sized from the by-value arguments alone.
+ *   - Everything the call needs from d_work it initialises itself, whatever the workspace held before: poison,
+ *     or what another batch of any shape left there.  Nothing is kept in the library between calls (there are
+ *     no device globals), so calls on different streams share nothing but the arrays they are given.
+ *   - A call, or a chain of calls on one stream (place -> flow update -> ACK build -> plan -> segment; demux ->
+ *     send; listen -> connection update -> control build), may therefore be stream-captured once and replayed
+ *     over new contents of the same arrays.  What is fixed at capture time is exactly what is passed by value:
+ *     the counts and caps, buf_log2, ip_id_base, flags and hints, the local addresses (their bytes are copied
+ *     into the launch) and the pointers.  Everything behind a pointer, d_ip_id_add's dword included, is read
+ *     when the launch runs.
+ * Outside this contract by design: rns_csum_batch_multi_dev (it switches devices and launches on each shard's
+ * stream) and the host-resident entries (rns_csum_batch_host, rns_csum_batch_multi_host, rns_io_*), which copy,
+ * wait and read back.
+ * tests/test_gpu_streams.py holds the pool, TCP and UDP entries to it. */
+
 /* Device-resident batch.  All pointers are device pointers on the current HIP
  * device; `stream` is a hipStream_t (NULL = the null stream).  Packet i is the
  * bytes d_arena[d_off[i] .. d_off[i] + d_len[i]) at any byte alignment; its seed

@@ -22,7 +22,7 @@ int launch_conn_update(const FlowArgs &a, hipStream_t st)
 int launch_ctl_build(const CtlArgs &a, hipStream_t st)
 {
     if (a.n_ctl == 0)
-        return hip_status(hipMemsetAsync(a.count, 0, 8, st));
+        return launch_fill32(a.count, 2, 0u, st);
     const uint32_t nb = blocks_of(a.n_ctl);
     RNS_LAUNCH((scan2_reduce_kernel<CtlValue, CtlArgs>), nb, kScanBlock, st, a, static_cast<uint64_t>(a.n_ctl), a.part);
     RNS_TRY(launch_scan2_parts(a.part, nb, a.count, st));

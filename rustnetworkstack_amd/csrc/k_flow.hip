@@ -20,7 +20,7 @@ int launch_flow_lists(const FlowArgs &a, uint32_t rec_dw, hipStream_t st)
         RNS_LAUNCH(count, blocks_of(a.n_pkts), kScanBlock, st, a);
         return RNS_OK;
     }
-    RNS_TRY(hip_status(hipMemsetAsync(a.cnt, 0, 4ull * a.n_flows, st)));
+    RNS_TRY(launch_fill32(a.cnt, a.n_flows, 0u, st));
     if (a.n_pkts) {
         const uint32_t nb = blocks_of(a.n_flows);
         RNS_LAUNCH(count, blocks_of(a.n_pkts), kScanBlock, st, a);
@@ -47,7 +47,7 @@ int launch_flow_update(const FlowArgs &a, hipStream_t st)
 int launch_ack_build(const AckArgs &a, hipStream_t st)
 {
     if (a.n_pkts == 0)
-        return hip_status(hipMemsetAsync(a.n_acks, 0, 8, st));
+        return launch_fill32(a.n_acks, 2, 0u, st);
     const uint32_t nb = blocks_of(a.n_pkts);
     RNS_LAUNCH((scan2_reduce_kernel<AckValue, AckArgs>), nb, kScanBlock, st, a, static_cast<uint64_t>(a.n_pkts), a.part);
     RNS_TRY(launch_scan2_parts(a.part, nb, a.n_acks, st));

@@ -8,7 +8,8 @@ namespace rns {
 int launch_rx_listen(const ListenArgs &a, hipStream_t st)
 {
     const uint32_t nb = static_cast<uint32_t>(scan_blocks(a.rx.n));
-    RNS_TRY(hip_status(hipMemsetAsync(a.tbl, 0xff, 12ull * a.slots, st)));  // every slot kListenEmpty64, kListenEmpty
+    // every slot kListenEmpty64, kListenEmpty: tbl's 8 and first's 4 bytes per slot lie one after the other
+    RNS_TRY(launch_fill32(reinterpret_cast<uint32_t *>(a.tbl), 3ull * a.slots, kListenEmpty, st));
     RNS_LAUNCH(listen_classify_kernel, nb, kScanBlock, st, a);
     RNS_LAUNCH(listen_resolve_kernel, nb, kScanBlock, st, a);
     RNS_TRY(launch_scan2_parts(a.w.part_a, nb, nullptr, st));

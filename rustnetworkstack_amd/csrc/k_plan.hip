@@ -8,10 +8,9 @@ namespace rns {
 int launch_tx_plan(const PlanArgs &a, hipStream_t st)
 {
     if (a.n_flows == 0) {  // no entry: E = 0 names every block, and the totals are zero
-        RNS_TRY(hip_status(hipMemsetAsync(a.seg_first, 0, 4, st)));
-        RNS_TRY(hip_status(hipMemsetAsync(a.n_out, 0, 8, st)));
-        const uint64_t nblk = (static_cast<uint64_t>(a.seg_cap) + 63) / 64;
-        return nblk ? hip_status(hipMemsetAsync(a.blk_flow, 0, 4 * nblk, st)) : RNS_OK;
+        RNS_TRY(launch_fill32(a.seg_first, 1, 0u, st));
+        RNS_TRY(launch_fill32(a.n_out, 2, 0u, st));
+        return launch_fill32(a.blk_flow, (static_cast<uint64_t>(a.seg_cap) + 63) / 64, 0u, st);
     }
     const uint64_t E = 2ull * a.n_flows;
     const uint32_t nf = static_cast<uint32_t>(scan_blocks(a.n_flows)), nb = static_cast<uint32_t>(scan_blocks(E));

@@ -16,8 +16,8 @@ int launch_rx_udp(const UdpArgs &a, bool nt, hipStream_t st)
         RNS_TRY(launch_scan2_parts(a.part, nb, a.count, st));
         RNS_LAUNCH(udp_prefix_kernel, nb, kScanBlock, st, a, m);
     } else {  // no socket: no entry
-        RNS_TRY(hip_status(hipMemsetAsync(a.count, 0, 8, st)));
-        RNS_TRY(hip_status(hipMemsetAsync(a.q_first, 0, 4, st)));
+        RNS_TRY(launch_fill32(a.count, 2, 0u, st));
+        RNS_TRY(launch_fill32(a.q_first, 1, 0u, st));
     }
     return with_flags(
         [&](auto NT) {

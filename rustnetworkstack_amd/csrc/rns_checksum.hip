@@ -270,7 +270,7 @@ int count_only(uint32_t *d_count, size_t bytes, void *stream)
     if (!d_count || misaligned(d_count, 3))
         return RNS_E_INVALID;
     RNS_TRY(check_device());
-    return hip_status(hipMemsetAsync(d_count, 0, bytes, static_cast<hipStream_t>(stream)));
+    return launch_fill32(d_count, bytes / 4, 0u, static_cast<hipStream_t>(stream));
 }
 
 }  // namespace
@@ -592,8 +592,8 @@ int rns_rx_udp_demux_pool_dev(const uint8_t *d_pool, uint64_t pool_bytes, uint32
         return RNS_E_INVALID;
     if (n_pkts == 0) {  // no datagram: the counts and the empty queues alone
         RNS_TRY(check_device());
-        RNS_TRY(hip_status(hipMemsetAsync(d_count, 0, 8, static_cast<hipStream_t>(stream))));
-        return hip_status(hipMemsetAsync(d_q_first, 0, 4ull * (n_socks + 1), static_cast<hipStream_t>(stream)));
+        RNS_TRY(launch_fill32(d_count, 2, 0u, static_cast<hipStream_t>(stream)));
+        return launch_fill32(d_q_first, n_socks + 1ull, 0u, static_cast<hipStream_t>(stream));
     }
     // every rejection of the verify's and this entry's own, before the device is touched
     if (!pool_rx_valid(d_pool, buf_log2, kUdpMinLog2, d_buf_idx, n_frags, d_blk_first, d_len16, n_pkts, local_ipv4, local_ipv6,

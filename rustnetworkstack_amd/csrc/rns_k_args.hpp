@@ -193,7 +193,7 @@ struct ListenArgs {
 };
 
 // Slots of the key table for n_pkts datagrams: the flow table's rule, a power of two >= 2 * n_pkts and >= 64.
-// The workspace, 8-byte aligned: the table (8 + 4 B per slot, the two arrays one after the other so that one memset
+// The workspace, 8-byte aligned: the table (8 + 4 B per slot, the two arrays one after the other so that one fill
 // clears both; 12 * slots is a multiple of 8), then the build's own.  2^20 datagrams: 28 MiB.
 inline uint64_t listen_work_bytes(uint64_t n_pkts)
 {

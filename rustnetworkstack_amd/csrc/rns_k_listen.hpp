@@ -18,7 +18,7 @@ namespace rns {
 //                              four blocks per workgroup: decides unmatched / candidate from the meta, the
 //                              listen table and the first buffer, leaves a dword per datagram in the
 //                              workspace, and a candidate inserts its key into the open-addressing table
-//                              (cleared to all ones by a memset before the launch).
+//                              (cleared to all ones by a fill kernel before the launch).
 //   2. listen_resolve_kernel   the same decomposition: an unmatched datagram looks s(key) up, decides
 //                              SYN / HOST / LATER / RST, a first SYN walks its options; the workgroup's
 //                              sums of (replies, IPv4 replies) and (accepts, 0).
@@ -137,8 +137,8 @@ __device__ __forceinline__ bool listen_same(const ListenArgs &a, uint32_t r, con
            o.key[5] == k[5];
 }
 
-constexpr uint32_t kListenEmpty = 0xffffffffu;        // a slot's first after the memset
-constexpr unsigned long long kListenEmpty64 = ~0ull;  // a slot's (resident, tag) after the memset: no resident is 2^32 - 1
+constexpr uint32_t kListenEmpty = 0xffffffffu;        // a slot's first after the clear
+constexpr unsigned long long kListenEmpty64 = ~0ull;  // a slot's (resident, tag) after the clear: no resident is 2^32 - 1
 
 // Whether the slot word r (resident | tag << 32) stands for key k of hash h, asked by datagram p.
 __device__ __forceinline__ bool listen_match(const ListenArgs &a, unsigned long long r, uint32_t h, uint32_t p, const uint32_t (&k)[6])

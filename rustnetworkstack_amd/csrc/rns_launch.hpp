@@ -122,6 +122,8 @@ inline int launch(void (*kernel)(const CsumArgs), dim3 grid, dim3 block, size_t 
 
 // k_scan.hip: the scan's one-workgroup middle launch
 int launch_scan2_parts(uint2 *part, uint32_t nb, uint32_t *total2, hipStream_t st);
+// k_scan.hip: p[0..n) = v by a kernel: every clear inside a launch sequence (no memset nodes: see the kernel)
+int launch_fill32(uint32_t *p, uint64_t n, uint32_t v, hipStream_t st);
 
 // A builder into the pool transmit form (rns_k_pool_txform.hpp) over n items: the counts zeroed, classify(blocks),
 // the two scans of its block sums, build(blocks); both return a status.
@@ -129,7 +131,7 @@ template <class Classify, class Build>
 int launch_build_seq(uint32_t *count, const BuildWork &w, uint64_t n, hipStream_t st, Classify classify, Build build)
 {
     const uint32_t nb = static_cast<uint32_t>(scan_blocks(n));
-    RNS_TRY(hip_status(hipMemsetAsync(count, 0, 12, st)));
+    RNS_TRY(launch_fill32(count, 3, 0u, st));
     RNS_TRY(classify(nb));
     RNS_TRY(launch_scan2_parts(w.part_a, nb, nullptr, st));
     RNS_TRY(launch_scan2_parts(w.part_b, nb, nullptr, st));
